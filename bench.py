@@ -15,6 +15,11 @@ dataflow (nonzeros at the key owners, row sums and losses exchanged), the weight
 all-to-all (stale1) as the supplementary `exchange_dataflow` leg; FM: weights and gradients.
 
 Prints ONE JSON line (rank 0).  See DESIGN.md for the byte model behind `roofline`.
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints
+the line (`value`, `ms_per_step`, the per-kernel events of the timed steps).  `--full` adds
+everything else the line has carried: held-out logloss, repeated blocks, the supplementary legs,
+the CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed (dump_outputs).
 """
 import argparse
 import json
@@ -106,6 +111,17 @@ def parse_args():
                     help="xf_tune switches (xf_common.h: key_build, old_weight, lr_gradient, "
                          "owner_pass); repeatable")
     ap.add_argument("--seed", type=int, default=20260926)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: held-out logloss, the repeated "
+                         "blocks, the sustained run, the key-build, FM, Zipf, table-size, "
+                         "first-epoch, N = 8 shape and end-to-end legs, the measured copy peak, "
+                         "the CPU baseline, the N > 1 supplementary dataflows and the sequential "
+                         "per-kernel pass (the --no-* switches above apply inside it).  Without "
+                         "it: set-up, warm-up, the K timed steps, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>"
+                         ".npy (single shard): the minibatch's per-row loss and a fixed, seeded "
+                         "sample of every table's rows (by key), float32 / float64")
     return ap.parse_args()
 
 
@@ -134,19 +150,25 @@ def make_batches(args, rank, nkeys_total, keytab, sample_seed=None, rows=None, n
     S = min(max(0, getattr(args, "signal_keys", 0)) * max(1, nkeys_total // kpg), nkeys_total)
     if S:
         wstar[:S] = np.random.RandomState(args.seed + 2).randn(S).astype(np.float32) * 1.5
-    out = []
-    for _ in range(args.batches if nbatches is None else nbatches):
-        if args.zipf > 0:
-            fid = np.minimum(rng.zipf(args.zipf, size=R * nnz), nkeys_total) - 1
-        else:
-            fid = rng.randint(0, nkeys_total, size=R * nnz)
-        if S:
-            fid.reshape(R, nnz)[:, 0] = rng.randint(0, S, size=R)
+    rowptr = (np.arange(R + 1, dtype=np.uint64) * np.uint64(nnz))
+
+    def finish(fid, u):   # (numpy's gathers release the GIL: the batches run side by side)
         logit = wstar[fid].reshape(R, nnz).sum(axis=1)
-        labels = (rng.rand(R) < 1.0 / (1.0 + np.exp(-logit))).astype(np.int32)
-        rowptr = (np.arange(R + 1, dtype=np.uint64) * np.uint64(nnz))
-        out.append((rowptr, keytab[fid], labels))
-    return out
+        labels = (u < 1.0 / (1.0 + np.exp(-logit))).astype(np.int32)
+        return rowptr.copy(), keytab[fid], labels
+    from concurrent.futures import ThreadPoolExecutor
+    futs = []
+    with ThreadPoolExecutor(max(1, min(8, len(os.sched_getaffinity(0))))) as pool:
+        for _ in range(args.batches if nbatches is None else nbatches):
+            # the draws in one stream, in this order: fids, the signal field, the label coins
+            if args.zipf > 0:
+                fid = np.minimum(rng.zipf(args.zipf, size=R * nnz), nkeys_total) - 1
+            else:
+                fid = rng.randint(0, nkeys_total, size=R * nnz)
+            if S:
+                fid.reshape(R, nnz)[:, 0] = rng.randint(0, S, size=R)
+            futs.append(pool.submit(finish, fid, rng.rand(R)))
+        return [f.result() for f in futs]
 
 
 def bytes_model(model, k, R, NNZ, U, opt, fused=False, fused_fm=False):
@@ -1136,6 +1158,37 @@ def summary_of(out):
     return {k: r3(v) for k, v in s.items() if v is not None}
 
 
+DUMP_ROWS = 1 << 20     # table rows x dim sampled per table by --dump-outputs
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, trainer, R):
+    """--dump-outputs: what a caller of the timed step has after its last one — the minibatch's
+    per-row loss (p - y, float32) and the tables (Table.export: sorted by key).  A table's rows
+    beyond DUMP_ROWS / dim are a fixed sample (RandomState(0) over the key-sorted rows, so two
+    builds that hold the same keys dump the same ones); a key is written as its high and low
+    32 bits in float64 (exact)."""
+    from xflow_amd import capi
+    arrs = {"loss": trainer.ws.fetch_loss(R)}
+    for name, t in (("w", trainer.w), ("v", trainer.v)):
+        if t is None:
+            continue
+        keys, w, n, z = t.export()
+        take = min(len(keys), max(1, DUMP_ROWS // t.dim))
+        idx = np.arange(len(keys)) if take == len(keys) else \
+            np.sort(np.random.RandomState(0).choice(len(keys), size=take, replace=False))
+        arrs[name + "_key_hi"] = (keys[idx] >> np.uint64(32)).astype(np.float64)
+        arrs[name + "_key_lo"] = (keys[idx] & np.uint64(0xFFFFFFFF)).astype(np.float64)
+        arrs[name + "_w"] = w[idx]
+        if t.opt == capi.OPT_FTRL:   # (SGD tables have no n, z)
+            arrs[name + "_n"], arrs[name + "_z"] = n[idx], z[idx]
+    assert sum(a.nbytes for a in arrs.values()) <= DUMP_MAX_BYTES
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        assert a.dtype in (np.float32, np.float64), k
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def spread(ms):
     ms = sorted(ms)
     return {"median": ms[len(ms) // 2], "min": ms[0], "max": ms[-1], "n": len(ms)}
@@ -1529,6 +1582,8 @@ def main():
         args.keys_per_gpu = 10_000_000 if world == 1 else 12_500_000
     if args.optimizer is None:
         args.optimizer = "ftrl" if args.model == "lr" else "sgd"
+    if args.dump_outputs and (world > 1 or args.force_sharded):
+        raise SystemExit("bench.py --dump-outputs: single-shard runs only")
     import torch
     from xflow_amd import capi
     if not torch.cuda.is_available():
@@ -1593,15 +1648,17 @@ def main():
     compiled = [trainer.compile(*b) for b in batches]
     # the logloss half of BASELINE's metric: held-out rows from the same generator (same ground
     # truth; SURVEY 8d config 2: 10^5 rows), scored before the first step and after the last
+    # (--full)
     held = hb = None
-    try:
-        held = make_batches(args, rank, nkeys_total, keytab,
-                            sample_seed=args.seed + 7919 + 1000 * rank, rows=args.heldout_rows,
-                            nbatches=1)[0]
-        hb = trainer.compile(*held)
-    except Exception as e:   # (collective at N > 1: a failure here is every rank's)
-        print("bench.py: held-out minibatch: %s" % e, file=sys.stderr)
-        held = hb = None
+    if args.full:
+        try:
+            held = make_batches(args, rank, nkeys_total, keytab,
+                                sample_seed=args.seed + 7919 + 1000 * rank,
+                                rows=args.heldout_rows, nbatches=1)[0]
+            hb = trainer.compile(*held)
+        except Exception as e:   # (collective at N > 1: a failure here is every rank's)
+            print("bench.py: held-out minibatch: %s" % e, file=sys.stderr)
+            held = hb = None
 
     def heldout_logloss():
         res = trainer.predict(hb)
@@ -1686,10 +1743,13 @@ def main():
     kern_ms, ksteps = trainer.profile_read()
     trainer.profile(False)
     trainer.check()
-    # the same K-step block again, `--repeats` times: how far `ms_per_step` of ONE block is
-    # from the typical one (profiling off here: no event packets in the stream)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, trainer,
+                     compiled[(args.warmup + args.steps - 1) % len(compiled)].R)
+    # (--full) the same K-step block again, `--repeats` times: how far `ms_per_step` of ONE
+    # block is from the typical one (profiling off here: no event packets in the stream)
     rep_ms = []
-    for rep in range(args.repeats):
+    for rep in range(args.repeats if args.full else 0):
         barrier()
         t1 = time.perf_counter()
         for i in range(args.steps):
@@ -1700,7 +1760,8 @@ def main():
         rep_ms.append(allmax(time.perf_counter() - t1) / args.steps * 1e3)
     trainer.check()
     sustained = None
-    if world == 1 and not sharded and args.model == "lr" and args.sustained_seconds > 0:
+    if args.full and world == 1 and not sharded and args.model == "lr" \
+            and args.sustained_seconds > 0:
         try:
             sustained = sustained_leg(args, trainer, compiled, dt / args.steps * 1e3)
         except Exception as e:   # the throughput line must not depend on this extra
@@ -1710,7 +1771,10 @@ def main():
                     "records, into a ring of event sets: the host never waits for a step it " \
                     "has just launched; the averages are over those sampled steps, so their " \
                     "sum need not equal ms_per_step to the microsecond)"
-    if sharded and not any(kern_ms.values()):
+    if sharded and not any(kern_ms.values()) and not args.full:
+        kernel_timing = "none: the timed region overlaps two streams (--full: a sequential " \
+                        "pass of 8 steps after it)"
+    elif sharded and not any(kern_ms.values()):
         # the overlapped schedule runs two streams: per-kernel events are taken in a short
         # sequential pass after the timed region instead
         if hasattr(trainer, "set_schedule"):
@@ -1737,33 +1801,36 @@ def main():
             trainer.check()
     dt = allmax(dt)
     # ... and after the last step (warm-up + the K timed steps + the repeats)
-    steps_trained = args.warmup + args.steps * (1 + args.repeats) + \
+    steps_trained = args.warmup + args.steps * (1 + len(rep_ms)) + \
         (sustained.get("steps", 0) if sustained else 0)
-    try:
-        if hb is None:
-            raise RuntimeError("no held-out minibatch (see stderr)")
-        logloss = heldout_logloss()
-        logloss.update({
-            "rows": int(len(held[2])), "steps_trained": steps_trained,
-            "distinct_minibatches_trained_on": min(len(compiled), args.warmup + args.steps),
-            "before_training": logloss_before,
-            "note": "held-out rows of rank 0 from the bench stream's generator, scored before "
-                    "the first and after the last step of this run (every rank scores its own; "
-                    "the exchange is collective); reference_format = mean(y*log2 p + (1-y)*log2"
-                    "(1-p)), base.h:97-100.  The signal the weights pick up is the "
-                    "low-cardinality field's (--signal-keys): with gradients scaled by 1/R and "
-                    "the reference's alpha, lambda1, lambda2 the once-per-minibatch keys stay "
-                    "inside the L1 dead zone for the whole run.  GPU and oracle side by side on "
-                    "the same stream: cpu_baseline.gpu_vs_oracle.heldout_logloss"})
-    except Exception as e:  # the throughput line must not depend on this extra
-        logloss = {"error": str(e)}
+    logloss = None   # (--full)
+    if args.full:
+        try:
+            if hb is None:
+                raise RuntimeError("no held-out minibatch (see stderr)")
+            logloss = heldout_logloss()
+            logloss.update({
+                "rows": int(len(held[2])), "steps_trained": steps_trained,
+                "distinct_minibatches_trained_on": min(len(compiled), args.warmup + args.steps),
+                "before_training": logloss_before,
+                "note": "held-out rows of rank 0 from the bench stream's generator, scored "
+                        "before the first and after the last step of this run (every rank "
+                        "scores its own; the exchange is collective); reference_format = "
+                        "mean(y*log2 p + (1-y)*log2(1-p)), base.h:97-100.  The signal the "
+                        "weights pick up is the low-cardinality field's (--signal-keys): with "
+                        "gradients scaled by 1/R and the reference's alpha, lambda1, lambda2 the "
+                        "once-per-minibatch keys stay inside the L1 dead zone for the whole "
+                        "run.  GPU and oracle side by side on the same stream: "
+                        "cpu_baseline.gpu_vs_oracle.heldout_logloss"})
+        except Exception as e:  # the throughput line must not depend on this extra
+            logloss = {"error": str(e)}
     # Supplementary leg (N > 1, LR, C++ trainer): the same K steps on the OWNER-COMPUTE dataflow
     # (XF_SCHEDULE_OWNER: nonzeros at the key owners, row sums and losses exchanged) on a second
     # trainer over the same group.  Not `value`; every rank takes part; a failure is reported,
     # not raised (it is symmetric across the ranks: the condition depends on the arguments only).
     owner_leg = None
     other = "stale1" if owner_df else "owner"
-    if group is not None and args.model == "lr" and not args.no_owner_leg \
+    if args.full and group is not None and args.model == "lr" and not args.no_owner_leg \
             and (world > 1 or args.general_path):
         try:
             ot = NativeSharded(group, args, other, capacity)
@@ -1820,7 +1887,7 @@ def main():
     # LRWorker::update on the ranks' minibatches laid end to end) instead of one per rank.  The
     # owner's gradient + Push pass then is the one-source pass whatever N.  Not `value`.
     sum_leg = None
-    if group is not None and args.model == "lr" and owner_df and world > 1 \
+    if args.full and group is not None and args.model == "lr" and owner_df and world > 1 \
             and not args.no_owner_leg:
         try:
             st2 = NativeSharded(group, args, "owner", capacity, update="sum_then_step")
@@ -1850,7 +1917,8 @@ def main():
         except Exception as e:
             sum_leg = {"error": str(e)}
     wkb_sharded = None
-    if group is not None and (world > 1 or args.general_path) and args.model == "lr" \
+    if args.full and group is not None and (world > 1 or args.general_path) \
+            and args.model == "lr" \
             and args.key_build_steps > 0 and hasattr(trainer, "st"):
         try:   # (collective: every rank; a failure is symmetric)
             wkb_sharded = with_key_build_sharded(args, trainer, batches, R, world, barrier,
@@ -1863,7 +1931,8 @@ def main():
         imbalance = {"owned_keys_per_step_by_rank": [float(x) for x in own],
                      "max_over_mean": float(own.max() / own.mean()) if own.mean() > 0 else None}
     fm_sharded = None
-    if world > 1 and group is not None and args.model == "lr" and not args.no_fm_leg:
+    if args.full and world > 1 and group is not None and args.model == "lr" \
+            and not args.no_fm_leg:
         err = None   # (collective: every rank, before the ranks other than 0 leave)
         try:
             fm_sharded = fm_leg_sharded(args, batches, group, world, barrier, allmax)
@@ -1988,11 +2057,12 @@ def main():
         "step_bytes_survey_8d": survey_bytes,
         "step_gbs_survey_8d": survey_bytes / (ms_per_step * 1e-3) / 1e9,
     }
-    if world == 1:
+    if args.full and world == 1:
         copy = stream_copy_gbs()
         out["roofline"]["peak_measured_copy"] = copy
         out["roofline"]["frac_of_measured_copy"] = achieved / copy if copy > 0 else None
-    if world == 1 and not args.force_sharded and args.model == "lr" and args.key_build_steps > 0:
+    if args.full and world == 1 and not args.force_sharded and args.model == "lr" \
+            and args.key_build_steps > 0:
         out["with_key_build"] = with_key_build(args, trainer, batches)
     if wkb_sharded is not None:
         out["with_key_build"] = wkb_sharded
@@ -2004,14 +2074,16 @@ def main():
         out["config"]["with_key_build_ms"] = out["with_key_build"]["ms_per_step"]
     if fm_sharded is not None:
         out["fm"] = fm_sharded
-    if world == 1 and not args.force_sharded and args.model == "lr" and not args.no_fm_leg:
+    if args.full and world == 1 and not args.force_sharded and args.model == "lr" \
+            and not args.no_fm_leg:
         del compiled, trainer, hb  # (the FM tables want the memory's bandwidth to themselves)
         trainer = hb = None
         try:
             out["fm"] = fm_leg(args, batches)
         except Exception as e:   # the LR line must not depend on this extra
             out["fm"] = {"error": str(e)}
-    if world == 1 and not args.force_sharded and args.model == "lr" and not args.zipf:
+    if args.full and world == 1 and not args.force_sharded and args.model == "lr" \
+            and not args.zipf:
         compiled = trainer = hb = None
         if not args.no_zipf_leg:
             try:
@@ -2025,7 +2097,8 @@ def main():
                 out["table_sweep"] = {"error": str(e)}
     if sustained is not None:
         out["sustained"] = sustained
-    if world == 1 and not args.force_sharded and args.model == "lr" and not args.zipf:
+    if args.full and world == 1 and not args.force_sharded and args.model == "lr" \
+            and not args.zipf:
         if not args.no_fresh_table:
             out["fresh_table"] = []
             for nk in [int(x) for x in args.fresh_keys.split(",") if x]:
@@ -2043,15 +2116,16 @@ def main():
     if args.pmc_calibrate:
         for kind in range(10):
             capi.check(capi.lib().xf_calib_stream(kind, 1 << 30, 3))
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, batches, held)
-    if not args.no_cpu_baseline and world == 1 and args.model == "lr":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.model == "lr":
         try:
             out["logloss"]["learning_check"] = learning_check(args.seed + 5)
         except Exception as e:   # the throughput line must not depend on this extra
             out["logloss"]["learning_check"] = {"error": str(e)}
     out["end_to_end"] = None
-    if world == 1 and not args.force_sharded and args.model == "lr" and not args.no_end_to_end:
+    if args.full and world == 1 and not args.force_sharded and args.model == "lr" \
+            and not args.no_end_to_end:
         try:   # the worker on a text file, fresh processes: measured here, on a small file
             out["end_to_end"] = end_to_end_leg()
         except Exception as e:

@@ -5,7 +5,7 @@ Runs ONLY in the build container (needs /root/reference and oracle/_ref, the sub
 the real reference that compiles from its own sources: src/io + src/base).  The outputs
 are data (inputs + expected outputs); no reference source text is stored.
 
-  python tests/golden/make_golden.py
+  python tests/golden/make_golden.py [--live]     (--live: (6) alone)
 """
 import json
 import os
@@ -84,8 +84,38 @@ def main():
             keys=np.concatenate([b[1] for b in blocks]),
             fgid=np.concatenate([b[2] for b in blocks]),
             labels=np.concatenate([b[3] for b in blocks]))
+    live_vectors()
     print("golden vectors written to", HERE)
 
 
+def live_vectors():
+    """(6) the real code's answers to the fuzz inputs of tests/test_oracle.py and
+    tests/test_capi_cpu.py (hash, sigmoid, parser edge cases at several block sizes): those
+    tests compare against these wherever oracle/_ref is not built"""
+    import tempfile
+    from tests.test_capi_cpu import sigmoid_fuzz_inputs
+    from tests.test_oracle import PARSER_CAPS, parser_cases, random_strings
+    assert O.ref_available(), "build oracle/_ref first: make -C oracle"
+    R = O.ref()
+    out = {"hash": np.array([R.ref_hash(b, len(b)) for b in random_strings()], np.uint64),
+           "sigmoid": np.array([R.ref_sigmoid(x) for x in sigmoid_fuzz_inputs()], np.float32)}
+    with tempfile.TemporaryDirectory() as d:
+        for nm, txt in parser_cases().items():
+            p = os.path.join(d, nm)
+            with open(p, "w") as f:
+                f.write(txt)
+            for cap in PARSER_CAPS:
+                tag = "parse_%s_%d" % (nm, cap)
+                blocks = list(O.ref_read_blocks(p, cap))
+                out[tag + "_n"] = np.array(len(blocks), np.int64)
+                for i, b in enumerate(blocks):
+                    for j, a in enumerate(b):
+                        out["%s_%d_%d" % (tag, i, j)] = a
+    np.savez_compressed(os.path.join(HERE, "ref_live_vectors.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--live"]:   # (6) alone
+        live_vectors()
+    else:
+        main()

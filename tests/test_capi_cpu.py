@@ -431,14 +431,24 @@ def test_auc_logloss_fuzz_three_way(seed):
             assert line == O.format_auc_line(oll, oauc, otp, ofp)
 
 
-def test_sigmoid_fuzz_vs_live_ref():
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built")
+def sigmoid_fuzz_inputs():
+    """(tests/golden/make_golden.py records the reference's answers to these)"""
     rng = np.random.RandomState(9)
     xs = np.concatenate([rng.uniform(-40, 40, 4000), rng.normal(0, 1e-3, 500),
                          [-30.0, 30.0, -30.000002, 30.000002, 0.0, -0.0, 88.0, -104.0]])
-    for x in xs.astype(np.float32):
-        assert O.sigmoid(x) == O.ref().ref_sigmoid(C_float(x)), x
+    return xs.astype(np.float32)
+
+
+def test_sigmoid_fuzz_vs_live_ref(golden_dir):
+    """the recorded answers of the reference's Base::sigmoid (tests/golden/ref_live_vectors.npz),
+    and the live oracle/_ref's where it is built"""
+    want = np.load(os.path.join(golden_dir, "ref_live_vectors.npz"))["sigmoid"]
+    xs = sigmoid_fuzz_inputs()
+    assert want.shape == xs.shape
+    for x, y in zip(xs, want):
+        assert O.sigmoid(x) == y, x
+        if O.ref_available():
+            assert O.ref().ref_sigmoid(C_float(x)) == y, x
 
 
 @pytest.mark.parametrize("cap", [202, 777, 1 << 20])

@@ -96,7 +96,7 @@ def test_bench_runs_two_ranks_and_reports_them(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2",
                           "--transport", "host", "--rows", "3000", "--nnz-per-row", "50",
                           "--keys-per-gpu", "200000", "--batches", "3", "--steps", "5",
-                          "--warmup", "2"], capture_output=True, text=True, timeout=240,
+                          "--warmup", "2", "--full"], capture_output=True, text=True, timeout=240,
                          env=dict(os.environ, MASTER_PORT=str(free_port()),
                                   XF_COLLECTIVE_TIMEOUT_S="60"))
     assert out.returncode == 0, out.stderr[-2000:]
@@ -117,6 +117,43 @@ def test_bench_runs_two_ranks_and_reports_them(tmp_path):
     # FM over both ranks on the owner-compute dataflow (sum_then_step)
     fm = line["fm"]
     assert "error" not in fm and fm["value"] > 0 and "sum_then_step" in fm["dataflow"]
+
+
+def test_bench_plain_run_dumps_what_its_last_step_computed(tmp_path, monkeypatch):
+    """`python bench.py` without --full: the headline line alone, and --dump-outputs writes the
+    table after the W + K steps — bit for bit the exact-sum oracle's after the same minibatches
+    (regenerated here from the bench's seed), keys exact in their two float64 halves."""
+    import json
+    import sys
+    import bench
+    argv = ["--rows", "3000", "--nnz-per-row", "50", "--keys-per-gpu", "200000", "--batches",
+            "3", "--steps", "5", "--warmup", "2"]
+    d = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + argv +
+                         ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "examples/sec" and line["unit"] == "examples/sec"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 5
+    assert abs(line["value"] * line["ms_per_step"] * 1e-3 / 3000 - 1) < 1e-9
+    assert line["logloss"] is None and not {"fm", "cpu_baseline", "zipf"} & set(line)
+    got = {f[:-4]: np.load(str(d / f)) for f in os.listdir(str(d))}
+    assert set(got) == {"loss", "w_key_hi", "w_key_lo", "w_w", "w_n", "w_z"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["loss"].shape == (3000,) and np.all(np.abs(got["loss"]) <= 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    args = bench.parse_args()
+    keytab = bench.make_key_table(args.keys_per_gpu)
+    batches = bench.make_batches(args, 0, args.keys_per_gpu, keytab)
+    s = O.Store(O.OPT_FTRL, 1)
+    with O.sum_mode(1):
+        for i in range(args.warmup + args.steps):
+            O.lr_update(s, O.Batch(*batches[i % len(batches)]))
+    keys, w, n, z = s.export()
+    same(got["w_key_hi"].astype(np.uint64) << np.uint64(32) |
+         got["w_key_lo"].astype(np.uint64), keys)
+    for nm, e in (("w", w), ("n", n), ("z", z)):
+        same(got["w_" + nm], e)
 
 
 def test_one_worker_save_over_a_sharded_checkpoint_is_what_loads(sample_prefixes, tmp_path):

@@ -12,6 +12,25 @@ from xflow_amd import capi
 
 
 def free_port():
+    """A free port on 127.0.0.1 below the kernel's ephemeral range.  A port from bind(0) lies
+    inside that range, where any process's connect() may take it as its source port before the
+    ranks bind it: then no rank can bind it, and every rank waits in vain to reach rank 0."""
+    import random
+    lo = 32768
+    try:
+        with open("/proc/sys/net/ipv4/ip_local_port_range") as f:
+            lo = int(f.read().split()[0])
+    except (OSError, ValueError, IndexError):
+        pass
+    rng = random.Random()
+    for _ in range(100):
+        port = rng.randrange(max(1024, lo // 2), max(1025, lo))
+        with socket.socket() as s:
+            try:
+                s.bind(("127.0.0.1", port))
+            except OSError:
+                continue
+            return port
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]

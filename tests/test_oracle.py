@@ -21,14 +21,32 @@ def test_hash_kats(kats):
         assert O.hash_str(s) == int(hx, 16), s
 
 
-def test_hash_random_vs_live_ref():
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built")
+def random_strings():
+    """the hash fuzz's inputs (tests/golden/make_golden.py records the reference's answers)"""
     rng = np.random.RandomState(1)
+    out = []
     for _ in range(2000):
         n = rng.randint(0, 40)
-        b = bytes(rng.randint(32, 127, size=n).astype(np.uint8))
-        assert O.lib().xo_hash_bytes(b, n) == O.ref().ref_hash(b, n)
+        out.append(bytes(rng.randint(32, 127, size=n).astype(np.uint8)))
+    return out
+
+
+@pytest.fixture(scope="module")
+def live(golden_dir):
+    """the live oracle/_ref's answers to the fuzz inputs of this file and test_capi_cpu.py,
+    recorded by tests/golden/make_golden.py: the comparisons run without the reference tree,
+    and against it as well where oracle/_ref is built"""
+    return np.load(os.path.join(golden_dir, "ref_live_vectors.npz"))
+
+
+def test_hash_random_vs_live_ref(live):
+    strs = random_strings()
+    want = live["hash"]
+    assert len(want) == len(strs)
+    for b, h in zip(strs, want):
+        assert O.lib().xo_hash_bytes(b, len(b)) == int(h), b
+        if O.ref_available():
+            assert O.ref().ref_hash(b, len(b)) == int(h), b
 
 
 def test_sigmoid_table(kats):
@@ -61,11 +79,9 @@ def test_parser_golden(golden_dir, name, cap):
     assert np.array_equal(rp.astype(np.uint64), g["rowptr"])
 
 
-def test_parser_edge_cases_vs_live_ref(tmp_path):
+def parser_cases():
     """No trailing newline, trailing blank, block exactly ending on a newline, labels
     that binarise (>1e-7), empty file."""
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built")
     cases = {
         "nonl": "1\t0:1:1 2:22:0.5\n0\t3:333:1",
         "blank": "0.5\t0:1:1 2:22:0.5 \n0.00000001\t3:333:1\n",
@@ -79,16 +95,30 @@ def test_parser_edge_cases_vs_live_ref(tmp_path):
     cases["dblank"] = "1\t0:1:1  2:2:2 \n0\t3:3:3   4:4:4\n"
     cases["blank_eof"] = "1\t0:1:1 2:22:0.5 \n0\t3:333:1 "
     cases["blank_cut"] = ("1\t0:12345:1 1:67:1 \n") * 6 + "0\t5:5:5\n"   # 20-byte lines ending in a blank
-    for nm, txt in cases.items():
+    return cases
+
+
+PARSER_CAPS = (41, 64, 1 << 16)
+
+
+def test_parser_edge_cases_vs_live_ref(tmp_path, live):
+    """parser_cases() at PARSER_CAPS: the reference's blocks as recorded, and as the live
+    oracle/_ref reads them where it is built"""
+    for nm, txt in parser_cases().items():
         p = tmp_path / nm
         p.write_text(txt)
-        for cap in (41, 64, 1 << 16):
-            mine = list(O.read_blocks(str(p), cap))
-            theirs = list(O.ref_read_blocks(str(p), cap))
-            assert len(mine) == len(theirs), (nm, cap)
-            for a, b in zip(mine, theirs):
-                for x, y in zip(a, b):
-                    assert np.array_equal(x, y), (nm, cap)
+        for cap in PARSER_CAPS:
+            tag = "parse_%s_%d" % (nm, cap)
+            want = [tuple(live["%s_%d_%d" % (tag, i, j)] for j in range(4))
+                    for i in range(int(live[tag + "_n"]))]
+            runs = [list(O.read_blocks(str(p), cap))]
+            if O.ref_available():
+                runs.append(list(O.ref_read_blocks(str(p), cap)))
+            for got in runs:
+                assert len(got) == len(want), (nm, cap)
+                for a, b in zip(got, want):
+                    for x, y in zip(a, b):
+                        assert np.array_equal(x, y), (nm, cap)
 
 
 def test_parser_rejects_malformed(tmp_path):

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf /tmp/fm64s
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fm64s -- python $R/bench.py --model fm --k 64 --optimizer ftrl --zipf 1.1 --steps 12 --warmup 4 --no-cpu-baseline --batches 4 --repeats 2 > /tmp/fm64s.json 2>/tmp/fm64s.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fm64s -- python $R/bench.py --full --model fm --k 64 --optimizer ftrl --zipf 1.1 --steps 12 --warmup 4 --no-cpu-baseline --batches 4 --repeats 2 > /tmp/fm64s.json 2>/tmp/fm64s.err
 python3 - <<'PY'
 import csv, glob, re
 f = glob.glob("/tmp/fm64s/**/*kernel_stats.csv", recursive=True)[0]

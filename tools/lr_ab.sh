@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for v in "$@"; do
   if [ $v = default ]; then unset XF_LIB; else export XF_LIB=$R/xflow_amd/lib/var_$v/libxflow_amd.so; fi
-  python $R/bench.py --no-cpu-baseline --no-fm-leg --repeats 4 --batches 4 $EXTRA 2>/dev/null | python3 -c "
+  python $R/bench.py --full --no-cpu-baseline --no-fm-leg --repeats 4 --batches 4 $EXTRA 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if not l.startswith('{'): continue

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 rm -rf /tmp/n8s
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/n8s -- python $R/bench.py --rows 400000 --nnz-per-row 25 --keys-per-gpu 12500000 --force-sharded --general-path --schedule owner --no-cpu-baseline --repeats 1 --batches 4 --key-build-steps 0 ${EXTRA:-} > /tmp/n8s.json 2>/tmp/n8s.err
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/n8s -- python $R/bench.py --full --rows 400000 --nnz-per-row 25 --keys-per-gpu 12500000 --force-sharded --general-path --schedule owner --no-cpu-baseline --repeats 1 --batches 4 --key-build-steps 0 ${EXTRA:-} > /tmp/n8s.json 2>/tmp/n8s.err
 python3 - <<'PY'
 import csv, glob, re
 f = glob.glob("/tmp/n8s/**/*kernel_stats.csv", recursive=True)[0]

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   if [ -n "${FMLEG:-}" ]; then CMD="python $R/tools/fm_leg.py --batches 4 --pmc-calibrate"
-  else CMD="python $R/bench.py --model fm $ARGS --steps 6 --warmup 4 --no-cpu-baseline --pmc-calibrate"; fi
+  else CMD="python $R/bench.py --full --model fm $ARGS --steps 6 --warmup 4 --no-cpu-baseline --pmc-calibrate"; fi
   timeout -s KILL 200 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$OUT/pmc_$c -- \
       $CMD > $R/$OUT/pmc_$c.json 2> $R/$OUT/pmc_$c.err
 done

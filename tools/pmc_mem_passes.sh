@@ -16,7 +16,7 @@ for grp in "TA_BUSY_avr TA_TOTAL_WAVEFRONTS_sum" \
            "TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_sum TCP_TCC_READ_REQ_LATENCY_sum"; do
   i=$((i+1))
   timeout -s KILL 90 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $R/$OUT/g$i -- \
-      python $R/bench.py --steps 6 --warmup 8 --no-cpu-baseline --key-build-steps 0 "$@" > $R/$OUT/g$i.json 2> $R/$OUT/g$i.err
+      python $R/bench.py --full --steps 6 --warmup 8 --no-cpu-baseline --key-build-steps 0 "$@" > $R/$OUT/g$i.json 2> $R/$OUT/g$i.err
 done
 cd $R
 python tools/pmc_summary.py $OUT

@@ -16,7 +16,7 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "TCC_TAG_STALL_sum TCC_BUSY_avr TCC_READ_sum TCC_WRITE_sum"; do
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $R/$OUT/g$i -- \
-      python $R/bench.py --steps 6 --warmup 8 --no-cpu-baseline "$@" > $R/$OUT/g$i.json 2> $R/$OUT/g$i.err
+      python $R/bench.py --full --steps 6 --warmup 8 --no-cpu-baseline "$@" > $R/$OUT/g$i.json 2> $R/$OUT/g$i.err
 done
 cd $R
 python tools/pmc_summary.py $OUT

@@ -2,7 +2,7 @@
 """Per-kernel HBM traffic from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE).
 
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d out/pmc_FETCH_SIZE -- \
-      python bench.py --steps 6 --warmup 8 --no-cpu-baseline --pmc-calibrate
+      python bench.py --full --steps 6 --warmup 8 --no-cpu-baseline --pmc-calibrate
   rocprofv3 --pmc WRITE_SIZE ... (same command)
   python tools/pmc_traffic.py out/pmc_FETCH_SIZE out/pmc_WRITE_SIZE > profiles/rNN/pmc_traffic.json
 

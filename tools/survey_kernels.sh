@@ -4,7 +4,7 @@
 # the same command, then every kernel's average time next to its traffic — a kernel far below
 # ~3 TB/s with little traffic is waiting on something else (dependent round trips, divergence,
 # one long chain): that is how the FM heavy-key kernels were found (217 us for 45 MB).
-#   bash tools/survey_kernels.sh gpurun_out/survey "python bench.py --zipf 1.1 --no-cpu-baseline --no-fm-leg --repeats 0 --pmc-calibrate"
+#   bash tools/survey_kernels.sh out/survey "python bench.py --full --zipf 1.1 --no-cpu-baseline --no-fm-leg --repeats 0 --pmc-calibrate"
 set -u
 OUT=$1; CMD=$2
 R=$PWD

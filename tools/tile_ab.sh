@@ -12,5 +12,5 @@ for l in sys.stdin:
 for v in "$@"; do
   if [ $v = default ]; then unset XF_LIB; else export XF_LIB=$R/xflow_amd/lib/var_$v/libxflow_amd.so; fi
   python $R/tools/fm_leg.py --batches 4 2>/dev/null | show "fm16 $v"
-  [ -n "$FM64" ] && python $R/bench.py --model fm --k 64 --optimizer ftrl --zipf 1.1 --steps 12 --warmup 4 --no-cpu-baseline --batches 4 --repeats 2 2>/dev/null | show "fm64-zipf $v"
+  [ -n "$FM64" ] && python $R/bench.py --full --model fm --k 64 --optimizer ftrl --zipf 1.1 --steps 12 --warmup 4 --no-cpu-baseline --batches 4 --repeats 2 2>/dev/null | show "fm64-zipf $v"
 done
