@@ -431,6 +431,18 @@ int xf_workspace_capture(xf_workspace *ws, int enable);
 #define XF_PARITY_EXACT_SUMS 0
 #define XF_PARITY_REFERENCE_ORDER 1
 int xf_workspace_parity(xf_workspace *ws, int mode);
+/* FM form of xf_fm_step / xf_fm_predict with this workspace:
+ *   XF_FM_REFERENCE  (default) the reference's second-order term as written (fm_worker.cc:
+ *                    178-196): sums pooled over all k factors, v_y = (sum a_u)^2 - sum b_u
+ *   XF_FM_CANONICAL  Rendle's FM: per-factor sums S[r,f] = sum_j v[u_j,f],
+ *                    y2 = 0.5 (sum_f S^2 - sum_f sum_j v^2) = sum_{i<j} <v_i, v_j>;
+ *                    gw = (sum_occ loss) / R, gv[u,f] = (sum_occ loss (S[r,f] - v[u,f])) / R.
+ *                    Exact fp64 sums of fp32 terms, as XF_PARITY_EXACT_SUMS.  Needs a minibatch
+ *                    with a key list (xf_batch_compile / _gpu / _dev, not the keyed build of
+ *                    xf_batch_compile_fm*); refused together with XF_PARITY_REFERENCE_ORDER. */
+#define XF_FM_REFERENCE 0
+#define XF_FM_CANONICAL 1
+int xf_workspace_fm_mode(xf_workspace *ws, int mode);
 /* copies of the last step's intermediates to host (parity hook): any pointer may be NULL */
 int xf_workspace_fetch(xf_workspace *ws, float *wu, float *loss, float *g, size_t U,
                        size_t R);
@@ -609,6 +621,11 @@ int xf_sharded_set_schedule(xf_sharded *st, int schedule);
  * (xf_sbatch_fm_keyed) has no index of its key list, and the reference-order kernels refuse it
  * (the call says so and names this remedy) */
 int xf_sharded_set_parity(xf_sharded *st, int mode);
+/* the FM form (xf_workspace_fm_mode) of a one-rank FM trainer, accepted only while its tables
+ * hold no key.  XF_FM_CANONICAL also starts an SGD v table from the hash-normal init (a constant
+ * init would keep a key's k factors equal forever), and minibatches compiled from then on carry
+ * a key list (xf_batch_compile_gpu / _dev).  A trainer of more than one rank: XF_EINVAL. */
+int xf_sharded_set_fm_mode(xf_sharded *st, int mode);
 int xf_sharded_tables(xf_sharded *st, xf_table **w, xf_table **v);
 int xf_sharded_stream(xf_sharded *st, void **stream);
 /* ms_sum[6] = owner pull, weights exchange, forward, gradient, gradients exchange, owner
@@ -642,6 +659,8 @@ int XFDestroy(void **h);
  *        update(rank_ordered|sum_then_step: with schedule=owner)
  *        parity(exact|reference_order: the forward's row sums in the reference's own fp32
  *        order — one worker, checking mode)
+ *        fm_mode(reference|canonical: FM's second-order term as the reference writes it, or
+ *        Rendle's per-factor form — xf_workspace_fm_mode; canonical: model 1, one worker)
  *        model_in model_out (model file to load before / save after training)
  *        block_cache(0|1) block_cache_dir (binarized block cache of the text files)
  *        ingest(host|gpu: the text of a block tokenised and hashed on the GPU, xf_ingest_*;

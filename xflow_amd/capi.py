@@ -15,6 +15,8 @@ XF_OK = 0
 OPT_FTRL, OPT_SGD = 0, 1
 INIT_ZERO, INIT_CONST, INIT_HASHNORM = 0, 1, 2
 HEAVY_SEG = 64
+FM_REFERENCE, FM_CANONICAL = 0, 1
+FM_MODES = {"reference": FM_REFERENCE, "canonical": FM_CANONICAL}
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -110,6 +112,7 @@ SIGNATURES = {
     "xf_source_hash": (C.c_char_p, []),
     "xf_workspace_capture": (C.c_int, [vp, C.c_int]),
     "xf_workspace_parity": (C.c_int, [vp, C.c_int]),
+    "xf_workspace_fm_mode": (C.c_int, [vp, C.c_int]),
     "xf_batch_dims": (C.c_int, [vp, u32p, u32p, u32p, u32p]),
     "xf_batch_host": (C.c_int, [vp, C.POINTER(u64p), C.POINTER(u32p), C.POINTER(u32p),
                                 C.POINTER(u32p), C.POINTER(u32p), C.POINTER(i32p),
@@ -195,6 +198,7 @@ SIGNATURES = {
     "xf_sharded_check": (C.c_int, [vp]),
     "xf_sharded_set_schedule": (C.c_int, [vp, C.c_int]),
     "xf_sharded_set_parity": (C.c_int, [vp, C.c_int]),
+    "xf_sharded_set_fm_mode": (C.c_int, [vp, C.c_int]),
     "xf_sharded_tables": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "xf_sharded_stream": (C.c_int, [vp, C.POINTER(vp)]),
     "xf_sharded_profile": (C.c_int, [vp, C.c_int]),
@@ -747,6 +751,11 @@ class Workspace:
         order: slow, for checking)"""
         check(lib().xf_workspace_parity(self.h, {"exact": 0, "reference_order": 1}[mode]))
 
+    def fm_mode(self, mode):
+        """FM form of fm_step / fm_predict: 'reference' (default: the reference's pooled
+        second-order term) or 'canonical' (Rendle's per-factor sums)"""
+        check(lib().xf_workspace_fm_mode(self.h, FM_MODES[mode]))
+
     def fetch(self, U, R):
         wu = np.empty(U, np.float32)
         loss = np.empty(R, np.float32)
@@ -902,7 +911,8 @@ class Sharded:
 
     def __init__(self, group=None, model="lr", optimizer="ftrl", k=10, capacity=1 << 22,
                  schedule="sequential", seed=0, host_key_build=False, update="rank_ordered",
-                 **hyper):
+                 fm_mode="reference", **hyper):
+        """fm_mode="canonical": Rendle's FM on a one-rank trainer (xf_sharded_set_fm_mode)"""
         require_gpu()
         c = ShardedConfig()
         lib().xf_sharded_config_default(C.byref(c))
@@ -923,6 +933,12 @@ class Sharded:
         check(lib().xf_sharded_tables(self.h, C.byref(w), C.byref(v)))
         self.w = Table.from_handle(w, 1, c.optimizer)
         self.v = Table.from_handle(v, k, c.optimizer) if v else None
+        if fm_mode != "reference":
+            self.set_fm_mode(fm_mode)
+
+    def set_fm_mode(self, mode):
+        """'reference' or 'canonical': before the first step, one rank only"""
+        check(lib().xf_sharded_set_fm_mode(self.h, FM_MODES[mode]))
 
     def close(self):
         if getattr(self, "h", None):

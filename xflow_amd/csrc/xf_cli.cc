@@ -18,7 +18,8 @@ int main(int argc, char *argv[]) {
     std::cout << "usage: xflow_lr <train_prefix> <test_prefix> <model: 0 LR | 1 FM> <epochs>"
                  " [name=value ...]\n"
               << "LR model example: xflow_lr data/small_train data/small_test 0 100\n"
-              << "FM model example: xflow_lr data/small_train data/small_test 1 100\n";
+              << "FM model example: xflow_lr data/small_train data/small_test 1 100\n"
+              << "Rendle's FM (per-factor second-order term, one worker): append fm_mode=canonical\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler

@@ -1,0 +1,417 @@
+// xf_fm_canonical.hip — canonical factorization machine (fm_mode = canonical, gfx950).
+//
+// Rendle's second-order term with per-factor sums and the 1/2:
+//   S[r,f] = sum_j v[u_j,f]                 (R x k, kept for the gradient)
+//   y2_r   = 0.5 * (sum_f S[r,f]^2 - sum_f sum_j v[u_j,f]^2) = sum_{i<j} <v_i, v_j>
+//   gw[u]   = (sum_occ loss) / R
+//   gv[u,f] = (sum_occ loss * (S[sid,f] - v[u,f])) / R
+// The reference form (xf_model.hip, fm_worker.cc:159-202) pools its sums over all k factors,
+// which collapses the k factors into one scalar per key; this form does not.  Every fp64 sum
+// adds fp32 values (products are rounded to fp32 first), so it is exact and the result does
+// not depend on lane assignment or order.
+//
+// Forward: one wavefront per row.  A lane is a (nonzero slot, factor) pair — P factors, 64 / P
+// slots, four nonzeros in flight per lane; the per-factor fp64 sums are joined across the slots
+// with shuffles, the S row leaves as one coalesced store.  P = k for k in {4, 8, 16, 32, 64};
+// other k run with P = the next power of two (lanes beyond k idle), k > 64 in passes of 64.
+// Gradient + the two Pushes: the minibatch's key tiles (xf_tiling.h) as in k_fm_grad_tiled,
+// a tile's occurrence rows and losses staged in LDS, a lane per (key, factor) reading
+// S[sid, f] of the key's occurrences from L2.  Heavy keys (> XF_HEAVY_SEG occurrences) are
+// reduced in chunks over the whole chip and stepped by a second kernel.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "xf_common.h"
+#include "xf_device.h"
+#include "xf_wave.h"
+
+namespace xf {
+const TableDev &table_dev(const xf_table *t);
+}
+
+namespace {
+
+constexpr int kBlock = 256;
+using xf::blocks_for_groups;  // xf_wave.h
+using xf::group_sum;
+using xf::heavy_of_chunk;
+
+// ------------------------------------------------------------------------------ forward
+// P: factors per pass (a power of two <= 64); EXACT: k == P (a compile-time factor count)
+template <int P, bool EXACT>
+__global__ void __launch_bounds__(kBlock)
+k_fmc_forward(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ uidx,
+              const float *__restrict__ wu, const float *__restrict__ vu, int k_rt,
+              const int32_t *__restrict__ labels, uint32_t R, float *__restrict__ loss,
+              float *__restrict__ pctr, float *__restrict__ S) {
+#pragma clang fp contract(off)
+  static_assert(P >= 1 && P <= 64 && (P & (P - 1)) == 0, "P: a power of two <= 64");
+  const uint32_t k = EXACT ? (uint32_t)P : (uint32_t)k_rt;
+  constexpr uint32_t kG = 64u / P;  // nonzero slots per pass
+  const uint32_t lane = threadIdx.x & 63u, f = lane % P, sub = lane / P;
+  const uint32_t nwaves = gridDim.x * (kBlock / 64);
+  for (uint32_t r = blockIdx.x * (kBlock / 64) + threadIdx.x / 64; r < R; r += nwaves) {
+    const uint32_t b = rowptr[r], n = rowptr[r + 1] - b;
+    double wx = 0.0, t = 0.0, q = 0.0;
+    for (uint32_t f0 = 0; f0 < k; f0 += P) {  // one pass unless k > 64
+      const uint32_t fk = f0 + f;
+      const bool on = fk < k;
+      double s = 0.0;
+      for (uint32_t j0 = sub; j0 < n; j0 += 4 * kG) {
+        uint32_t ui[4];
+        float vv[4], ww[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ui[i] = j0 + i * kG < n ? uidx[b + j0 + i * kG] : 0xFFFFFFFFu;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          vv[i] = (on && ui[i] != 0xFFFFFFFFu) ? vu[(size_t)ui[i] * k + fk] : 0.0f;
+          ww[i] = (f0 == 0 && f == 0 && ui[i] != 0xFFFFFFFFu) ? wu[ui[i]] : 0.0f;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          s += (double)vv[i];
+          q += (double)(vv[i] * vv[i]);  // fp32 product
+          wx += (double)ww[i];
+        }
+      }
+#pragma unroll
+      for (uint32_t off = P; off < 64; off <<= 1) s += __shfl_xor(s, (int)off);
+      const float sf = (float)s;
+      if (sub == 0 && on) {
+        S[(size_t)r * k + fk] = sf;
+        t += (double)(sf * sf);  // fp32 square
+      }
+    }
+    t = group_sum<64>(t);
+    q = group_sum<64>(q);
+    wx = group_sum<64>(wx);
+    if (lane == 0) {
+      const float y2 = (float)(0.5 * (t - q));
+      const float p = xf::sigmoid_ref((float)wx + y2);
+      if (pctr) pctr[r] = p;
+      loss[r] = p - (float)labels[r];
+    }
+  }
+}
+
+// ------------------------------------------------------------ gradient + the two Pushes
+// A workgroup per gradient tile (keys [tile_ptr[t], tile_ptr[t+1]), <= XF_GRAD_TILE_NNZ
+// occurrences): the occurrences' rows and losses go to LDS once, then a lane per (key, factor)
+// item sums loss * (S[sid, f] - v[u, f]) over the key's occurrences — the S values of one
+// occurrence are read by neighbouring lanes from one contiguous k x 4-byte row — and applies
+// the optimizer step to that coordinate of the key's v row (the pulled value is the current
+// weight: nothing touched the row since the Pull).  One lane per key does the same for w.
+template <int OPT, int K /* compile-time factor count, 0 = k_rt */>
+__global__ void __launch_bounds__(kBlock)
+k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ tile_ptr,
+                 uint32_t ntiles, const uint32_t *__restrict__ segptr,
+                 const uint32_t *__restrict__ coo_row, const float *__restrict__ loss,
+                 const float *__restrict__ S, const float *__restrict__ wu,
+                 const float *__restrict__ vu, const uint32_t *__restrict__ rows_w,
+                 const uint32_t *__restrict__ rows_v, uint32_t R, int k_rt,
+                 float *__restrict__ gw) {
+#pragma clang fp contract(off)
+  __shared__ float lv[XF_GRAD_TILE_NNZ];
+  __shared__ uint32_t ss[XF_GRAD_TILE_NNZ];
+  __shared__ uint32_t sp[XF_GRAD_TILE_KEYS + 1];
+  const uint32_t k = K > 0 ? (uint32_t)K : (uint32_t)k_rt;
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const uint32_t ua = tile_ptr[tile], ub = tile_ptr[tile + 1], nk = ub - ua;
+    const uint32_t j0 = segptr[ua], j1 = segptr[ub];
+    if (nk == 1 && j1 - j0 > XF_HEAVY_SEG) continue;  // heavy key: the chunked kernels
+    for (uint32_t q = tid; q <= nk; q += kBlock) sp[q] = segptr[ua + q] - j0;
+    for (uint32_t j = j0 + tid; j < j1; j += kBlock) {
+      const uint32_t sid = coo_row[j];
+      ss[j - j0] = sid;
+      lv[j - j0] = loss[sid];
+    }
+    __syncthreads();
+    const uint32_t nel = nk * k;
+    constexpr int kUn = 4;  // items in flight per lane: factors and state requested together
+    for (uint32_t el0 = tid; el0 < nel; el0 += kBlock * kUn) {
+      uint32_t kq[kUn], kk[kUn];
+      float v[kUn], vn[kUn], vz[kUn];
+      size_t to[kUn];
+      bool on[kUn];
+#pragma unroll
+      for (int i = 0; i < kUn; ++i) {
+        const uint32_t el = el0 + i * kBlock;
+        on[i] = el < nel;
+        kq[i] = on[i] ? el / k : 0;
+        kk[i] = on[i] ? el - kq[i] * k : 0;
+      }
+#pragma unroll
+      for (int i = 0; i < kUn; ++i) {
+        v[i] = on[i] ? vu[(size_t)(ua + kq[i]) * k + kk[i]] : 0.0f;
+        to[i] = on[i] ? (size_t)rows_v[ua + kq[i]] * k + kk[i] : 0;
+      }
+      if (OPT == XF_OPT_FTRL) {
+#pragma unroll
+        for (int i = 0; i < kUn; ++i) {
+          vn[i] = vz[i] = 0.0f;
+          if (on[i]) xf::load_nz(TV, to[i], vn[i], vz[i]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < kUn; ++i) {
+        if (!on[i]) continue;
+        const uint32_t a = sp[kq[i]], e = sp[kq[i] + 1];
+        double acc = 0.0;
+        uint32_t j = a;
+        for (; j + 3 < e; j += 4) {  // four S gathers in flight
+          float sv[4];
+#pragma unroll
+          for (int m = 0; m < 4; ++m) sv[m] = S[(size_t)ss[j + m] * k + kk[i]];
+#pragma unroll
+          for (int m = 0; m < 4; ++m) acc += (double)(lv[j + m] * (sv[m] - v[i]));
+        }
+        for (; j < e; ++j) acc += (double)(lv[j] * (S[(size_t)ss[j] * k + kk[i]] - v[i]));
+        const float g = xf::div_by_rows((float)acc, R);
+        if (OPT == XF_OPT_FTRL) {
+          float w = v[i], nn = vn[i], z = vz[i];
+          xf::ftrl_step(TV.alpha, TV.inv_alpha, TV.beta, TV.lambda1, TV.lambda2, g, w, nn, z);
+          TV.w[to[i]] = w;
+          xf::store_nz(TV, to[i], nn, z);
+        } else {
+          TV.w[to[i]] = xf::sgd_step(TV.lr, g, v[i]);
+        }
+      }
+    }
+    // the keys' w: the true gradient (sum of the occurrences' losses) / R, one lane per key
+    for (uint32_t q = tid; q < nk; q += kBlock) {
+      double aw = 0.0;
+      for (uint32_t j = sp[q]; j < sp[q + 1]; ++j) aw += (double)lv[j];
+      const float g1 = xf::div_by_rows((float)aw, R);
+      gw[ua + q] = g1;
+      const uint32_t rw = rows_w[ua + q];
+      if (OPT == XF_OPT_FTRL) {
+        float w = wu[ua + q], nn, z;
+        xf::load_nz(TW, rw, nn, z);
+        xf::ftrl_step(TW.alpha, TW.inv_alpha, TW.beta, TW.lambda1, TW.lambda2, g1, w, nn, z);
+        TW.w[rw] = w;
+        xf::store_nz(TW, rw, nn, z);
+      } else {
+        TW.w[rw] = xf::sgd_step(TW.lr, g1, wu[ua + q]);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------- heavy keys
+// A heavy key's occurrences in chunks of XF_TILE_NNZ (the batch's heavy_chunk_ptr), one
+// workgroup per chunk: partial[chunk][col] for the k factor columns and the loss sum (column k).
+// A thread is (slice of the chunk's occurrences, column); columns beyond one workgroup's width
+// (k >= 256) take further passes.
+__global__ void __launch_bounds__(kBlock)
+k_fmc_heavy_partial(const uint32_t *__restrict__ heavy, const uint32_t *__restrict__ hch,
+                    uint32_t H, const uint32_t *__restrict__ segptr,
+                    const uint32_t *__restrict__ coo_row, const float *__restrict__ loss,
+                    const float *__restrict__ S, const float *__restrict__ vu, int k_rt,
+                    double *__restrict__ partial) {
+#pragma clang fp contract(off)
+  __shared__ float lv[XF_TILE_NNZ];
+  __shared__ uint32_t ss[XF_TILE_NNZ];
+  __shared__ double red[kBlock];
+  const uint32_t tid = threadIdx.x, c = blockIdx.x, k = (uint32_t)k_rt;
+  const uint32_t h = heavy_of_chunk(hch, H, c);
+  const uint32_t u = heavy[h];
+  const uint32_t b = segptr[u] + (c - hch[h]) * XF_TILE_NNZ;
+  const uint32_t e = min(segptr[u + 1], b + XF_TILE_NNZ);
+  const uint32_t n = e > b ? e - b : 0u;
+  for (uint32_t j = tid; j < n; j += kBlock) {
+    const uint32_t sid = coo_row[b + j];
+    ss[j] = sid;
+    lv[j] = loss[sid];
+  }
+  __syncthreads();
+  const uint32_t ncol = k + 1u, cpp = min(ncol, (uint32_t)kBlock), nsl = kBlock / cpp;
+  const uint32_t cl = tid % cpp, sl = tid / cpp;
+  for (uint32_t c0 = 0; c0 < ncol; c0 += cpp) {
+    const uint32_t col = c0 + cl;
+    const bool act = sl < nsl && col < ncol, fac = col < k;
+    const float v = (act && fac) ? vu[(size_t)u * k + col] : 0.0f;
+    double acc = 0.0;
+    if (act) {
+      if (fac) {
+        // a slice is ~n / nsl occurrences long (k = 64: ~680): eight S gathers in flight per
+        // thread, eight independent sums (exact: joined in any order)
+        double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        uint32_t j = sl;
+        for (; j + 7 * nsl < n; j += 8 * nsl) {
+          float sv[8];
+#pragma unroll
+          for (int m = 0; m < 8; ++m) sv[m] = S[(size_t)ss[j + m * nsl] * k + col];
+#pragma unroll
+          for (int m = 0; m < 8; ++m) a[m] += (double)(lv[j + m * nsl] * (sv[m] - v));
+        }
+        for (; j < n; j += nsl) a[0] += (double)(lv[j] * (S[(size_t)ss[j] * k + col] - v));
+        acc = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+      } else {
+        for (uint32_t j = sl; j < n; j += nsl) acc += (double)lv[j];
+      }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    if (sl == 0 && col < ncol) {
+      for (uint32_t q = 1; q < nsl; ++q) acc += red[q * cpp + cl];
+      partial[(size_t)c * ncol + col] = acc;
+    }
+    __syncthreads();
+  }
+}
+
+// one workgroup per heavy key: its chunks' partial sums added per column, then the optimizer
+// steps of its k factors and of its w
+template <int OPT>
+__global__ void __launch_bounds__(kBlock)
+k_fmc_heavy_finish(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ heavy,
+                   const uint32_t *__restrict__ hch, const double *__restrict__ partial,
+                   const uint32_t *__restrict__ rows_w, const uint32_t *__restrict__ rows_v,
+                   const float *__restrict__ wu, const float *__restrict__ vu, uint32_t R,
+                   int k_rt, float *__restrict__ gw) {
+#pragma clang fp contract(off)
+  __shared__ double red[kBlock];
+  const uint32_t tid = threadIdx.x, h = blockIdx.x, k = (uint32_t)k_rt;
+  const uint32_t u = heavy[h], c0h = hch[h], c1h = hch[h + 1];
+  const uint32_t ncol = k + 1u, cpp = min(ncol, (uint32_t)kBlock), nsl = kBlock / cpp;
+  const uint32_t cl = tid % cpp, sl = tid / cpp;
+  for (uint32_t p0 = 0; p0 < ncol; p0 += cpp) {
+    const uint32_t col = p0 + cl;
+    double acc = 0.0;
+    if (sl < nsl && col < ncol)
+      for (uint32_t c = c0h + sl; c < c1h; c += nsl) acc += partial[(size_t)c * ncol + col];
+    red[tid] = acc;
+    __syncthreads();
+    if (sl == 0 && col < ncol) {
+      for (uint32_t q = 1; q < nsl; ++q) acc += red[q * cpp + cl];
+      const float g = xf::div_by_rows((float)acc, R);
+      if (col < k) {
+        const size_t o = (size_t)rows_v[u] * k + col;
+        float w = vu[(size_t)u * k + col];
+        if (OPT == XF_OPT_FTRL) {
+          float nn, z;
+          xf::load_nz(TV, o, nn, z);
+          xf::ftrl_step(TV.alpha, TV.inv_alpha, TV.beta, TV.lambda1, TV.lambda2, g, w, nn, z);
+          TV.w[o] = w;
+          xf::store_nz(TV, o, nn, z);
+        } else {
+          TV.w[o] = xf::sgd_step(TV.lr, g, w);
+        }
+      } else {
+        gw[u] = g;
+        const uint32_t rw = rows_w[u];
+        float w = wu[u];
+        if (OPT == XF_OPT_FTRL) {
+          float nn, z;
+          xf::load_nz(TW, rw, nn, z);
+          xf::ftrl_step(TW.alpha, TW.inv_alpha, TW.beta, TW.lambda1, TW.lambda2, g, w, nn, z);
+          TW.w[rw] = w;
+          xf::store_nz(TW, rw, nn, z);
+        } else {
+          TW.w[rw] = xf::sgd_step(TW.lr, g, w);
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+}  // namespace
+
+namespace xf {
+
+// scratch of the heavy keys' chunk sums: doubles
+size_t fmc_heavy_doubles(const xf_dev_batch *b, int k) {
+  return b->H ? (size_t)b->n_heavy_chunks * ((size_t)k + 1) : 0;
+}
+
+// loss[R], pctr[R] (may be null), S[R x k] from the pulled rows w_u[U], v_u[U x k]
+int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_vu, float *d_S,
+                float *d_loss, float *d_pctr, hipStream_t s) {
+  XF_REQUIRE(b && d_wu && d_vu && d_S && d_loss && k >= 1, "fm canonical forward: bad argument");
+  if (b->R == 0) return XF_OK;
+  const dim3 g(blocks_for_groups(b->R, kBlock / 64)), blk(kBlock);
+#define XF_FMC_FWD(PP, EX)                                                                     \
+  hipLaunchKernelGGL((k_fmc_forward<PP, EX>), g, blk, 0, s, b->rowptr, b->uidx, d_wu, d_vu, k, \
+                     b->labels, b->R, d_loss, d_pctr, d_S)
+  switch (k) {
+    case 4: XF_FMC_FWD(4, true); break;
+    case 8: XF_FMC_FWD(8, true); break;
+    case 16: XF_FMC_FWD(16, true); break;
+    case 32: XF_FMC_FWD(32, true); break;
+    case 64: XF_FMC_FWD(64, true); break;
+    default:
+      if (k <= 1) XF_FMC_FWD(1, false);
+      else if (k <= 2) XF_FMC_FWD(2, false);
+      else if (k <= 4) XF_FMC_FWD(4, false);
+      else if (k <= 8) XF_FMC_FWD(8, false);
+      else if (k <= 16) XF_FMC_FWD(16, false);
+      else if (k <= 32) XF_FMC_FWD(32, false);
+      else XF_FMC_FWD(64, false);
+      break;
+  }
+#undef XF_FMC_FWD
+  XF_HIP(hipGetLastError());
+  return XF_OK;
+}
+
+// gradient + both Pushes for the tables on this GPU.  rows_w / rows_v: the keys' state rows,
+// d_wu / d_vu: the rows the Pull returned (current: the step has not written them yet).  gw[U]
+// is written for every key (the capture hook); d_hpart: fmc_heavy_doubles(b, k) doubles.
+int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uint32_t *d_rows_w,
+                    const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
+                    const float *d_S, const float *d_loss, float *d_gw, double *d_hpart,
+                    hipStream_t s) {
+  XF_REQUIRE(tw && tv && b && d_rows_w && d_rows_v && d_wu && d_vu && d_S && d_loss && d_gw,
+             "fm canonical gradient: null argument");
+  if (b->U == 0) return XF_OK;
+  const xf::TableDev &TW = xf::table_dev(tw), &TV = xf::table_dev(tv);
+  const int k = TV.dim;
+  const bool ftrl = TV.nz != nullptr;
+  XF_REQUIRE((TW.nz != nullptr) == ftrl, "fm canonical gradient: w and v use different optimizers");
+  XF_REQUIRE(b->ntiles && b->tile_ptr, "fm canonical gradient: the minibatch has no gradient tiles");
+  XF_REQUIRE(!b->H || (b->heavy_chunk_ptr && d_hpart),
+             "fm canonical gradient: heavy keys without their chunks or scratch");
+  const dim3 gt((unsigned)std::min<uint32_t>(b->ntiles, 1u << 16)), blk(kBlock);
+#define XF_FMC_GU(OPTV, KK)                                                                     \
+  hipLaunchKernelGGL((k_fmc_grad_tiled<OPTV, KK>), gt, blk, 0, s, TW, TV, b->tile_ptr, b->ntiles, \
+                     b->segptr, b->coo_row, d_loss, d_S, d_wu, d_vu, d_rows_w, d_rows_v, b->R, k, \
+                     d_gw)
+#define XF_FMC_GU_K(OPTV)                 \
+  switch (k) {                            \
+    case 4: XF_FMC_GU(OPTV, 4); break;    \
+    case 8: XF_FMC_GU(OPTV, 8); break;    \
+    case 16: XF_FMC_GU(OPTV, 16); break;  \
+    case 32: XF_FMC_GU(OPTV, 32); break;  \
+    case 64: XF_FMC_GU(OPTV, 64); break;  \
+    default: XF_FMC_GU(OPTV, 0); break;   \
+  }
+  if (ftrl) {
+    XF_FMC_GU_K(XF_OPT_FTRL)
+  } else {
+    XF_FMC_GU_K(XF_OPT_SGD)
+  }
+#undef XF_FMC_GU_K
+#undef XF_FMC_GU
+  XF_HIP(hipGetLastError());
+  if (b->H) {
+    hipLaunchKernelGGL(k_fmc_heavy_partial, dim3(b->n_heavy_chunks), blk, 0, s, b->heavy,
+                       b->heavy_chunk_ptr, b->H, b->segptr, b->coo_row, d_loss, d_S, d_vu, k,
+                       d_hpart);
+    if (ftrl)
+      hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_FTRL>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
+                         b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
+                         d_gw);
+    else
+      hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_SGD>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
+                         b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
+                         d_gw);
+    XF_HIP(hipGetLastError());
+  }
+  return XF_OK;
+}
+
+}  // namespace xf

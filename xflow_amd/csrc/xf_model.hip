@@ -30,6 +30,7 @@
 #include "xf_common.h"
 #include "xf_device.h"
 #include "xf_scratch.h"
+#include "xf_wave.h"
 
 namespace xf {
 const TableDev &table_dev(const xf_table *t);
@@ -50,6 +51,14 @@ int cells_lr_grad_update(const xf_cells *c, const xf_table *t, const float *d_lo
 int gather_f32(const float *src, const uint32_t *rows, size_t n, float *dst, hipStream_t s);
 int batch_sorted_uidx(xf_batch *b, hipStream_t s);
 int batch_reference_coo(xf_batch *b, hipStream_t s);
+// canonical FM (xf_fm_canonical.hip)
+size_t fmc_heavy_doubles(const xf_dev_batch *b, int k);
+int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_vu, float *d_S,
+                float *d_loss, float *d_pctr, hipStream_t s);
+int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uint32_t *d_rows_w,
+                    const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
+                    const float *d_S, const float *d_loss, float *d_gw, double *d_hpart,
+                    hipStream_t s);
 }  // namespace xf
 
 namespace {
@@ -58,13 +67,9 @@ constexpr int kBlock = 256;
 inline hipStream_t S(void *s) { return (hipStream_t)s; }
 
 using xf::div_by_rows;  // xf_device.h
-
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-  return v;
-}
+using xf::blocks_for_groups;  // xf_wave.h
+using xf::group_sum;
+using xf::heavy_of_chunk;
 
 // ------------------------------------------------------------------ LR forward (a5, a6)
 // loss[r] = sigmoid(sum_{j in row r} w_u[uidx[j]]) - label[r]
@@ -301,18 +306,6 @@ k_lr_grad_tiled(xf::TableDev T, const uint32_t *__restrict__ tile_ptr, uint32_t 
 // them takes milliseconds.  Every heavy key is cut into chunks of XF_TILE_NNZ occurrences
 // (heavy_chunk_ptr, built with the batch), one workgroup reduces one chunk, and a second
 // small kernel adds a key's chunk sums in chunk order (deterministic) and applies the step.
-__device__ __forceinline__ uint32_t heavy_of_chunk(const uint32_t *__restrict__ hch, uint32_t H,
-                                                   uint32_t c) {
-  uint32_t lo = 0, hi = H;  // largest h with hch[h] <= c
-  while (hi - lo > 1) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (hch[mid] <= c) lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
-
 // the same by a whole wavefront: 64 probes per round (three dependent loads for any H up to
 // 2^18 instead of log2 H; every lane returns the answer)
 __device__ __forceinline__ uint32_t heavy_of_chunk_wave(const uint32_t *__restrict__ hch,
@@ -1073,13 +1066,6 @@ constexpr size_t kFlatForwardBytes = (size_t)4 << 20;
 // blocks for one wavefront per item
 inline unsigned waves_grid(uint32_t n) { return (unsigned)(((size_t)n * 64 + kBlock - 1) / kBlock); }
 
-inline int blocks_for_groups(uint32_t n_items, int items_per_block) {
-  size_t g = ((size_t)n_items + items_per_block - 1) / items_per_block;
-  if (g > 8192) g = 8192;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
 
 // ------------------------------------------------ reference-order forward (parity mode 1)
@@ -1607,6 +1593,14 @@ struct xf_workspace {
   // parity mode: 0 = row / key sums exact in fp64 (the production path); 1 = "reference order":
   // the forward's row sums as fp32 running sums in the reference's own order (slow kernels)
   int parity = 0;
+  // FM form: XF_FM_REFERENCE (pooled sums, as fm_worker.cc) or XF_FM_CANONICAL (per-factor)
+  int fm_mode = XF_FM_REFERENCE;
+  float *fmc_S = nullptr;      // canonical FM: the per-factor row sums, R x k
+  size_t capS = 0;
+  float *fmc_vu = nullptr;     // canonical FM: the pulled factor rows, U x k
+  size_t capVu = 0;
+  double *fmc_hpart = nullptr; // canonical FM: the heavy keys' chunk sums
+  size_t capHpart = 0;
   uint32_t lastU = 0, lastR = 0;
   // optional per-kernel HIP-event timing (same stream, inside the caller's timed region)
   bool profiling = false;
@@ -1632,7 +1626,8 @@ struct xf_workspace {
   int nmark = 0;
 };
 
-static int ws_reserve(xf_workspace *ws, size_t U, size_t UK, size_t R) {
+// fm_pooled = false: not the reference-form FM's factor scratch (v_u, gv, the per-key records)
+static int ws_reserve(xf_workspace *ws, size_t U, size_t UK, size_t R, bool fm_pooled = true) {
   auto grow = [](void **p, size_t bytes) -> hipError_t {
     if (*p) {
       hipError_t e = hipFree(*p);
@@ -1648,7 +1643,7 @@ static int ws_reserve(xf_workspace *ws, size_t U, size_t UK, size_t R) {
     XF_HIP(grow((void **)&ws->g, m * 4));
     ws->capU = m;
   }
-  if (!ws->vu || UK > ws->capUK) {
+  if (fm_pooled && (!ws->vu || UK > ws->capUK)) {
     const size_t m = std::max<size_t>(UK + UK / 8, 1024);
     XF_HIP(grow((void **)&ws->vu, m * 4));
     XF_HIP(grow((void **)&ws->gv, m * 4));
@@ -1674,7 +1669,8 @@ extern "C" int xf_workspace_create(xf_workspace **out) {
 extern "C" int xf_workspace_destroy(xf_workspace *ws) {
   if (!ws) return XF_OK;
   void *ps[] = {ws->slots, ws->slots2, ws->wu,   ws->g,  ws->vu,      ws->gv,
-                ws->loss,  ws->pctr,   ws->vsum, ws->ks, ws->partial, ws->gdense};
+                ws->loss,  ws->pctr,   ws->vsum, ws->ks, ws->partial, ws->gdense,
+                ws->fmc_S, ws->fmc_hpart, ws->fmc_vu};
   for (void *p : ps)
     if (p) hipFree(p);
   for (auto &e : ws->sets)
@@ -1778,7 +1774,21 @@ static int ws_reserve_cells(xf_workspace *ws, const xf_cells *c, bool dense_g) {
 extern "C" int xf_workspace_parity(xf_workspace *ws, int mode) {
   XF_REQUIRE(ws && (mode == XF_PARITY_EXACT_SUMS || mode == XF_PARITY_REFERENCE_ORDER),
              "xf_workspace_parity: bad argument");
+  XF_REQUIRE(mode == XF_PARITY_EXACT_SUMS || ws->fm_mode != XF_FM_CANONICAL,
+             "xf_workspace_parity: the reference-order mode is the reference form's; this "
+             "workspace runs canonical FM (xf_workspace_fm_mode), whose sums are exact only");
   ws->parity = mode;
+  return XF_OK;
+}
+
+extern "C" int xf_workspace_fm_mode(xf_workspace *ws, int mode) {
+  XF_REQUIRE(ws, "xf_workspace_fm_mode: null workspace");
+  XF_REQUIRE(mode == XF_FM_REFERENCE || mode == XF_FM_CANONICAL,
+             "xf_workspace_fm_mode: mode must be XF_FM_REFERENCE (0) or XF_FM_CANONICAL (1)");
+  XF_REQUIRE(mode == XF_FM_REFERENCE || ws->parity == XF_PARITY_EXACT_SUMS,
+             "xf_workspace_fm_mode: canonical FM has no reference-order parity mode; this "
+             "workspace is in XF_PARITY_REFERENCE_ORDER (xf_workspace_parity)");
+  ws->fm_mode = mode;
   return XF_OK;
 }
 
@@ -2084,11 +2094,103 @@ static int fm_prepare_records(xf_table *w, xf_table *vt, xf_batch *b, bool fresh
   return XF_OK;
 }
 
+// ---- canonical FM (xf_workspace_fm_mode; kernels in xf_fm_canonical.hip)
+static int fmc_reserve(xf_workspace *ws, const xf_batch *b, int k) {
+  const size_t nV = std::max<size_t>((size_t)b->U * k, 1);
+  if (nV > ws->capVu) {
+    if (ws->fmc_vu) XF_HIP(hipFree(ws->fmc_vu));
+    ws->fmc_vu = nullptr;
+    ws->capVu = 0;
+    XF_HIP(hipMalloc((void **)&ws->fmc_vu, (nV + nV / 8 + 1024) * 4));
+    ws->capVu = nV + nV / 8 + 1024;
+  }
+  const size_t nS = std::max<size_t>((size_t)b->R * k, 1);
+  if (nS > ws->capS) {
+    if (ws->fmc_S) XF_HIP(hipFree(ws->fmc_S));
+    ws->fmc_S = nullptr;
+    ws->capS = 0;
+    XF_HIP(hipMalloc((void **)&ws->fmc_S, (nS + nS / 8 + 1024) * 4));
+    ws->capS = nS + nS / 8 + 1024;
+  }
+  const size_t nH = std::max<size_t>(xf::fmc_heavy_doubles(&b->view, k), 1);
+  if (nH > ws->capHpart) {
+    if (ws->fmc_hpart) XF_HIP(hipFree(ws->fmc_hpart));
+    ws->fmc_hpart = nullptr;
+    ws->capHpart = 0;
+    XF_HIP(hipMalloc((void **)&ws->fmc_hpart, (nH + nH / 8 + 1024) * 8));
+    ws->capHpart = nH + nH / 8 + 1024;
+  }
+  return XF_OK;
+}
+
+static int fmc_check_batch(const xf_batch *b, const char *who) {
+  XF_REQUIRE(!b->fm_keyed || b->U == 0,
+             "%s: canonical FM needs a minibatch with an index of its key list; this one comes "
+             "from the keyed build against the tables' settled tiers (xf_batch_compile_fm*): "
+             "compile it with xf_batch_compile_dev / xf_batch_compile_gpu", who);
+  return XF_OK;
+}
+
+// One canonical FM update: the two Pulls (w gathered with the rows, v rows gathered), the
+// forward (loss, S), the gradient + both Pushes.  Both tables are written by kernels that keep no
+// per-row records: the reference-mode records of any minibatch are rebuilt before they are read.
+static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
+                             void *stream) {
+  XF_TRY(fmc_check_batch(b, "xf_fm_step"));
+  XF_REQUIRE(ws->parity == XF_PARITY_EXACT_SUMS, "xf_fm_step: canonical FM with a parity mode");
+  const int k = xf::table_dim(vt);
+  XF_TRY(xf_batch_upload(b, stream));
+  XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
+  XF_TRY(fmc_reserve(ws, b, k));
+  ws->rec = ws->profiling && ws->step_no++ % xf_workspace::kProfileEvery == 0;
+  if (ws->rec) XF_TRY(ws_next_set(ws));
+  const xf_dev_batch &v = b->view;
+  ws->lastU = b->U;
+  ws->lastR = b->R;
+  XF_BEGIN();
+  XF_TRY(fm_resolve_rows(w, vt, b, ws, stream, true, nullptr));  // :228, 231 (w gathered)
+  const uint32_t *rows_w = v.U ? b->d_fm_rows[0] : ws->slots;
+  const uint32_t *rows_v = v.U ? b->d_fm_rows[1] : ws->slots2;
+  XF_END(kEvResolve);
+  if (v.U) XF_TRY(xf_table_gather_dev(vt, rows_v, v.U, ws->fmc_vu, stream));
+  XF_END(kEvGather);
+  XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr, S(stream)));
+  XF_END(kEvForward);
+  if (v.U && v.R) {
+    xf::table_note_write(w);
+    xf::table_note_write(vt);
+    XF_TRY(xf::fmc_grad_update(w, vt, &v, rows_w, rows_v, ws->wu, ws->fmc_vu, ws->fmc_S,
+                               ws->loss, ws->g, ws->fmc_hpart, S(stream)));
+  }
+  XF_END(kEvGrad);
+  if (ws->rec) ws->sets[ws->cur].pending = true;
+  return XF_OK;
+}
+
+// forward only: pulls (and so inserts) the keys, as the reference-mode predict does
+static int fm_canonical_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
+                                float *pctr_out) {
+  XF_TRY(fmc_check_batch(b, "xf_fm_predict"));
+  const int k = xf::table_dim(vt);
+  XF_TRY(xf_batch_upload(b, nullptr));
+  XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
+  XF_TRY(fmc_reserve(ws, b, k));
+  const xf_dev_batch &v = b->view;
+  XF_TRY(xf_table_pull_dev(w, v.ukeys, v.U, ws->slots, ws->wu, nullptr));
+  XF_TRY(xf_table_resolve_dev(vt, v.ukeys, v.U, ws->slots2, nullptr));
+  XF_TRY(xf_table_gather_dev(vt, ws->slots2, v.U, ws->fmc_vu, nullptr));
+  XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr, nullptr));
+  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(xf_table_check(w, nullptr));
+  return xf_table_check(vt, nullptr);
+}
+
 extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
                           void *stream) {
   XF_REQUIRE(w && vt && b && ws, "xf_fm_step: null argument");
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_fm_step: the w table must have dim 1");
   XF_REQUIRE(!b->local, "xf_fm_step: needs a minibatch with a key list (xf_batch_compile*)");
+  if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_step(w, vt, b, ws, stream);
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, stream));
   XF_TRY(ws_reserve(ws, b->U, (size_t)b->U * k, b->R));
@@ -2361,6 +2463,7 @@ extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
                              float *pctr_out) {
   XF_REQUIRE(w && vt && b && ws && pctr_out, "xf_fm_predict: null argument");
   XF_REQUIRE(!b->local, "xf_fm_predict: needs a minibatch with a key list (xf_batch_compile*)");
+  if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_predict(w, vt, b, ws, pctr_out);
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, nullptr));
   XF_TRY(ws_reserve(ws, b->U, (size_t)b->U * k, b->R));

@@ -70,6 +70,7 @@ int table_head_rows(const uint64_t *d_keys_sorted, const uint32_t *d_order,
                     const uint32_t *d_rows, size_t n, uint32_t *d_hrow, hipStream_t s);
 int table_update_heads(xf_table *t, const uint32_t *d_hrow, const uint32_t *d_order, size_t n,
                        const float *d_grads, hipStream_t s);
+void table_set_init(xf_table *t, int kind, float init_const, uint64_t seed);
 }  // namespace xf
 
 namespace {
@@ -212,6 +213,7 @@ struct xf_sharded {
   xf_table *tw = nullptr, *tv = nullptr;
   xf_workspace *ws = nullptr;  // world 1: the fused step's scratch
   int parity_mode = XF_PARITY_EXACT_SUMS;  // (what xf_sharded_set_parity last set)
+  int fm_mode = XF_FM_REFERENCE;           // (what xf_sharded_set_fm_mode last set)
   uint64_t seen_upper = 0;     // world 1: host-side upper bound on the keys in the table
   Dev<double> partial;         // LR forward scratch
   // the owner-compute compile's staging: the worker's nonzeros grouped by owner (sent from
@@ -1497,7 +1499,7 @@ extern "C" int xf_sharded_compile(xf_sharded *st, xf_sbatch **out, const uint64_
     else if (st->cfg.model == 0)
       XF_TRY(xf_batch_compile_local(&b->b, st->tw, rowptr, keys, labels, row_begin, row_end,
                                     keep, s));
-    else if (st->tv && st->parity_mode == XF_PARITY_EXACT_SUMS)
+    else if (st->tv && st->parity_mode == XF_PARITY_EXACT_SUMS && st->fm_mode == XF_FM_REFERENCE)
       // FM: against the tables' settled tiers when every key sits there (no sort; otherwise
       // this is xf_batch_compile_gpu)
       XF_TRY(xf_batch_compile_fm(&b->b, st->tw, st->tv, rowptr, keys, labels, row_begin, row_end,
@@ -1554,7 +1556,7 @@ extern "C" int xf_sharded_compile_dev(xf_sharded *st, xf_sbatch **out, const uin
     if (st->cfg.model == 0)
       XF_TRY(xf_batch_compile_local_dev(&b->b, st->tw, d_keys, d_rowptr, d_labels, R, NNZ, keep,
                                         s));
-    else if (st->tv && st->parity_mode == XF_PARITY_EXACT_SUMS)
+    else if (st->tv && st->parity_mode == XF_PARITY_EXACT_SUMS && st->fm_mode == XF_FM_REFERENCE)
       XF_TRY(xf_batch_compile_fm_dev(&b->b, st->tw, st->tv, d_keys, d_rowptr, d_labels, R, NNZ, s,
                                      nullptr));
     else
@@ -1770,6 +1772,32 @@ extern "C" int xf_sharded_set_parity(xf_sharded *st, int mode) {
   // list: the reference-order step refuses those; minibatches compiled from here on are built
   // for the mode set)
   st->parity_mode = mode;
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_set_fm_mode(xf_sharded *st, int mode) {
+  XF_REQUIRE(st, "xf_sharded_set_fm_mode: null trainer");
+  XF_REQUIRE(mode == XF_FM_REFERENCE || mode == XF_FM_CANONICAL,
+             "xf_sharded_set_fm_mode: mode must be XF_FM_REFERENCE (0) or XF_FM_CANONICAL (1)");
+  XF_REQUIRE(st->cfg.model == 1 && st->tv, "xf_sharded_set_fm_mode: not an FM trainer");
+  XF_REQUIRE(st->world == 1 && st->fused && st->ws,
+             "xf_sharded_set_fm_mode: canonical FM runs on one rank only (world %d): the "
+             "exchanges of several ranks carry the reference form's row sums", st->world);
+  uint64_t nw = 0, nv = 0;
+  XF_TRY(xf_table_size(st->tw, &nw));
+  XF_TRY(xf_table_size(st->tv, &nv));
+  XF_REQUIRE(nw == 0 && nv == 0,
+             "xf_sharded_set_fm_mode: the tables hold keys already (%llu, %llu): set the FM form "
+             "before the first step", (unsigned long long)nw, (unsigned long long)nv);
+  XF_TRY(xf_workspace_fm_mode(st->ws, mode));
+  // canonical: hash-normal factors for both optimizers (SGD's constant init would give every
+  // factor of a key the same gradient forever); the reference form keeps sgd.h:67-72
+  if (st->cfg.optimizer == XF_OPT_SGD) {
+    if (mode == XF_FM_CANONICAL) xf::table_set_init(st->tv, XF_INIT_HASHNORM, 0.0f, st->cfg.seed);
+    else
+      xf::table_set_init(st->tv, XF_INIT_CONST, 0.001f, 0);
+  }
+  st->fm_mode = mode;
   return XF_OK;
 }
 

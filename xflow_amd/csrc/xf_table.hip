@@ -2336,4 +2336,13 @@ bool table_records_all_is(const xf_table *t, const uint64_t key[5]) {
 // weight writes so far by code that does not maintain the records; table_note_write: one more
 uint64_t table_writes(const xf_table *t) { return t->writes; }
 void table_note_write(xf_table *t) { ++t->writes; }
+// the first-touch init of the rows inserted from now on (a caller switches an empty table)
+void table_set_init(xf_table *t, int kind, float init_const, uint64_t seed) {
+  t->cfg.init_kind = kind;
+  t->cfg.init_const = init_const;
+  t->cfg.seed = seed;
+  t->T.init_kind = kind;
+  t->T.init_const = init_const;
+  t->T.seed = seed;
+}
 }  // namespace xf

@@ -100,6 +100,7 @@ int Worker::create_tables() {
   c.update_rule = update_rule;
   XF_TRY(xf_sharded_create(&sharded_, group_, &c));
   if (parity != XF_PARITY_EXACT_SUMS) XF_TRY(xf_sharded_set_parity(sharded_, parity));
+  if (fm_mode != XF_FM_REFERENCE) XF_TRY(xf_sharded_set_fm_mode(sharded_, fm_mode));
   XF_TRY(xf_sharded_tables(sharded_, &table_w_, &table_v_));
   // One update() and one predict of a two-row minibatch on a private single-shard trainer: the
   // first launch of a kernel loads its code object and the builders size their scratch on first
@@ -114,7 +115,8 @@ int Worker::create_tables() {
     const int32_t lab[2] = {0, 1};
     float p[2];
     xf_sbatch *b = nullptr;
-    int rc = xf_sharded_compile(warm, &b, rp, keys, lab, 0, 2, 1);
+    int rc = fm_mode != XF_FM_REFERENCE ? xf_sharded_set_fm_mode(warm, fm_mode) : XF_OK;
+    if (rc == XF_OK) rc = xf_sharded_compile(warm, &b, rp, keys, lab, 0, 2, 1);
     if (rc == XF_OK) rc = xf_sharded_step(warm, b);
     if (rc == XF_OK) rc = xf_sharded_predict(warm, b, p);
     if (b) xf_sbatch_free(b);
@@ -662,6 +664,18 @@ int Worker::predict(int rank, int block, bool reader) {
 
 // train (lr_worker.cc:207-217, fm_worker.cc:277-287)
 int Worker::train() {
+  if (fm_mode == XF_FM_CANONICAL && !sharded_) {  // before any rendezvous of a group
+    XF_REQUIRE(model_ == 1, "XFStartTrain: fm_mode=canonical needs model 1 (FM), not model %d",
+               model_);
+    int w = world;
+    if (w <= 0) {
+      const char *v = env_first({"WORLD_SIZE", "XF_WORLD", "DMLC_NUM_WORKER"});
+      w = v ? atoi(v) : 1;
+    }
+    XF_REQUIRE(w <= 1, "XFStartTrain: fm_mode=canonical runs on one worker only (world %d)", w);
+    XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS,
+               "XFStartTrain: fm_mode=canonical has no parity=reference_order mode");
+  }
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
   std::cout << "my rank is = " << rank << std::endl;
@@ -760,6 +774,12 @@ int Worker::set_param(const char *name, const char *value) {
     else if (!strcmp(value, "reference_order")) parity = XF_PARITY_REFERENCE_ORDER;
     else
       return xf::set_error(XF_EINVAL, "XFSetParam: parity must be exact or reference_order");
+  } else if (n == "fm_mode") {
+    XF_REQUIRE(!sharded_, "XFSetParam: fm_mode cannot change after training started");
+    if (!strcmp(value, "reference")) fm_mode = XF_FM_REFERENCE;
+    else if (!strcmp(value, "canonical")) fm_mode = XF_FM_CANONICAL;
+    else
+      return xf::set_error(XF_EINVAL, "XFSetParam: fm_mode must be reference or canonical");
   } else if (n == "key_build") {
     if (!strcmp(value, "gpu")) key_build_gpu = true;
     else if (!strcmp(value, "host")) key_build_gpu = false;

@@ -6,16 +6,23 @@ class SingleGpuTrainer:
     """One shard, one GPU: LRWorker::update / FMWorker::update on device-resident batches."""
 
     def __init__(self, model="lr", optimizer="ftrl", k=10, capacity=1 << 22, seed=7,
-                 rank=0, world=1, **hyper):
+                 rank=0, world=1, fm_mode="reference", **hyper):
+        """fm_mode (FM): "reference" (the reference's pooled second-order term) or "canonical"
+        (Rendle's per-factor form; the v table starts hash-normal for both optimizers)"""
         assert world == 1
+        assert fm_mode in capi.FM_MODES, fm_mode
         opt = capi.OPT_FTRL if optimizer == "ftrl" else capi.OPT_SGD
         self.model = model
+        self.fm_mode = fm_mode if model == "fm" else "reference"
         self.w = capi.Table(opt, 1, capi.INIT_ZERO, capacity=capacity, **hyper)
         self.v = None
         if model == "fm":
-            init = capi.INIT_HASHNORM if opt == capi.OPT_FTRL else capi.INIT_CONST
+            hashnorm = opt == capi.OPT_FTRL or self.fm_mode == "canonical"
+            init = capi.INIT_HASHNORM if hashnorm else capi.INIT_CONST
             self.v = capi.Table(opt, k, init, 0.001, seed=seed, capacity=capacity, **hyper)
         self.ws = capi.Workspace()
+        if self.fm_mode != "reference":
+            self.ws.fm_mode(self.fm_mode)
 
     def compile(self, rowptr, keys, labels):
         if self.model == "lr":   # sort-free key build against the table (cells)
