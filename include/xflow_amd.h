@@ -55,7 +55,8 @@ uint32_t xf_shard_of(uint64_t key, uint32_t nshards);
 /* ---------------------------------------------------------------- text block reader   */
 /* load_minibatch_hash_data_fread (load_data_from_disk.cc:103-210): block = what fits in
  * cap_bytes-1 bytes, cut at the last newline when the buffer fills; label = atof > 1e-7;
- * key = hash of the middle field of fgid:fid:val; val is never read. */
+ * key = hash of the middle field of fgid:fid:val; val is read only by a reader with feature
+ * values switched on (xf_reader_set_values, below). */
 typedef struct xf_reader xf_reader;
 int xf_reader_open(xf_reader **out, const char *path, size_t cap_bytes);
 /* The same reader over a binarized block cache: when `cache_path` holds the
@@ -82,6 +83,20 @@ int xf_block_destroy(xf_block *b);
 int xf_reader_next_into(xf_reader *r, xf_block *blk, size_t *rows_out, size_t *nnz_out,
                         const uint64_t **rowptr, const uint64_t **keys, const int32_t **fgid,
                         const int32_t **labels);
+
+/* ---- feature values (not in the reference: its parser stops at the second field) ----
+ * xf_reader_set_values(r, 1), before the first block: every token's third field — the bytes after
+ * the second colon up to the blank or the end of the line; further colons belong to it — is
+ * converted too, value = (float)atof(field), an empty field is 0; an empty token, which duplicates
+ * the row's previous key, duplicates its value.  A field of 48 bytes or more, or a value that is
+ * not finite, is XF_EPARSE.  Labels, keys, block boundaries and row order do not change.  The
+ * values run beside the keys (nnz floats): xf_reader_values for the reader-owned arrays of
+ * xf_reader_next, xf_block_values for a block of xf_reader_next_into / xf_reader_parse_text.  The
+ * block cache and the GPU tokeniser carry no values: a reader opened with xf_reader_open_cached
+ * refuses (XF_EINVAL). */
+int xf_reader_set_values(xf_reader *r, int on);
+int xf_reader_values(xf_reader *r, const float **vals);
+int xf_block_values(xf_block *blk, const float **vals);
 
 /* ---- the block as text, for a caller that tokenises it itself (xf_ingest_*) ----
  * xf_reader_peek_text: the next block's text by the block rule above (*len = 0 at the end of the
@@ -156,6 +171,29 @@ int xf_batch_compile_dev(xf_batch **out, const uint64_t *d_keys, const uint32_t 
                          const int32_t *d_labels, uint32_t R, uint32_t NNZ, void *stream);
 int xf_batch_compile_gpu(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
                          const int32_t *labels, size_t row_begin, size_t row_end, void *stream);
+/* The generic build of a minibatch WITH FEATURE VALUES (vals[] / d_vals[] beside keys[]): the
+ * arrays above plus xval[NNZ] in CSR order (beside uidx) and coo_val[NNZ] in key-grouped order
+ * (beside coo_row), on the device, where the _dev / _gpu builds make them (coo_val[j] =
+ * xval[position of sorted entry j], the line that writes coo_row); the host build gives the
+ * same arrays.  xf_dev_batch is that of a binary minibatch: the two value arrays come from
+ * xf_batch_values_dev (after xf_batch_upload for a host-built batch; NULLs for a binary
+ * minibatch), their host views from xf_batch_values_host.  xf_lr_step / xf_lr_predict and, with
+ * XF_FM_CANONICAL, xf_fm_step / xf_fm_predict compute with x = val on such a minibatch:
+ *   wx_r = sum_j w[u_j] x_j, S[r,f] = sum_j v[u_j,f] x_j, y2 = 0.5 (sum_f S^2 - sum_f sum_j (v x)^2),
+ *   gw[u] = (sum_occ loss x) / R, gv[u,f] = (sum_occ loss x (S[r,f] - v[u,f] x)) / R
+ * (exact fp64 sums of fp32 products; all values 1: the binary path's results bit for bit).
+ * XF_FM_REFERENCE, XF_PARITY_REFERENCE_ORDER and xf_workspace_capture refuse it (XF_EINVAL). */
+int xf_batch_compile_valued(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
+                            const float *vals, const int32_t *labels, size_t row_begin,
+                            size_t row_end);
+int xf_batch_compile_valued_dev(xf_batch **out, const uint64_t *d_keys, const float *d_vals,
+                                const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
+                                uint32_t NNZ, void *stream);
+int xf_batch_compile_valued_gpu(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
+                                const float *vals, const int32_t *labels, size_t row_begin,
+                                size_t row_end, void *stream);
+int xf_batch_values_dev(const xf_batch *b, const float **xval, const float **coo_val);
+int xf_batch_values_host(const xf_batch *b, const float **xval, const float **coo_val);
 /* The FM key build (fm_worker.cc:205-225) against the tables themselves: when every key of the
  * minibatch sits in the v table's settled tier (xf_table_defrag) and the w table numbers its rows
  * the same way, the key list comes with its state rows, the key-grouped occurrence lists and
@@ -601,6 +639,15 @@ int xf_sharded_compile(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
 int xf_sharded_compile_dev(xf_sharded *st, xf_sbatch **out, const uint64_t *d_keys,
                            const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
                            uint32_t NNZ, int keep);
+/* The same with feature values (xf_batch_compile_valued_gpu / _dev; the host build with
+ * host_key_build): LR, and FM after xf_sharded_set_fm_mode(XF_FM_CANONICAL), on a trainer of one
+ * rank — more than one: XF_EINVAL.  xf_sharded_step / _predict take the result as any other. */
+int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
+                              const uint64_t *keys, const float *vals, const int32_t *labels,
+                              size_t row_begin, size_t row_end, int keep);
+int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out, const uint64_t *d_keys,
+                                  const float *d_vals, const uint32_t *d_rowptr,
+                                  const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep);
 int xf_sbatch_free(xf_sbatch *b);
 int xf_sbatch_dims(const xf_sbatch *b, uint32_t *R, uint32_t *NNZ, uint32_t *U,
                    uint64_t *n_owned /* keys of this minibatch (all ranks) this rank owns */);
@@ -661,6 +708,9 @@ int XFDestroy(void **h);
  *        order — one worker, checking mode)
  *        fm_mode(reference|canonical: FM's second-order term as the reference writes it, or
  *        Rendle's per-factor form — xf_workspace_fm_mode; canonical: model 1, one worker)
+ *        feature_values(off|on: a nonzero contributes x = val, the third field of
+ *        fgid:fid:val, instead of 1 — model 0, or model 1 with fm_mode=canonical; one worker,
+ *        parity=exact, block_cache=0, ingest=host)
  *        model_in model_out (model file to load before / save after training)
  *        block_cache(0|1) block_cache_dir (binarized block cache of the text files)
  *        ingest(host|gpu: the text of a block tokenised and hashed on the GPU, xf_ingest_*;

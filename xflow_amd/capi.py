@@ -92,6 +92,21 @@ SIGNATURES = {
     "xf_reader_next": (C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                  C.POINTER(u64p), C.POINTER(u64p), C.POINTER(i32p),
                                  C.POINTER(i32p)]),
+    "xf_reader_set_values": (C.c_int, [vp, C.c_int]),
+    "xf_reader_values": (C.c_int, [vp, C.POINTER(f32p)]),
+    "xf_block_values": (C.c_int, [vp, C.POINTER(f32p)]),
+    "xf_batch_compile_valued": (C.c_int, [C.POINTER(vp), u64p, u64p, f32p, i32p, C.c_size_t,
+                                          C.c_size_t]),
+    "xf_batch_compile_valued_dev": (C.c_int, [C.POINTER(vp), vp, vp, vp, vp, C.c_uint32,
+                                              C.c_uint32, vp]),
+    "xf_batch_compile_valued_gpu": (C.c_int, [C.POINTER(vp), u64p, u64p, f32p, i32p, C.c_size_t,
+                                              C.c_size_t, vp]),
+    "xf_batch_values_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
+    "xf_batch_values_host": (C.c_int, [vp, C.POINTER(f32p), C.POINTER(f32p)]),
+    "xf_sharded_compile_valued": (C.c_int, [vp, C.POINTER(vp), u64p, u64p, f32p, i32p,
+                                            C.c_size_t, C.c_size_t, C.c_int]),
+    "xf_sharded_compile_valued_dev": (C.c_int, [vp, C.POINTER(vp), vp, vp, vp, vp, C.c_uint32,
+                                                C.c_uint32, C.c_int]),
     "xf_scratch_reserve": (C.c_int, [C.c_size_t]),
     "xf_batch_pool_reserve": (C.c_int, [C.c_size_t]),
     "xf_batch_compile": (C.c_int, [C.POINTER(vp), u64p, u64p, i32p, C.c_size_t, C.c_size_t]),
@@ -337,9 +352,10 @@ def hash_decimal_ids(ids):
     return out
 
 
-def read_blocks(path, cap_bytes, cache_path=None, info=None):
+def read_blocks(path, cap_bytes, cache_path=None, info=None, values=False):
     """Yield (rowptr, keys, fgid, labels) numpy copies per text block.  With `cache_path` the
-    blocks come from / go to the binarized block cache; info["from_cache"] says which."""
+    blocks come from / go to the binarized block cache; info["from_cache"] says which.
+    values=True: the feature values (float32, beside keys) as a fifth array."""
     L = lib()
     h = vp()
     if cache_path is None:
@@ -351,6 +367,8 @@ def read_blocks(path, cap_bytes, cache_path=None, info=None):
         if info is not None:
             info["from_cache"] = bool(hit.value)
     try:
+        if values:
+            check(L.xf_reader_set_values(h, 1))
         while True:
             rows, nnz = C.c_size_t(0), C.c_size_t(0)
             rp, ks, fg, lb = u64p(), u64p(), i32p(), i32p()
@@ -359,10 +377,15 @@ def read_blocks(path, cap_bytes, cache_path=None, info=None):
             if rows.value == 0:
                 return
             r, n = rows.value, nnz.value
-            yield (np.ctypeslib.as_array(rp, (r + 1,)).copy(),
+            blk = (np.ctypeslib.as_array(rp, (r + 1,)).copy(),
                    np.ctypeslib.as_array(ks, (n,)).copy() if n else np.zeros(0, np.uint64),
                    np.ctypeslib.as_array(fg, (n,)).copy() if n else np.zeros(0, np.int32),
                    np.ctypeslib.as_array(lb, (r,)).copy())
+            if values:
+                vs = f32p()
+                check(L.xf_reader_values(h, C.byref(vs)))
+                blk += (np.ctypeslib.as_array(vs, (n,)).copy() if n else np.zeros(0, np.float32),)
+            yield blk
     finally:
         L.xf_reader_close(h)
 
@@ -449,16 +472,32 @@ class Ingest:
 class Batch:
     """A compiled minibatch (host arrays; device mirror after upload())."""
 
-    def __init__(self, rowptr, keys, labels, row_begin=0, row_end=None, on_gpu=False):
+    def __init__(self, rowptr, keys, labels, row_begin=0, row_end=None, on_gpu=False,
+                 values=None):
         """on_gpu=False: host key build (xf_batch_compile); True: the GPU one
-        (xf_batch_compile_gpu), the batch is then already device-resident."""
+        (xf_batch_compile_gpu), the batch is then already device-resident.  values (float32,
+        beside keys): a minibatch with feature values (xf_batch_compile_valued / _gpu)."""
         rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
         if row_end is None:
             row_end = len(rowptr) - 1
         self.h = vp()
-        if on_gpu:
+        self.valued = values is not None
+        if self.valued:
+            values = np.ascontiguousarray(values, dtype=np.float32)
+            assert len(values) == len(keys), "one value per key"
+            if len(values) == 0:
+                values = np.zeros(1, np.float32)   # a non-null pointer
+            if on_gpu:
+                check(lib().xf_batch_compile_valued_gpu(
+                    C.byref(self.h), _p(rowptr, u64p), _p(keys, u64p), _p(values, f32p),
+                    _p(labels, i32p), row_begin, row_end, None))
+            else:
+                check(lib().xf_batch_compile_valued(
+                    C.byref(self.h), _p(rowptr, u64p), _p(keys, u64p), _p(values, f32p),
+                    _p(labels, i32p), row_begin, row_end))
+        elif on_gpu:
             check(lib().xf_batch_compile_gpu(C.byref(self.h), _p(rowptr, u64p), _p(keys, u64p),
                                              _p(labels, i32p), row_begin, row_end, None))
         else:
@@ -489,6 +528,15 @@ class Batch:
                     uidx=arr(ui, self.NNZ, np.uint32), segptr=arr(sp, self.U + 1, np.uint32),
                     coo_row=arr(cr, self.NNZ, np.uint32), labels=arr(lb, self.R, np.int32),
                     heavy=arr(hv, self.H, np.uint32))
+
+    def values(self):
+        """(xval, coo_val) of a valued minibatch: the values in CSR order and grouped by key"""
+        xv, cv = f32p(), f32p()
+        check(lib().xf_batch_values_host(self.h, C.byref(xv), C.byref(cv)))
+        if not self.valued or self.NNZ == 0:
+            return np.zeros(0, np.float32), np.zeros(0, np.float32)
+        return (np.ctypeslib.as_array(xv, (self.NNZ,)).copy(),
+                np.ctypeslib.as_array(cv, (self.NNZ,)).copy())
 
     def panels(self):
         P, pp, pi = C.c_uint32(0), u32p(), u32p()
@@ -947,7 +995,8 @@ class Sharded:
 
     __del__ = close
 
-    def compile(self, rowptr, keys, labels, row_begin=0, row_end=None, keep=True):
+    def compile(self, rowptr, keys, labels, row_begin=0, row_end=None, keep=True, values=None):
+        """values (float32, beside keys): a minibatch with feature values, one rank only"""
         rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
@@ -956,6 +1005,15 @@ class Sharded:
         if row_end is None:
             row_end = len(rowptr) - 1
         h = vp()
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float32)
+            assert len(values) == len(keys), "one value per key"
+            if len(values) == 0:
+                values = np.zeros(1, np.float32)
+            check(lib().xf_sharded_compile_valued(
+                self.h, C.byref(h), _p(rowptr, u64p), _p(keys, u64p), _p(values, f32p),
+                _p(labels, i32p), row_begin, row_end, 1 if keep else 0))
+            return ShardedBatch(h, self)
         check(lib().xf_sharded_compile(self.h, C.byref(h), _p(rowptr, u64p), _p(keys, u64p),
                                        _p(labels, i32p), row_begin, row_end, 1 if keep else 0))
         return ShardedBatch(h, self)
@@ -966,6 +1024,13 @@ class Sharded:
         h = vp()
         check(lib().xf_sharded_compile_dev(self.h, C.byref(h), d_keys, d_rowptr, d_labels, R, NNZ,
                                            1 if keep else 0))
+        return ShardedBatch(h, self)
+
+    def compile_valued_dev(self, d_keys, d_vals, d_rowptr, d_labels, R, NNZ, keep=True):
+        """compile_dev with the feature values (f32, beside the keys) as a device pointer"""
+        h = vp()
+        check(lib().xf_sharded_compile_valued_dev(self.h, C.byref(h), d_keys, d_vals, d_rowptr,
+                                                  d_labels, R, NNZ, 1 if keep else 0))
         return ShardedBatch(h, self)
 
     def step(self, b):

@@ -335,8 +335,9 @@ extern "C" int xf_batch_panels(const xf_batch *b, uint32_t *P, const uint32_t **
   return XF_OK;
 }
 
-extern "C" int xf_batch_compile(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
-                                const int32_t *labels, size_t row_begin, size_t row_end) {
+static int batch_compile_host(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
+                              const float *vals, const int32_t *labels, size_t row_begin,
+                              size_t row_end) {
   XF_REQUIRE(out && rowptr && labels && row_end >= row_begin, "xf_batch_compile: bad argument");
   const size_t R = row_end - row_begin;
   const uint64_t base = rowptr[row_begin];
@@ -373,6 +374,12 @@ extern "C" int xf_batch_compile(xf_batch **out, const uint64_t *rowptr, const ui
     b->uidx[kp[j].pos] = (uint32_t)(b->ukeys.size() - 1);
     b->coo_row[j] = row_of[kp[j].pos];
   }
+  if (vals) {
+    b->valued = true;
+    b->xval.assign(vals + base, vals + base + NNZ);
+    b->coo_val.resize(NNZ);
+    for (size_t j = 0; j < NNZ; ++j) b->coo_val[j] = b->xval[kp[j].pos];
+  }
   b->segptr.push_back((uint32_t)NNZ);
   b->U = (uint32_t)b->ukeys.size();
   for (uint32_t u = 0; u < b->U; ++u)
@@ -385,6 +392,38 @@ extern "C" int xf_batch_compile(xf_batch **out, const uint64_t *rowptr, const ui
   build_panels(b);
   build_tiles(b);
   *out = b;
+  return XF_OK;
+}
+
+extern "C" int xf_batch_compile(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
+                                const int32_t *labels, size_t row_begin, size_t row_end) {
+  return batch_compile_host(out, rowptr, keys, nullptr, labels, row_begin, row_end);
+}
+
+// the same with the nonzeros' values (vals[] runs beside keys[])
+extern "C" int xf_batch_compile_valued(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
+                                       const float *vals, const int32_t *labels, size_t row_begin,
+                                       size_t row_end) {
+  XF_REQUIRE(vals || (rowptr && row_end >= row_begin && rowptr[row_end] == rowptr[row_begin]),
+             "xf_batch_compile_valued: null values");
+  static const float none[1] = {0.0f};
+  return batch_compile_host(out, rowptr, keys, vals ? vals : none, labels, row_begin, row_end);
+}
+
+// device arrays of a valued minibatch (null, null for a binary one); host views likewise
+extern "C" int xf_batch_values_dev(const xf_batch *b, const float **xval, const float **coo_val) {
+  XF_REQUIRE(b, "xf_batch_values_dev: null batch");
+  XF_REQUIRE(!b->valued || b->d_blob, "xf_batch_values_dev: batch not uploaded");
+  if (xval) *xval = b->valued ? b->d_xval : nullptr;
+  if (coo_val) *coo_val = b->valued ? b->d_coo_val : nullptr;
+  return XF_OK;
+}
+
+extern "C" int xf_batch_values_host(const xf_batch *b, const float **xval, const float **coo_val) {
+  XF_REQUIRE(b, "xf_batch_values_host: null batch");
+  XF_TRY(need_host(b));
+  if (xval) *xval = b->valued ? b->xval.data() : nullptr;
+  if (coo_val) *coo_val = b->valued ? b->coo_val.data() : nullptr;
   return XF_OK;
 }
 
@@ -401,6 +440,7 @@ extern "C" int xf_batch_free(xf_batch *b) {
   }
   if (b->d_blob) xf::blob_free(b->d_blob, b->d_blob_bytes);
   if (b->d_blob2) xf::blob_free(b->d_blob2, b->d_blob2_bytes);
+  if (b->d_vals) xf::blob_free(b->d_vals, b->d_vals_bytes);
   if (b->cells) xf::cells_free(b->cells);
   if (b->d_raw) xf::blob_free(b->d_raw, b->d_raw_bytes);
   if (b->d_rows_u) (void)hipFree(b->d_rows_u);
@@ -483,6 +523,17 @@ extern "C" int xf_batch_upload(xf_batch *b, void *stream) {
   if (b->P) {
     XF_HIP(put(o_ftile, b->ftile_ptr.data(), b->ftile_ptr.size() * 4));
     XF_HIP(put(o_forder, b->fpanel_first.data(), b->fpanel_first.size() * 4));
+  }
+  if (b->valued) {
+    const size_t vb = al((size_t)b->NNZ * 4);
+    XF_TRY(xf::blob_alloc((void **)&b->d_vals, 2 * vb + 256, &b->d_vals_bytes));
+    b->d_xval = b->d_vals;
+    b->d_coo_val = (const float *)((const char *)b->d_vals + vb);
+    if (b->NNZ) {
+      XF_HIP(hipMemcpyAsync(b->d_vals, b->xval.data(), (size_t)b->NNZ * 4, hipMemcpyHostToDevice, s));
+      XF_HIP(hipMemcpyAsync((char *)b->d_vals + vb, b->coo_val.data(), (size_t)b->NNZ * 4,
+                            hipMemcpyHostToDevice, s));
+    }
   }
   XF_HIP(hipStreamSynchronize(s));  // host vectors are pageable: finish before returning
   b->d_blob = d;

@@ -21,6 +21,14 @@ struct xf_batch {
   std::vector<uint32_t> ftile_ptr, fpanel_first;  // forward tiles over (panel,row) cells
   uint32_t fwd_grid = 0;
   std::vector<int32_t> labels;
+  // feature values (xf_batch_compile_valued*): xval[NNZ] in CSR order beside uidx, coo_val[NNZ]
+  // in key-grouped order beside coo_row; on the device in an allocation of their own (the
+  // layout of d_blob and xf_dev_batch are those of a binary minibatch)
+  bool valued = false;
+  std::vector<float> xval, coo_val;
+  float *d_vals = nullptr;  // xval | coo_val
+  size_t d_vals_bytes = 0;
+  const float *d_xval = nullptr, *d_coo_val = nullptr;
   bool on_device_only = false;  // built by xf_batch_compile_dev and not downloaded yet
   void *d_blob = nullptr;  // one device allocation holding all arrays
   size_t d_blob_bytes = 0;
@@ -87,7 +95,7 @@ int sort_key_pos(const uint64_t *d_keys, uint32_t n, uint64_t lo, uint64_t span,
 // xf_batch_compile_dev, with or without the panel-major forward view (xf_batch_dev.hip)
 int batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint32_t *d_rowptr,
                          const int32_t *d_labels, uint32_t R, uint32_t NNZ, hipStream_t stream,
-                         bool panels);
+                         bool panels, const float *d_vals = nullptr);
 // LR, the worker side of the weight / gradient exchange (xf_keybuild.hip): a minibatch with its
 // sorted unique keys, row offsets and labels on the device — nothing else — and its cells over
 // the unique-key index.  *done = false: beyond that build's limits, nothing was built.

@@ -90,6 +90,12 @@ __global__ void k_uidx_coo(const uint32_t *__restrict__ spos, const uint32_t *__
   }
 }
 
+// a valued minibatch: the values in key-grouped order, beside coo_row (same gather by position)
+__global__ void k_coo_val(const uint32_t *__restrict__ spos, const float *__restrict__ xval,
+                          size_t n, float *__restrict__ coo_val) {
+  XF_GRID_STRIDE(j, n) coo_val[j] = xval[spos[j]];
+}
+
 // The heavy keys and the keys at which a gradient tile starts (xf_tiling.h), two ascending
 // lists, without arrays of U flags and their U-element scans: a tile starts every ~192 occurrences and
 // heavy keys are rare, so the lists are counted per block of kFlagBlk keys, the ~U / 4096 block
@@ -436,7 +442,7 @@ extern "C" int xf_batch_compile_dev(xf_batch **out, const uint64_t *d_keys,
 // nonzero build)
 int xf::batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint32_t *d_rowptr,
                              const int32_t *d_labels, uint32_t R, uint32_t NNZ, hipStream_t stream,
-                             bool panels) {
+                             bool panels, const float *d_vals) {
   XF_REQUIRE(out && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || d_keys),
              "xf_batch_compile_dev: null argument");
   hipStream_t s = (hipStream_t)stream;
@@ -445,7 +451,22 @@ int xf::batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint3
   b->R = R;
   b->NNZ = NNZ;
   b->on_device_only = true;
+  struct Guard {  // (an early error return frees what the batch owns by then)
+    xf_batch *b;
+    ~Guard() {
+      if (b) xf_batch_free(b);
+    }
+  } guard{d_vals ? b : nullptr};
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  if (d_vals) {  // xval | coo_val, an allocation of the batch's own
+    const size_t vb = al((size_t)NNZ * 4);
+    b->valued = true;
+    XF_TRY(xf::blob_alloc((void **)&b->d_vals, 2 * vb + 256, &b->d_vals_bytes));
+    b->d_xval = b->d_vals;
+    b->d_coo_val = (const float *)((const char *)b->d_vals + vb);
+    if (NNZ)
+      XF_HIP(hipMemcpyAsync(b->d_vals, d_vals, (size_t)NNZ * 4, hipMemcpyDeviceToDevice, s));
+  }
 
   // ---- 1. sort (key, position)
   uint64_t *sk = nullptr;
@@ -478,6 +499,9 @@ int xf::batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint3
                        pos /* reused: iota is no longer needed after the sort */);
     hipLaunchKernelGGL(k_uidx_coo, dim3(grid_for(NNZ)), dim3(kBlock), 0, s, spos, uid1, pos,
                        (size_t)NNZ, uidx, coo);
+    if (d_vals)
+      hipLaunchKernelGGL(k_coo_val, dim3(grid_for(NNZ)), dim3(kBlock), 0, s, spos, d_vals,
+                         (size_t)NNZ, (float *)b->d_coo_val);
   } else {
     XF_HIP(hipMemsetAsync(segptr, 0, 4, s));
   }
@@ -621,8 +645,20 @@ int xf::batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint3
   v.heavy_chunk_ptr = H ? (const uint32_t *)(d + o_hch) : nullptr;
   v.heavy_scratch = H ? (double *)(d + o_hscr) : nullptr;
   v.tile_ptr = (const uint32_t *)(d + o_tile);
+  guard.b = nullptr;
   *out = b;
   return XF_OK;
+}
+
+// The generic build with the nonzeros' values: d_vals[NNZ] runs beside d_keys.  The batch gains
+// xval (CSR order) and coo_val (key-grouped order) on the device — xf_batch_values_dev.
+extern "C" int xf_batch_compile_valued_dev(xf_batch **out, const uint64_t *d_keys,
+                                           const float *d_vals, const uint32_t *d_rowptr,
+                                           const int32_t *d_labels, uint32_t R, uint32_t NNZ,
+                                           void *stream) {
+  XF_REQUIRE(d_vals, "xf_batch_compile_valued_dev: null values");
+  return xf::batch_compile_dev_ex(out, d_keys, d_rowptr, d_labels, R, NNZ, (hipStream_t)stream,
+                                  false, d_vals);
 }
 
 // Bring a device-built batch's arrays to the host vectors (inspection / tests).
@@ -650,6 +686,10 @@ extern "C" int xf_batch_download(xf_batch *b) {
     XF_HIP(get(b->pidx, v.pidx, v.NNZ));
     XF_HIP(get(b->ftile_ptr, v.fwd_tile_ptr, (size_t)v.fwd_ntiles + 1));
     XF_HIP(get(b->fpanel_first, v.fwd_panel_first, (size_t)v.P + 1));
+  }
+  if (b->valued) {
+    XF_HIP(get(b->xval, b->d_xval, v.NNZ));
+    XF_HIP(get(b->coo_val, b->d_coo_val, v.NNZ));
   }
   b->on_device_only = false;
   return XF_OK;
@@ -910,6 +950,41 @@ extern "C" int xf_batch_compile_gpu(xf_batch **out, const uint64_t *rowptr, cons
   if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
   XF_HIP(hipStreamSynchronize(s));
   return xf_batch_compile_dev(out, d_keys, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ, stream);
+}
+
+// host-array front end of xf_batch_compile_valued_dev
+extern "C" int xf_batch_compile_valued_gpu(xf_batch **out, const uint64_t *rowptr,
+                                           const uint64_t *keys, const float *vals,
+                                           const int32_t *labels, size_t row_begin, size_t row_end,
+                                           void *stream) {
+  XF_REQUIRE(out && rowptr && labels && row_end >= row_begin,
+             "xf_batch_compile_valued_gpu: bad argument");
+  const size_t R = row_end - row_begin;
+  const uint64_t base = rowptr[row_begin];
+  const size_t NNZ = (size_t)(rowptr[row_end] - base);
+  XF_REQUIRE(NNZ == 0 || (keys && vals), "xf_batch_compile_valued_gpu: null keys or values");
+  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile_valued_gpu: batch too large");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<uint32_t> rp(R + 1);
+  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
+  Scratch sc;
+  uint64_t *d_keys = nullptr;
+  float *d_vals = nullptr;
+  uint32_t *d_rp = nullptr;
+  int32_t *d_lab = nullptr;
+  XF_TRY(sc.get(&d_keys, NNZ));
+  XF_TRY(sc.get(&d_vals, NNZ + 1));
+  XF_TRY(sc.get(&d_rp, R + 1));
+  XF_TRY(sc.get(&d_lab, R));
+  if (NNZ) {
+    XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
+    XF_HIP(hipMemcpyAsync(d_vals, vals + base, NNZ * 4, hipMemcpyHostToDevice, s));
+  }
+  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
+  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
+  XF_HIP(hipStreamSynchronize(s));
+  return xf_batch_compile_valued_dev(out, d_keys, d_vals, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ,
+                                     stream);
 }
 
 // host-array front end of xf_batch_compile_fm_dev (the reader's block arrays and a row slice)

@@ -19,7 +19,9 @@ int main(int argc, char *argv[]) {
                  " [name=value ...]\n"
               << "LR model example: xflow_lr data/small_train data/small_test 0 100\n"
               << "FM model example: xflow_lr data/small_train data/small_test 1 100\n"
-              << "Rendle's FM (per-factor second-order term, one worker): append fm_mode=canonical\n";
+              << "Rendle's FM (per-factor second-order term, one worker): append fm_mode=canonical\n"
+              << "feature values (x = val of fgid:fid:val instead of 1; LR, or FM with "
+                 "fm_mode=canonical; one worker): append feature_values=on\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler

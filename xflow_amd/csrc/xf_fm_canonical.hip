@@ -358,6 +358,22 @@ int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_
   return XF_OK;
 }
 
+// the heavy keys' second kernel on its own (the valued kernels, xf_valued.hip, end with the same
+// step): k = 0 steps w alone (TV is not read)
+void fmc_heavy_finish(const TableDev &TW, const TableDev &TV, int k, const xf_dev_batch *b,
+                      const double *d_hpart, const uint32_t *d_rows_w, const uint32_t *d_rows_v,
+                      const float *d_wu, const float *d_vu, float *d_gw, hipStream_t s) {
+  const dim3 blk(kBlock);
+  if (TW.nz != nullptr)
+    hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_FTRL>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
+                       b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
+                       d_gw);
+  else
+    hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_SGD>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
+                       b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
+                       d_gw);
+}
+
 // gradient + both Pushes for the tables on this GPU.  rows_w / rows_v: the keys' state rows,
 // d_wu / d_vu: the rows the Pull returned (current: the step has not written them yet).  gw[U]
 // is written for every key (the capture hook); d_hpart: fmc_heavy_doubles(b, k) doubles.
@@ -401,14 +417,7 @@ int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uin
     hipLaunchKernelGGL(k_fmc_heavy_partial, dim3(b->n_heavy_chunks), blk, 0, s, b->heavy,
                        b->heavy_chunk_ptr, b->H, b->segptr, b->coo_row, d_loss, d_S, d_vu, k,
                        d_hpart);
-    if (ftrl)
-      hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_FTRL>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
-                         b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
-                         d_gw);
-    else
-      hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_SGD>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
-                         b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
-                         d_gw);
+    fmc_heavy_finish(TW, TV, k, b, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, d_gw, s);
     XF_HIP(hipGetLastError());
   }
   return XF_OK;

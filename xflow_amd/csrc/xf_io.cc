@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <exception>
 #include <mutex>
 #include <functional>
@@ -218,6 +219,7 @@ static void block_resize(BlockVec<T> &v, size_t n) {
 struct Piece {
   std::vector<uint64_t> keys, rowend;
   std::vector<int32_t> fgid, labels;
+  std::vector<float> vals;  // (feature values on)
   const char *err = nullptr;
   bool hit_nul = false;
 };
@@ -300,6 +302,9 @@ struct xf_reader {
   size_t held = 0;  // bytes at the front of buf not yet parsed (carry + fresh read)
   BlockVec<uint64_t> rowptr, keys;
   BlockVec<int32_t> fgid, labels;
+  // feature values (xf_reader_set_values): the third field of every token, beside keys
+  bool values = false, started = false;
+  BlockVec<float> vals;
   // per-thread pieces, kept between blocks: fresh 100 MB vectors per block meant page faults
   // and munmap under 64 threads every time
   std::vector<Piece> pieces;
@@ -603,8 +608,51 @@ inline uint64_t hash_fid(const char *ptr, size_t len, const char *safe_end) {
   return h;
 }
 
+// (float)atof of the third field [b, e) (feature values on).  Plain short decimals — an optional
+// '-', digits, an optional '.' and digits, at most 15 digits in all — are converted directly: the
+// digits as an integer and the power of ten are both exact doubles, so their quotient is the
+// correctly rounded value, the one atof gives.  Everything else (exponents, "nan", further
+// colons, blanks atof skips) goes through atof.  An empty field is 0.  *err: the cause of a
+// rejected field.
+const double kPow10[16] = {1e0, 1e1, 1e2,  1e3,  1e4,  1e5,  1e6,  1e7,
+                           1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15};
+inline float field_value(const char *b, const char *e, const char **err) {
+  const size_t n = (size_t)(e - b);
+  if (n == 0) return 0.0f;
+  double d;
+  {
+    const char *c = b;
+    const bool neg = *c == '-';
+    if (neg) ++c;
+    uint64_t m = 0;
+    int nd = 0, nf = 0;
+    for (; c < e && (unsigned)(*c - '0') <= 9u; ++c, ++nd) m = m * 10 + (uint64_t)(*c - '0');
+    if (c < e && *c == '.')
+      for (++c; c < e && (unsigned)(*c - '0') <= 9u; ++c, ++nd, ++nf)
+        m = m * 10 + (uint64_t)(*c - '0');
+    if (c == e && nd >= 1 && nd <= 15 && n <= 17) {
+      d = (double)m / kPow10[nf];
+      if (neg) d = -d;
+      return (float)d;  // (at most 15 digits: finite)
+    }
+  }
+  char tmp[48];
+  if (n >= sizeof(tmp)) {
+    *err = "val field too long";
+    return 0.0f;
+  }
+  memcpy(tmp, b, n);
+  tmp[n] = '\0';
+  d = atof(tmp);
+  const float f = (float)d;
+  if (!std::isfinite(f)) *err = "val is not finite";
+  return f;
+}
+
 // One contiguous run of whole lines (load_data_from_disk.cc:126-208).  `safe_end`: the end of
-// the buffer the text sits in (bytes up to there may be read, not interpreted).
+// the buffer the text sits in (bytes up to there may be read, not interpreted).  VAL: the third
+// field of every token is converted too (out->vals beside out->keys).
+template <bool VAL>
 void parse_piece(const char *p, const char *end, bool last_piece, const char *safe_end,
                  Piece *out) {
   // one reservation per piece instead of reallocating under 64 threads' malloc contention:
@@ -614,6 +662,7 @@ void parse_piece(const char *p, const char *end, bool last_piece, const char *sa
   out->fgid.reserve(bytes / 6 + 16);
   out->labels.reserve(bytes / 8 + 16);
   out->rowend.reserve(bytes / 8 + 16);
+  if (VAL) out->vals.reserve(bytes / 6 + 16);
   while (p < end) {
     if (*p == '\0') {
       out->hit_nul = true;
@@ -657,6 +706,15 @@ void parse_piece(const char *p, const char *end, bool last_piece, const char *sa
             while (q < eol && *q != ' ') ++q;
             out->fgid.push_back((int32_t)fgv);
             out->keys.push_back(hash_fid(f, (size_t)(c2f - f), safe_end));
+            if (VAL) {
+              const char *verr = nullptr;
+              out->vals.push_back(field_value(c2f + 1, q, &verr));
+              if (verr) {
+                out->labels.pop_back();
+                out->err = verr;
+                return;
+              }
+            }
             t = q + 1;
             continue;
           }
@@ -680,6 +738,7 @@ void parse_piece(const char *p, const char *end, bool last_piece, const char *sa
         }
         out->keys.push_back(out->keys.back());
         out->fgid.push_back(out->fgid.back());
+        if (VAL) out->vals.push_back(out->vals.back());
         t = te + 1;
         continue;
       }
@@ -696,12 +755,22 @@ void parse_piece(const char *p, const char *end, bool last_piece, const char *sa
       }
       out->fgid.push_back((int32_t)fg);
       out->keys.push_back(xf_hash_bytes(c1 + 1, (size_t)(c2 - (c1 + 1))));  // :151
+      if (VAL) {
+        const char *verr = nullptr;
+        out->vals.push_back(field_value(c2 + 1, te, &verr));
+        if (verr) {
+          out->labels.pop_back();
+          out->err = verr;
+          return;
+        }
+      }
       t = te + 1;
     }
     if (eol == end && last_piece) {  // this line is closed by the block terminator, not by '\n'
       if (eol > tab + 1 && eol[-1] == ' ' && out->keys.size() > row_first) {
         out->keys.push_back(out->keys.back());
         out->fgid.push_back(out->fgid.back());
+        if (VAL) out->vals.push_back(out->vals.back());
       } else if (eol == tab + 1 || (eol[-1] == ' ' && out->keys.size() == row_first)) {
         out->labels.pop_back();
         out->err = "row without tokens at the end of the block";
@@ -720,6 +789,7 @@ void parse_piece(const char *p, const char *end, bool last_piece, const char *sa
 struct xf_block {
   BlockVec<uint64_t> rowptr, keys;
   BlockVec<int32_t> fgid, labels;
+  BlockVec<float> vals;  // (a reader with feature values on)
 };
 
 extern "C" int xf_block_create(xf_block **out) {
@@ -742,10 +812,38 @@ extern "C" int xf_reader_next_into(xf_reader *r, xf_block *blk, size_t *rows_out
   blk->keys.swap(r->keys);
   blk->fgid.swap(r->fgid);
   blk->labels.swap(r->labels);
+  if (r->values) blk->vals.swap(r->vals);
   if (rowptr) *rowptr = blk->rowptr.data();
   if (keys) *keys = blk->keys.data();
   if (fgid) *fgid = blk->fgid.data();
   if (labels) *labels = blk->labels.data();
+  return XF_OK;
+}
+
+// ---- feature values: the third field of fgid:fid:val, (float)atof of its bytes, beside the keys.
+// Off by default (the reference never reads the field); switched on before the first block.  The
+// block cache holds no values: a reader over a cache refuses.
+extern "C" int xf_reader_set_values(xf_reader *r, int on) {
+  XF_REQUIRE(r, "xf_reader_set_values: null reader");
+  XF_REQUIRE(!r->started, "xf_reader_set_values: the reader has handed out a block already");
+  XF_REQUIRE(!on || (!r->cfp && !r->tfp),
+             "xf_reader_set_values: the block cache (xf_reader_open_cached) carries no feature "
+             "values: open the text with xf_reader_open");
+  r->values = on != 0;
+  return XF_OK;
+}
+
+// the values of the block xf_reader_next last returned (reader-owned, nnz entries) / of a block
+// filled by xf_reader_next_into or xf_reader_parse_text; NULL from a reader with values off
+extern "C" int xf_reader_values(xf_reader *r, const float **vals) {
+  XF_REQUIRE(r && vals, "xf_reader_values: null argument");
+  *vals = r->values ? r->vals.data() : nullptr;
+  return XF_OK;
+}
+
+extern "C" int xf_block_values(xf_block *blk, const float **vals) {
+  XF_REQUIRE(blk && vals, "xf_block_values: null argument");
+  *vals = blk->vals.data();
   return XF_OK;
 }
 
@@ -800,6 +898,8 @@ static int block_extent(xf_reader *r, const char **base_out, size_t *text_out, s
 // block is cut at newlines into one piece per thread; the pieces are concatenated in order
 // (bit-identical to a serial pass).  safe_end: bytes up to there may be READ beyond a token.
 static int parse_text(xf_reader *r, const char *base, size_t text, const char *safe_end) {
+  r->started = true;
+  r->vals.clear();
   r->rowptr.assign(1, 0);
   r->keys.clear();
   r->fgid.clear();
@@ -826,11 +926,15 @@ static int parse_text(xf_reader *r, const char *base, size_t text, const char *s
     pc.rowend.clear();
     pc.fgid.clear();
     pc.labels.clear();
+    pc.vals.clear();
     pc.err = nullptr;
     pc.hit_nul = false;
   }
+  const bool values = r->values;
   r->team.run(nt, [&](unsigned t) {
-    parse_piece(cut[t], cut[t + 1], cut[t + 1] == end, safe_end, &pieces[t]);
+    if (values) parse_piece<true>(cut[t], cut[t + 1], cut[t + 1] == end, safe_end, &pieces[t]);
+    else
+      parse_piece<false>(cut[t], cut[t + 1], cut[t + 1] == end, safe_end, &pieces[t]);
   });
   // offsets of every piece in the block's arrays, then a parallel copy
   std::vector<size_t> key_off(nt + 1, 0), row_off(nt + 1, 0);
@@ -854,12 +958,14 @@ static int parse_text(xf_reader *r, const char *base, size_t text, const char *s
   block_resize(r->fgid, nkeys);
   block_resize(r->labels, nrows);
   block_resize(r->rowptr, nrows + 1);
+  if (values) block_resize(r->vals, nkeys);
   r->rowptr[0] = 0;
   auto place = [&](unsigned t) {
     Piece &pc = pieces[t];
     if (!pc.keys.empty()) {
       memcpy(&r->keys[key_off[t]], pc.keys.data(), pc.keys.size() * sizeof(uint64_t));
       memcpy(&r->fgid[key_off[t]], pc.fgid.data(), pc.fgid.size() * sizeof(int32_t));
+      if (values) memcpy(&r->vals[key_off[t]], pc.vals.data(), pc.vals.size() * sizeof(float));
     }
     if (!pc.labels.empty())
       memcpy(&r->labels[row_off[t]], pc.labels.data(), pc.labels.size() * sizeof(int32_t));
@@ -973,6 +1079,7 @@ extern "C" int xf_reader_parse_text(xf_reader *r, const char *text, size_t len, 
   blk->keys.swap(r->keys);
   blk->fgid.swap(r->fgid);
   blk->labels.swap(r->labels);
+  if (r->values) blk->vals.swap(r->vals);
   if (rowptr) *rowptr = blk->rowptr.data();
   if (keys) *keys = blk->keys.data();
   if (fgid) *fgid = blk->fgid.data();

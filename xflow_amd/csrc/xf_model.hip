@@ -51,6 +51,18 @@ int cells_lr_grad_update(const xf_cells *c, const xf_table *t, const float *d_lo
 int gather_f32(const float *src, const uint32_t *rows, size_t n, float *dst, hipStream_t s);
 int batch_sorted_uidx(xf_batch *b, hipStream_t s);
 int batch_reference_coo(xf_batch *b, hipStream_t s);
+// feature values (xf_valued.hip)
+int val_fm_forward(const xf_dev_batch *b, const float *d_xval, int k, const float *d_wu,
+                   const float *d_vu, float *d_S, float *d_loss, float *d_pctr, hipStream_t s);
+int val_lr_forward(const xf_dev_batch *b, const float *d_xval, const float *d_wu, float *d_loss,
+                   float *d_pctr, hipStream_t s);
+int val_fm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const float *d_coo_val,
+                       const uint32_t *d_rows_w, const uint32_t *d_rows_v, const float *d_wu,
+                       const float *d_vu, const float *d_S, const float *d_loss, float *d_gw,
+                       double *d_hpart, hipStream_t s);
+int val_lr_grad_update(xf_table *tw, const xf_dev_batch *b, const float *d_coo_val,
+                       const uint32_t *d_rows_w, const float *d_wu, const float *d_loss,
+                       float *d_gw, double *d_hpart, hipStream_t s);
 // canonical FM (xf_fm_canonical.hip)
 size_t fmc_heavy_doubles(const xf_dev_batch *b, int k);
 int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_vu, float *d_S,
@@ -1896,9 +1908,14 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
   return XF_OK;
 }
 
+// feature values: the step / predict of a valued minibatch (below, with the canonical FM's)
+static int lr_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream);
+static int lr_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out);
+
 extern "C" int xf_lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream) {
   XF_REQUIRE(w && b && ws, "xf_lr_step: null argument");
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_lr_step: the w table must have dim 1");
+  if (b->valued) return lr_valued_step(w, b, ws, stream);
   return lr_step(w, b, ws, stream, nullptr);
 }
 
@@ -2123,6 +2140,18 @@ static int fmc_reserve(xf_workspace *ws, const xf_batch *b, int k) {
   return XF_OK;
 }
 
+// a valued minibatch (feature_values = on) has the exact-sums kernels of xf_valued.hip only
+static int valued_check(const xf_workspace *ws, const char *who) {
+  XF_REQUIRE(ws->parity == XF_PARITY_EXACT_SUMS,
+             "%s: a minibatch with feature values (feature_values) has no reference-order parity "
+             "mode (xf_workspace_parity): the reference never reads the values", who);
+  XF_REQUIRE(!ws->capture,
+             "%s: a minibatch with feature values (feature_values) is not stepped with "
+             "xf_workspace_capture on: its step leaves the pulled weights and the w gradients "
+             "for xf_workspace_fetch as it is", who);
+  return XF_OK;
+}
+
 static int fmc_check_batch(const xf_batch *b, const char *who) {
   XF_REQUIRE(!b->fm_keyed || b->U == 0,
              "%s: canonical FM needs a minibatch with an index of its key list; this one comes "
@@ -2138,6 +2167,7 @@ static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
                              void *stream) {
   XF_TRY(fmc_check_batch(b, "xf_fm_step"));
   XF_REQUIRE(ws->parity == XF_PARITY_EXACT_SUMS, "xf_fm_step: canonical FM with a parity mode");
+  if (b->valued) XF_TRY(valued_check(ws, "xf_fm_step"));
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, stream));
   XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
@@ -2154,13 +2184,21 @@ static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
   XF_END(kEvResolve);
   if (v.U) XF_TRY(xf_table_gather_dev(vt, rows_v, v.U, ws->fmc_vu, stream));
   XF_END(kEvGather);
-  XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr, S(stream)));
+  if (b->valued)
+    XF_TRY(xf::val_fm_forward(&v, b->d_xval, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr,
+                              S(stream)));
+  else
+    XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {
     xf::table_note_write(w);
     xf::table_note_write(vt);
-    XF_TRY(xf::fmc_grad_update(w, vt, &v, rows_w, rows_v, ws->wu, ws->fmc_vu, ws->fmc_S,
-                               ws->loss, ws->g, ws->fmc_hpart, S(stream)));
+    if (b->valued)
+      XF_TRY(xf::val_fm_grad_update(w, vt, &v, b->d_coo_val, rows_w, rows_v, ws->wu, ws->fmc_vu,
+                                    ws->fmc_S, ws->loss, ws->g, ws->fmc_hpart, S(stream)));
+    else
+      XF_TRY(xf::fmc_grad_update(w, vt, &v, rows_w, rows_v, ws->wu, ws->fmc_vu, ws->fmc_S,
+                                 ws->loss, ws->g, ws->fmc_hpart, S(stream)));
   }
   XF_END(kEvGrad);
   if (ws->rec) ws->sets[ws->cur].pending = true;
@@ -2179,10 +2217,65 @@ static int fm_canonical_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_works
   XF_TRY(xf_table_pull_dev(w, v.ukeys, v.U, ws->slots, ws->wu, nullptr));
   XF_TRY(xf_table_resolve_dev(vt, v.ukeys, v.U, ws->slots2, nullptr));
   XF_TRY(xf_table_gather_dev(vt, ws->slots2, v.U, ws->fmc_vu, nullptr));
-  XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr, nullptr));
+  if (b->valued)
+    XF_TRY(xf::val_fm_forward(&v, b->d_xval, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr,
+                              nullptr));
+  else
+    XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr, nullptr));
   if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
   XF_TRY(xf_table_check(w, nullptr));
   return xf_table_check(vt, nullptr);
+}
+
+// ---- feature values, LR (kernels in xf_valued.hip): the w half of the canonical step on a
+// valued generic minibatch — Pull of the key list (rows kept with the minibatch for its
+// replays), forward over the CSR, gradient + Push over the gradient tiles
+static int lr_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream) {
+  XF_TRY(valued_check(ws, "xf_lr_step"));
+  XF_TRY(xf_batch_upload(b, stream));
+  XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
+  XF_TRY(fmc_reserve(ws, b, 0));  // (the heavy keys' chunk sums: one column)
+  ws->rec = ws->profiling && ws->step_no++ % xf_workspace::kProfileEvery == 0;
+  if (ws->rec) XF_TRY(ws_next_set(ws));
+  const xf_dev_batch &v = b->view;
+  ws->lastU = b->U;
+  ws->lastR = b->R;
+  XF_BEGIN();
+  if (v.U) {  // :170
+    const uint64_t uid = xf::table_uid(w), ep = xf::table_epoch(w);
+    const bool fresh = !b->d_fm_rows[0] || b->fm_uid[0] != uid || b->fm_epoch[0] != ep;
+    if (!b->d_fm_rows[0])
+      XF_TRY(xf::blob_alloc((void **)&b->d_fm_rows[0], (size_t)v.U * 4, &b->fm_rows_bytes[0]));
+    if (fresh) {
+      XF_TRY(xf_table_pull_dev(w, v.ukeys, v.U, b->d_fm_rows[0], ws->wu, stream));
+      b->fm_uid[0] = uid;
+      b->fm_epoch[0] = ep;
+    } else {
+      XF_TRY(xf::gather_f32(xf::table_dev(w).w, b->d_fm_rows[0], v.U, ws->wu, S(stream)));
+    }
+  }
+  XF_END(kEvResolve);
+  XF_TRY(xf::val_lr_forward(&v, b->d_xval, ws->wu, ws->loss, nullptr, S(stream)));  // :172
+  XF_END(kEvForward);
+  if (v.U && v.R) {  // :173, :175
+    xf::table_note_write(w);
+    XF_TRY(xf::val_lr_grad_update(w, &v, b->d_coo_val, b->d_fm_rows[0], ws->wu, ws->loss, ws->g,
+                                  ws->fmc_hpart, S(stream)));
+  }
+  XF_END(kEvGrad);
+  if (ws->rec) ws->sets[ws->cur].pending = true;
+  return XF_OK;
+}
+
+static int lr_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out) {
+  XF_TRY(valued_check(ws, "xf_lr_predict"));
+  XF_TRY(xf_batch_upload(b, nullptr));
+  XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
+  const xf_dev_batch &v = b->view;
+  XF_TRY(xf_table_pull_dev(w, v.ukeys, v.U, ws->slots, ws->wu, nullptr));
+  XF_TRY(xf::val_lr_forward(&v, b->d_xval, ws->wu, ws->loss, ws->pctr, nullptr));
+  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  return xf_table_check(w, nullptr);
 }
 
 extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
@@ -2191,6 +2284,10 @@ extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_fm_step: the w table must have dim 1");
   XF_REQUIRE(!b->local, "xf_fm_step: needs a minibatch with a key list (xf_batch_compile*)");
   if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_step(w, vt, b, ws, stream);
+  XF_REQUIRE(!b->valued,
+             "xf_fm_step: a minibatch with feature values (feature_values) needs fm_mode = "
+             "canonical (xf_workspace_fm_mode): the reference form's pooled sums have no meaning "
+             "with values");
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, stream));
   XF_TRY(ws_reserve(ws, b->U, (size_t)b->U * k, b->R));
@@ -2446,6 +2543,7 @@ int fm_owner_push_pulled(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *w
 extern "C" int xf_lr_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out) {
   XF_REQUIRE(w && b && ws && pctr_out, "xf_lr_predict: null argument");
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_lr_predict: the w table must have dim 1");
+  if (b->valued) return lr_valued_predict(w, b, ws, pctr_out);
   XF_TRY(xf::ensure_cells(b, w, nullptr));
   XF_TRY(ws_reserve(ws, b->U, 0, b->R));
   XF_TRY(ws_reserve_cells(ws, b->cells, false));
@@ -2464,6 +2562,9 @@ extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
   XF_REQUIRE(w && vt && b && ws && pctr_out, "xf_fm_predict: null argument");
   XF_REQUIRE(!b->local, "xf_fm_predict: needs a minibatch with a key list (xf_batch_compile*)");
   if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_predict(w, vt, b, ws, pctr_out);
+  XF_REQUIRE(!b->valued,
+             "xf_fm_predict: a minibatch with feature values (feature_values) needs fm_mode = "
+             "canonical (xf_workspace_fm_mode)");
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, nullptr));
   XF_TRY(ws_reserve(ws, b->U, (size_t)b->U * k, b->R));

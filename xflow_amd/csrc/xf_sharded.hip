@@ -1532,6 +1532,73 @@ extern "C" int xf_sharded_compile(xf_sharded *st, xf_sbatch **out, const uint64_
   return XF_OK;
 }
 
+// Feature values: a valued minibatch always takes the generic build, and steps on one rank only
+static int valued_trainer_check(const xf_sharded *st, const char *who) {
+  XF_REQUIRE(st->world == 1 && st->fused && st->ws,
+             "%s: feature values (feature_values) run on one worker only (world %d)", who,
+             st->world);
+  XF_REQUIRE(st->cfg.model == 0 || st->fm_mode == XF_FM_CANONICAL,
+             "%s: feature values (feature_values) with FM need fm_mode = canonical "
+             "(xf_sharded_set_fm_mode)", who);
+  XF_REQUIRE(st->parity_mode == XF_PARITY_EXACT_SUMS,
+             "%s: feature values (feature_values) have no reference-order parity mode", who);
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
+                                         const uint64_t *keys, const float *vals,
+                                         const int32_t *labels, size_t row_begin, size_t row_end,
+                                         int keep) {
+  (void)keep;  // (the generic minibatch is replayable as it is)
+  XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
+             "xf_sharded_compile_valued: bad argument");
+  XF_ALIVE(st);
+  XF_TRY(valued_trainer_check(st, "xf_sharded_compile_valued"));
+  xf_sbatch *b = new xf_sbatch;
+  struct Guard {
+    xf_sbatch *b;
+    ~Guard() {
+      if (b) xf_sbatch_free(b);
+    }
+  } guard{b};
+  b->owner = st;
+  if (st->cfg.host_key_build)
+    XF_TRY(xf_batch_compile_valued(&b->b, rowptr, keys, vals, labels, row_begin, row_end));
+  else
+    XF_TRY(xf_batch_compile_valued_gpu(&b->b, rowptr, keys, vals, labels, row_begin, row_end,
+                                       st->main));
+  XF_TRY(fused_room(st, b));
+  guard.b = nullptr;
+  *out = b;
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out,
+                                             const uint64_t *d_keys, const float *d_vals,
+                                             const uint32_t *d_rowptr, const int32_t *d_labels,
+                                             uint32_t R, uint32_t NNZ, int keep) {
+  (void)keep;
+  XF_REQUIRE(st && out && d_rowptr && d_vals && (R == 0 || d_labels) && (NNZ == 0 || d_keys),
+             "xf_sharded_compile_valued_dev: null argument");
+  XF_ALIVE(st);
+  XF_TRY(valued_trainer_check(st, "xf_sharded_compile_valued_dev"));
+  XF_REQUIRE(!st->cfg.host_key_build, "xf_sharded_compile_valued_dev: the trainer builds its keys "
+             "on the host (host_key_build): hand it host arrays");
+  xf_sbatch *b = new xf_sbatch;
+  struct Guard {
+    xf_sbatch *b;
+    ~Guard() {
+      if (b) xf_sbatch_free(b);
+    }
+  } guard{b};
+  b->owner = st;
+  XF_TRY(xf_batch_compile_valued_dev(&b->b, d_keys, d_vals, d_rowptr, d_labels, R, NNZ, st->main));
+  XF_TRY(fused_room(st, b));
+  guard.b = nullptr;
+  *out = b;
+  return XF_OK;
+}
+
 // The same from device-resident arrays (raw keys in CSR order, 32-bit row offsets, labels): what
 // a reader that parses straight into HBM, or a caller that keeps its blocks there, hands over.
 // The arrays may be released when this returns.  COLLECTIVE.

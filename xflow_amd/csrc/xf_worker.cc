@@ -115,8 +115,11 @@ int Worker::create_tables() {
     const int32_t lab[2] = {0, 1};
     float p[2];
     xf_sbatch *b = nullptr;
+    const float vals[4] = {1.0f, 0.5f, 0.25f, 2.0f};
     int rc = fm_mode != XF_FM_REFERENCE ? xf_sharded_set_fm_mode(warm, fm_mode) : XF_OK;
-    if (rc == XF_OK) rc = xf_sharded_compile(warm, &b, rp, keys, lab, 0, 2, 1);
+    if (rc == XF_OK)
+      rc = feature_values ? xf_sharded_compile_valued(warm, &b, rp, keys, vals, lab, 0, 2, 1)
+                          : xf_sharded_compile(warm, &b, rp, keys, lab, 0, 2, 1);
     if (rc == XF_OK) rc = xf_sharded_step(warm, b);
     if (rc == XF_OK) rc = xf_sharded_predict(warm, b, p);
     if (b) xf_sbatch_free(b);
@@ -258,6 +261,10 @@ int Worker::batch_training() {
       const double te0 = now_s();
       bool writes_cache = false;
       XF_TRY(open_reader(&rd, train_data_path, (size_t)block_size << 20, &writes_cache));
+      if (feature_values && xf_reader_set_values(rd, 1) != XF_OK) {
+        xf_reader_close(rd);
+        return XF_EINVAL;
+      }
       if (trace) fprintf(stderr, "epoch %d: reader open %.2f ms\n", epoch, (now_s() - te0) * 1e3);
       // The text of block i+1 is parsed on a second host thread while the GPU builds the keys
       // of block i and trains on it: two caller-owned blocks go round between the two threads.
@@ -266,6 +273,7 @@ int Worker::batch_training() {
         size_t rows = 0, nnz = 0;
         const uint64_t *rowptr = nullptr, *keys = nullptr;
         const int32_t *labels = nullptr;
+        const float *vals = nullptr;  // (feature_values)
         int rc = XF_OK;
         std::string err;
       };
@@ -299,6 +307,7 @@ int Worker::batch_training() {
           const int32_t *fgid = nullptr;
           p.rc = xf_reader_next_into(rd, p.blk, &p.rows, &p.nnz, &p.rowptr, &p.keys, &fgid,
                                      &p.labels);
+          if (p.rc == XF_OK && feature_values) p.rc = xf_block_values(p.blk, &p.vals);
           if (p.rc != XF_OK) p.err = xf_last_error();  // the message is thread-local
           const bool last = p.rc != XF_OK || p.rows == 0;
           {
@@ -339,10 +348,14 @@ int Worker::batch_training() {
           xf_sbatch *b = nullptr;
           const double tc0 = now_s();
           // a rank without rows of its own still takes part in the (collective) step
-          rc = end > start ? xf_sharded_compile(sharded_, &b, p->rowptr, p->keys, p->labels,
-                                                start, end, keep)
-                           : xf_sharded_compile(sharded_, &b, kNoRows, nullptr,
-                                                (const int32_t *)kNoRows, 0, 0, keep);
+          if (feature_values)  // (one worker: a block without rows ended the loop above)
+            rc = xf_sharded_compile_valued(sharded_, &b, p->rowptr, p->keys, p->vals, p->labels,
+                                           start, end, keep);
+          else if (end > start)
+            rc = xf_sharded_compile(sharded_, &b, p->rowptr, p->keys, p->labels, start, end, keep);
+          else
+            rc = xf_sharded_compile(sharded_, &b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0,
+                                    keep);
           if (rc != XF_OK) break;
           const double tc1 = now_s();
           rc = xf_sharded_step(sharded_, b);
@@ -604,6 +617,10 @@ int Worker::predict(int rank, int block, bool reader) {
     // 4 MiB blocks for LR (lr_worker.cc:80), 2 MiB for FM (fm_worker.cc:106)
     const size_t cap = model_ == 0 ? ((size_t)4 << 20) : ((size_t)2 << 20);
     XF_TRY(open_reader(&rd, test_data_path, cap));
+    if (feature_values && xf_reader_set_values(rd, 1) != XF_OK) {
+      xf_reader_close(rd);
+      return XF_EINVAL;
+    }
   }
   struct ReaderGuard {  // every return path closes the reader
     xf_reader *r;
@@ -619,8 +636,10 @@ int Worker::predict(int rank, int block, bool reader) {
     size_t rows = 0, nnz = 0;
     const uint64_t *rowptr = nullptr, *keys = nullptr;
     const int32_t *fgid = nullptr, *labels = nullptr;
+    const float *vals = nullptr;
     if (!mine_done) {
       XF_TRY(xf_reader_next(rd, &rows, &nnz, &rowptr, &keys, &fgid, &labels));
+      if (feature_values) XF_TRY(xf_reader_values(rd, &vals));
       if (rows == 0) mine_done = true;
     }
     bool any = false;
@@ -631,7 +650,9 @@ int Worker::predict(int rank, int block, bool reader) {
       const size_t start = i * thread_size, end = (i + 1) * thread_size;
       if (end == start && world <= 1) continue;
       xf_sbatch *b = nullptr;
-      if (end > start) XF_TRY(xf_sharded_compile(sharded_, &b, rowptr, keys, labels, start, end, 0));
+      if (feature_values)
+        XF_TRY(xf_sharded_compile_valued(sharded_, &b, rowptr, keys, vals, labels, start, end, 0));
+      else if (end > start) XF_TRY(xf_sharded_compile(sharded_, &b, rowptr, keys, labels, start, end, 0));
       else
         XF_TRY(xf_sharded_compile(sharded_, &b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0,
                                   0));
@@ -675,6 +696,23 @@ int Worker::train() {
     XF_REQUIRE(w <= 1, "XFStartTrain: fm_mode=canonical runs on one worker only (world %d)", w);
     XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS,
                "XFStartTrain: fm_mode=canonical has no parity=reference_order mode");
+  }
+  if (feature_values && !sharded_) {  // next to the canonical mode's: before any rendezvous
+    XF_REQUIRE(model_ == 0 || fm_mode == XF_FM_CANONICAL,
+               "XFStartTrain: feature_values=on with model 1 (FM) needs fm_mode=canonical (the "
+               "reference form's pooled sums have no meaning with values)");
+    int w = world;
+    if (w <= 0) {
+      const char *v = env_first({"WORLD_SIZE", "XF_WORLD", "DMLC_NUM_WORKER"});
+      w = v ? atoi(v) : 1;
+    }
+    XF_REQUIRE(w <= 1, "XFStartTrain: feature_values=on runs on one worker only (world %d)", w);
+    XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS,
+               "XFStartTrain: feature_values=on has no parity=reference_order mode");
+    XF_REQUIRE(!block_cache, "XFStartTrain: feature_values=on together with block_cache=1: the "
+               "block cache carries no values");
+    XF_REQUIRE(!ingest_gpu, "XFStartTrain: feature_values=on together with ingest=gpu: the GPU "
+               "tokeniser carries no values");
   }
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
@@ -780,6 +818,13 @@ int Worker::set_param(const char *name, const char *value) {
     else if (!strcmp(value, "canonical")) fm_mode = XF_FM_CANONICAL;
     else
       return xf::set_error(XF_EINVAL, "XFSetParam: fm_mode must be reference or canonical");
+  } else if (n == "feature_values") {
+    XF_REQUIRE(!sharded_, "XFSetParam: feature_values cannot change after training started");
+    if (!strcmp(value, "on")) feature_values = true;
+    else if (!strcmp(value, "off")) feature_values = false;
+    else
+      return xf::set_error(XF_EINVAL, "XFSetParam: feature_values must be on or off, not '%s'",
+                           value);
   } else if (n == "key_build") {
     if (!strcmp(value, "gpu")) key_build_gpu = true;
     else if (!strcmp(value, "host")) key_build_gpu = false;

@@ -50,6 +50,7 @@ class Worker {
   bool key_build_gpu = true;  // key build of update() on the GPU (xf_batch_compile_gpu)
   int parity = 0;             // XF_PARITY_*: the forward's row sums (one worker)
   int fm_mode = 0;            // XF_FM_*: FM's second-order term (canonical: one worker)
+  bool feature_values = false;  // a nonzero contributes x = val, not 1 (one worker)
   int update_rule = 0;        // XF_UPDATE_*: how an owner applies the workers' pushes of a step
   std::string pred_path;
   std::string model_in, model_out;  // load before / save after training (model file)

@@ -6,11 +6,16 @@ class SingleGpuTrainer:
     """One shard, one GPU: LRWorker::update / FMWorker::update on device-resident batches."""
 
     def __init__(self, model="lr", optimizer="ftrl", k=10, capacity=1 << 22, seed=7,
-                 rank=0, world=1, fm_mode="reference", **hyper):
+                 rank=0, world=1, fm_mode="reference", feature_values=False, **hyper):
         """fm_mode (FM): "reference" (the reference's pooled second-order term) or "canonical"
-        (Rendle's per-factor form; the v table starts hash-normal for both optimizers)"""
+        (Rendle's per-factor form; the v table starts hash-normal for both optimizers).
+        feature_values: a nonzero contributes x = val instead of 1 (compile(..., values=...));
+        LR, or FM with fm_mode="canonical"."""
         assert world == 1
         assert fm_mode in capi.FM_MODES, fm_mode
+        assert not feature_values or model == "lr" or fm_mode == "canonical", \
+            "feature_values with FM needs fm_mode='canonical'"
+        self.feature_values = bool(feature_values)
         opt = capi.OPT_FTRL if optimizer == "ftrl" else capi.OPT_SGD
         self.model = model
         self.fm_mode = fm_mode if model == "fm" else "reference"
@@ -24,7 +29,11 @@ class SingleGpuTrainer:
         if self.fm_mode != "reference":
             self.ws.fm_mode(self.fm_mode)
 
-    def compile(self, rowptr, keys, labels):
+    def compile(self, rowptr, keys, labels, values=None):
+        if self.feature_values:  # a valued minibatch always takes the generic build
+            assert values is not None, "feature_values=True: compile(..., values=...)"
+            return capi.Batch(rowptr, keys, labels, on_gpu=True, values=values)
+        assert values is None, "values need SingleGpuTrainer(feature_values=True)"
         if self.model == "lr":   # sort-free key build against the table (cells)
             return capi.LocalBatch(self.w, rowptr, keys, labels)
         return capi.Batch(rowptr, keys, labels).upload()
