@@ -180,6 +180,28 @@ __device__ __forceinline__ float sgd_step(float lr, float g, float w) {
   return w - lr * g;
 }
 
+// The optimizer step of one table coordinate in place (OPT: XF_OPT_*): offset o into T.w / T.nz,
+// its current weight w_old (the pulled value), its gradient g.  The second form takes the (n, z)
+// of an FTRL coordinate from a caller that requested them ahead of the sum that gives g.
+template <int OPT>
+__device__ __forceinline__ void step_coord(const TableDev &T, size_t o, float w_old, float g,
+                                           float n, float z) {
+  if (OPT == XF_OPT_FTRL) {
+    float w = w_old;
+    ftrl_step(T.alpha, T.inv_alpha, T.beta, T.lambda1, T.lambda2, g, w, n, z);
+    T.w[o] = w;
+    store_nz(T, o, n, z);
+  } else {
+    T.w[o] = sgd_step(T.lr, g, w_old);
+  }
+}
+template <int OPT>
+__device__ __forceinline__ void step_coord(const TableDev &T, size_t o, float w_old, float g) {
+  float n = 0.0f, z = 0.0f;
+  if (OPT == XF_OPT_FTRL) load_nz(T, o, n, z);
+  step_coord<OPT>(T, o, w_old, g, n, z);
+}
+
 // x / R exactly as the reference computes it — `float /= 1.0 * line_num`, i.e. the fp32 value
 // divided in double and rounded back to fp32 (lr_worker.cc:117, fm_worker.cc:150-156) — at the
 // price of an fp32 division: for x an fp32 number and R an integer below 2^24 the exact

@@ -1,14 +1,21 @@
 // xf_fm_canonical.hip — canonical factorization machine (fm_mode = canonical, gfx950).
 //
-// Rendle's second-order term with per-factor sums and the 1/2:
-//   S[r,f] = sum_j v[u_j,f]                 (R x k, kept for the gradient)
-//   y2_r   = 0.5 * (sum_f S[r,f]^2 - sum_f sum_j v[u_j,f]^2) = sum_{i<j} <v_i, v_j>
-//   gw[u]   = (sum_occ loss) / R
-//   gv[u,f] = (sum_occ loss * (S[sid,f] - v[u,f])) / R
+// Rendle's second-order term with per-factor sums and the 1/2, a nonzero contributing x (its
+// value with feature_values = on, else 1); fp32(.) marks every rounding to fp32:
+//   wx_r    = fp32(sum_j fp32(w[u_j] x_j))          gw[u] = fp32(fp32(sum_occ fp32(loss_r x_occ)) / R)
+//   a_jf    = fp32(v[u_j,f] x_j)                    S[r,f] = fp32(sum_j a_jf)   (R x k, kept for the gradient)
+//   y2_r    = fp32(0.5 (sum_f fp32(S[r,f]^2) - sum_f sum_j fp32(a_jf^2))) = sum_{i<j} <a_i, a_j>
+//   gv[u,f] = fp32(fp32(sum_occ fp32(fp32(loss_r x_occ) fp32(S[r,f] - a_occ,f))) / R)
 // The reference form (xf_model.hip, fm_worker.cc:159-202) pools its sums over all k factors,
 // which collapses the k factors into one scalar per key; this form does not.  Every fp64 sum
 // adds fp32 values (products are rounded to fp32 first), so it is exact and the result does
-// not depend on lane assignment or order.
+// not depend on lane assignment or order.  With x = 1 every product with x is exact: that gives
+// the binary form exactly, bit for bit.
+//
+// One set of kernels, VAL their last template parameter.  VAL = true streams the values with the
+// index they belong to (xval beside uidx in CSR order, coo_val beside coo_row grouped by key:
+// coalesced, never gathered); VAL = false is the binary form with x folded away at compile time —
+// no value load, no value staging, the value pointer (the last kernel argument) unread.
 //
 // Forward: one wavefront per row.  A lane is a (nonzero slot, factor) pair — P factors, 64 / P
 // slots, four nonzeros in flight per lane; the per-factor fp64 sums are joined across the slots
@@ -24,6 +31,7 @@
 
 #include "xf_common.h"
 #include "xf_device.h"
+#include "xf_fm_canonical.h"
 #include "xf_wave.h"
 
 namespace xf {
@@ -38,13 +46,16 @@ using xf::group_sum;
 using xf::heavy_of_chunk;
 
 // ------------------------------------------------------------------------------ forward
-// P: factors per pass (a power of two <= 64); EXACT: k == P (a compile-time factor count)
-template <int P, bool EXACT>
+// P: factors per pass (a power of two <= 64); EXACT: k == P (a compile-time factor count).
+// VAL: a = v x in place of v and w x in place of w, a lane's value loads at the addresses of its
+// index loads
+template <int P, bool EXACT, bool VAL>
 __global__ void __launch_bounds__(kBlock)
 k_fmc_forward(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ uidx,
               const float *__restrict__ wu, const float *__restrict__ vu, int k_rt,
               const int32_t *__restrict__ labels, uint32_t R, float *__restrict__ loss,
-              float *__restrict__ pctr, float *__restrict__ S) {
+              float *__restrict__ pctr, float *__restrict__ S,
+              const float *__restrict__ xval) {
 #pragma clang fp contract(off)
   static_assert(P >= 1 && P <= 64 && (P & (P - 1)) == 0, "P: a power of two <= 64");
   const uint32_t k = EXACT ? (uint32_t)P : (uint32_t)k_rt;
@@ -60,9 +71,13 @@ k_fmc_forward(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ 
       double s = 0.0;
       for (uint32_t j0 = sub; j0 < n; j0 += 4 * kG) {
         uint32_t ui[4];
-        float vv[4], ww[4];
+        float xv[4], vv[4], ww[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) ui[i] = j0 + i * kG < n ? uidx[b + j0 + i * kG] : 0xFFFFFFFFu;
+        for (int i = 0; i < 4; ++i) {
+          const bool in = j0 + i * kG < n;
+          ui[i] = in ? uidx[b + j0 + i * kG] : 0xFFFFFFFFu;
+          xv[i] = (VAL && in) ? xval[b + j0 + i * kG] : 0.0f;
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           vv[i] = (on && ui[i] != 0xFFFFFFFFu) ? vu[(size_t)ui[i] * k + fk] : 0.0f;
@@ -70,9 +85,10 @@ k_fmc_forward(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ 
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          s += (double)vv[i];
-          q += (double)(vv[i] * vv[i]);  // fp32 product
-          wx += (double)ww[i];
+          const float a = VAL ? vv[i] * xv[i] : vv[i];  // fp32 products, here and below
+          s += (double)a;
+          q += (double)(a * a);
+          wx += (double)(VAL ? ww[i] * xv[i] : ww[i]);
         }
       }
 #pragma unroll
@@ -102,7 +118,9 @@ k_fmc_forward(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ 
 // occurrence are read by neighbouring lanes from one contiguous k x 4-byte row — and applies
 // the optimizer step to that coordinate of the key's v row (the pulled value is the current
 // weight: nothing touched the row since the Pull).  One lane per key does the same for w.
-template <int OPT, int K /* compile-time factor count, 0 = k_rt */>
+// VAL: the occurrences' values staged beside their rows — lx = loss x (what the w gradient sums),
+// xs = x (for a = v x); binary: lx is the plain loss and xs is not there.
+template <int OPT, int K /* compile-time factor count, 0 = k_rt */, bool VAL>
 __global__ void __launch_bounds__(kBlock)
 k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ tile_ptr,
                  uint32_t ntiles, const uint32_t *__restrict__ segptr,
@@ -110,9 +128,10 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
                  const float *__restrict__ S, const float *__restrict__ wu,
                  const float *__restrict__ vu, const uint32_t *__restrict__ rows_w,
                  const uint32_t *__restrict__ rows_v, uint32_t R, int k_rt,
-                 float *__restrict__ gw) {
+                 float *__restrict__ gw, const float *__restrict__ coo_val) {
 #pragma clang fp contract(off)
-  __shared__ float lv[XF_GRAD_TILE_NNZ];
+  __shared__ float lx[XF_GRAD_TILE_NNZ];
+  __shared__ float xs[VAL ? XF_GRAD_TILE_NNZ : 1];
   __shared__ uint32_t ss[XF_GRAD_TILE_NNZ];
   __shared__ uint32_t sp[XF_GRAD_TILE_KEYS + 1];
   const uint32_t k = K > 0 ? (uint32_t)K : (uint32_t)k_rt;
@@ -124,8 +143,10 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
     for (uint32_t q = tid; q <= nk; q += kBlock) sp[q] = segptr[ua + q] - j0;
     for (uint32_t j = j0 + tid; j < j1; j += kBlock) {
       const uint32_t sid = coo_row[j];
+      const float x = VAL ? coo_val[j] : 1.0f;
       ss[j - j0] = sid;
-      lv[j - j0] = loss[sid];
+      if constexpr (VAL) xs[j - j0] = x;
+      lx[j - j0] = VAL ? loss[sid] * x : loss[sid];
     }
     __syncthreads();
     const uint32_t nel = nk * k;
@@ -165,36 +186,23 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
 #pragma unroll
           for (int m = 0; m < 4; ++m) sv[m] = S[(size_t)ss[j + m] * k + kk[i]];
 #pragma unroll
-          for (int m = 0; m < 4; ++m) acc += (double)(lv[j + m] * (sv[m] - v[i]));
+          for (int m = 0; m < 4; ++m)
+            acc += (double)(lx[j + m] * (sv[m] - (VAL ? v[i] * xs[j + m] : v[i])));
         }
-        for (; j < e; ++j) acc += (double)(lv[j] * (S[(size_t)ss[j] * k + kk[i]] - v[i]));
+        for (; j < e; ++j)
+          acc += (double)(lx[j] * (S[(size_t)ss[j] * k + kk[i]] - (VAL ? v[i] * xs[j] : v[i])));
         const float g = xf::div_by_rows((float)acc, R);
-        if (OPT == XF_OPT_FTRL) {
-          float w = v[i], nn = vn[i], z = vz[i];
-          xf::ftrl_step(TV.alpha, TV.inv_alpha, TV.beta, TV.lambda1, TV.lambda2, g, w, nn, z);
-          TV.w[to[i]] = w;
-          xf::store_nz(TV, to[i], nn, z);
-        } else {
-          TV.w[to[i]] = xf::sgd_step(TV.lr, g, v[i]);
-        }
+        constexpr bool kNZ = OPT == XF_OPT_FTRL;  // (vn, vz: requested above, FTRL only)
+        xf::step_coord<OPT>(TV, to[i], v[i], g, kNZ ? vn[i] : 0.0f, kNZ ? vz[i] : 0.0f);
       }
     }
     // the keys' w: the true gradient (sum of the occurrences' losses) / R, one lane per key
     for (uint32_t q = tid; q < nk; q += kBlock) {
       double aw = 0.0;
-      for (uint32_t j = sp[q]; j < sp[q + 1]; ++j) aw += (double)lv[j];
+      for (uint32_t j = sp[q]; j < sp[q + 1]; ++j) aw += (double)lx[j];
       const float g1 = xf::div_by_rows((float)aw, R);
       gw[ua + q] = g1;
-      const uint32_t rw = rows_w[ua + q];
-      if (OPT == XF_OPT_FTRL) {
-        float w = wu[ua + q], nn, z;
-        xf::load_nz(TW, rw, nn, z);
-        xf::ftrl_step(TW.alpha, TW.inv_alpha, TW.beta, TW.lambda1, TW.lambda2, g1, w, nn, z);
-        TW.w[rw] = w;
-        xf::store_nz(TW, rw, nn, z);
-      } else {
-        TW.w[rw] = xf::sgd_step(TW.lr, g1, wu[ua + q]);
-      }
+      xf::step_coord<OPT>(TW, rows_w[ua + q], wu[ua + q], g1);
     }
     __syncthreads();
   }
@@ -204,15 +212,18 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
 // A heavy key's occurrences in chunks of XF_TILE_NNZ (the batch's heavy_chunk_ptr), one
 // workgroup per chunk: partial[chunk][col] for the k factor columns and the loss sum (column k).
 // A thread is (slice of the chunk's occurrences, column); columns beyond one workgroup's width
-// (k >= 256) take further passes.
+// (k >= 256) take further passes.  VAL: the chunk's values staged as in k_fmc_grad_tiled.  k = 0
+// (LR, xf_valued.hip) leaves the loss column alone: S and vu are not read.
+template <bool VAL>
 __global__ void __launch_bounds__(kBlock)
 k_fmc_heavy_partial(const uint32_t *__restrict__ heavy, const uint32_t *__restrict__ hch,
                     uint32_t H, const uint32_t *__restrict__ segptr,
                     const uint32_t *__restrict__ coo_row, const float *__restrict__ loss,
                     const float *__restrict__ S, const float *__restrict__ vu, int k_rt,
-                    double *__restrict__ partial) {
+                    double *__restrict__ partial, const float *__restrict__ coo_val) {
 #pragma clang fp contract(off)
-  __shared__ float lv[XF_TILE_NNZ];
+  __shared__ float lx[XF_TILE_NNZ];
+  __shared__ float xs[VAL ? XF_TILE_NNZ : 1];
   __shared__ uint32_t ss[XF_TILE_NNZ];
   __shared__ double red[kBlock];
   const uint32_t tid = threadIdx.x, c = blockIdx.x, k = (uint32_t)k_rt;
@@ -223,8 +234,10 @@ k_fmc_heavy_partial(const uint32_t *__restrict__ heavy, const uint32_t *__restri
   const uint32_t n = e > b ? e - b : 0u;
   for (uint32_t j = tid; j < n; j += kBlock) {
     const uint32_t sid = coo_row[b + j];
+    const float x = VAL ? coo_val[b + j] : 1.0f;
     ss[j] = sid;
-    lv[j] = loss[sid];
+    if constexpr (VAL) xs[j] = x;
+    lx[j] = VAL ? loss[sid] * x : loss[sid];
   }
   __syncthreads();
   const uint32_t ncol = k + 1u, cpp = min(ncol, (uint32_t)kBlock), nsl = kBlock / cpp;
@@ -245,12 +258,14 @@ k_fmc_heavy_partial(const uint32_t *__restrict__ heavy, const uint32_t *__restri
 #pragma unroll
           for (int m = 0; m < 8; ++m) sv[m] = S[(size_t)ss[j + m * nsl] * k + col];
 #pragma unroll
-          for (int m = 0; m < 8; ++m) a[m] += (double)(lv[j + m * nsl] * (sv[m] - v));
+          for (int m = 0; m < 8; ++m)
+            a[m] += (double)(lx[j + m * nsl] * (sv[m] - (VAL ? v * xs[j + m * nsl] : v)));
         }
-        for (; j < n; j += nsl) a[0] += (double)(lv[j] * (S[(size_t)ss[j] * k + col] - v));
+        for (; j < n; j += nsl)
+          a[0] += (double)(lx[j] * (S[(size_t)ss[j] * k + col] - (VAL ? v * xs[j] : v)));
         acc = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
       } else {
-        for (uint32_t j = sl; j < n; j += nsl) acc += (double)lv[j];
+        for (uint32_t j = sl; j < n; j += nsl) acc += (double)lx[j];
       }
     }
     red[tid] = acc;
@@ -289,30 +304,10 @@ k_fmc_heavy_finish(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict_
       for (uint32_t q = 1; q < nsl; ++q) acc += red[q * cpp + cl];
       const float g = xf::div_by_rows((float)acc, R);
       if (col < k) {
-        const size_t o = (size_t)rows_v[u] * k + col;
-        float w = vu[(size_t)u * k + col];
-        if (OPT == XF_OPT_FTRL) {
-          float nn, z;
-          xf::load_nz(TV, o, nn, z);
-          xf::ftrl_step(TV.alpha, TV.inv_alpha, TV.beta, TV.lambda1, TV.lambda2, g, w, nn, z);
-          TV.w[o] = w;
-          xf::store_nz(TV, o, nn, z);
-        } else {
-          TV.w[o] = xf::sgd_step(TV.lr, g, w);
-        }
+        xf::step_coord<OPT>(TV, (size_t)rows_v[u] * k + col, vu[(size_t)u * k + col], g);
       } else {
         gw[u] = g;
-        const uint32_t rw = rows_w[u];
-        float w = wu[u];
-        if (OPT == XF_OPT_FTRL) {
-          float nn, z;
-          xf::load_nz(TW, rw, nn, z);
-          xf::ftrl_step(TW.alpha, TW.inv_alpha, TW.beta, TW.lambda1, TW.lambda2, g, w, nn, z);
-          TW.w[rw] = w;
-          xf::store_nz(TW, rw, nn, z);
-        } else {
-          TW.w[rw] = xf::sgd_step(TW.lr, g, w);
-        }
+        xf::step_coord<OPT>(TW, rows_w[u], wu[u], g);
       }
     }
     __syncthreads();
@@ -328,15 +323,21 @@ size_t fmc_heavy_doubles(const xf_dev_batch *b, int k) {
   return b->H ? (size_t)b->n_heavy_chunks * ((size_t)k + 1) : 0;
 }
 
-// loss[R], pctr[R] (may be null), S[R x k] from the pulled rows w_u[U], v_u[U x k]
+// loss[R], pctr[R] (may be null), S[R x k] from the pulled rows w_u[U], v_u[U x k].  d_xval: the
+// values in CSR order, null for a binary minibatch (the caller holds a valued one to its array).
 int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_vu, float *d_S,
-                float *d_loss, float *d_pctr, hipStream_t s) {
+                float *d_loss, float *d_pctr, const float *d_xval, hipStream_t s) {
   XF_REQUIRE(b && d_wu && d_vu && d_S && d_loss && k >= 1, "fm canonical forward: bad argument");
   if (b->R == 0) return XF_OK;
   const dim3 g(blocks_for_groups(b->R, kBlock / 64)), blk(kBlock);
-#define XF_FMC_FWD(PP, EX)                                                                     \
-  hipLaunchKernelGGL((k_fmc_forward<PP, EX>), g, blk, 0, s, b->rowptr, b->uidx, d_wu, d_vu, k, \
-                     b->labels, b->R, d_loss, d_pctr, d_S)
+#define XF_FMC_FWD_V(PP, EX, VAL)                                                                  \
+  hipLaunchKernelGGL((k_fmc_forward<PP, EX, VAL>), g, blk, 0, s, b->rowptr, b->uidx, d_wu, d_vu, k, \
+                     b->labels, b->R, d_loss, d_pctr, d_S, d_xval)
+#define XF_FMC_FWD(PP, EX)                  \
+  do {                                      \
+    if (d_xval) XF_FMC_FWD_V(PP, EX, true); \
+    else XF_FMC_FWD_V(PP, EX, false);       \
+  } while (0)
   switch (k) {
     case 4: XF_FMC_FWD(4, true); break;
     case 8: XF_FMC_FWD(8, true); break;
@@ -354,33 +355,41 @@ int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_
       break;
   }
 #undef XF_FMC_FWD
+#undef XF_FMC_FWD_V
   XF_HIP(hipGetLastError());
   return XF_OK;
 }
 
-// the heavy keys' second kernel on its own (the valued kernels, xf_valued.hip, end with the same
-// step): k = 0 steps w alone (TV is not read)
-void fmc_heavy_finish(const TableDev &TW, const TableDev &TV, int k, const xf_dev_batch *b,
-                      const double *d_hpart, const uint32_t *d_rows_w, const uint32_t *d_rows_v,
-                      const float *d_wu, const float *d_vu, float *d_gw, hipStream_t s) {
-  const dim3 blk(kBlock);
-  if (TW.nz != nullptr)
-    hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_FTRL>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
-                       b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
-                       d_gw);
-  else
-    hipLaunchKernelGGL(k_fmc_heavy_finish<XF_OPT_SGD>, dim3(b->H), blk, 0, s, TW, TV, b->heavy,
-                       b->heavy_chunk_ptr, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k,
-                       d_gw);
+// the heavy keys' two kernels: the chunk sums, then a key's chunks added and its k + 1 coordinates
+// stepped.  k = 0 steps w alone (valued LR, xf_valued.hip: d_S, d_vu, d_rows_v and TV are not
+// read).  d_coo_val: null for a binary minibatch.  d_hpart: fmc_heavy_doubles(b, k) doubles.
+void fmc_heavy_update(const TableDev &TW, const TableDev &TV, int k, const xf_dev_batch *b,
+                      const uint32_t *d_rows_w, const uint32_t *d_rows_v, const float *d_wu,
+                      const float *d_vu, const float *d_S, const float *d_loss, float *d_gw,
+                      double *d_hpart, const float *d_coo_val, hipStream_t s) {
+  const dim3 gp(b->n_heavy_chunks), gf(b->H), blk(kBlock);
+#define XF_FMC_HP(VAL)                                                                         \
+  hipLaunchKernelGGL(k_fmc_heavy_partial<VAL>, gp, blk, 0, s, b->heavy, b->heavy_chunk_ptr, b->H, \
+                     b->segptr, b->coo_row, d_loss, d_S, d_vu, k, d_hpart, d_coo_val)
+#define XF_FMC_HF(OPTV)                                                                         \
+  hipLaunchKernelGGL(k_fmc_heavy_finish<OPTV>, gf, blk, 0, s, TW, TV, b->heavy, b->heavy_chunk_ptr, \
+                     d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k, d_gw)
+  if (d_coo_val) XF_FMC_HP(true);
+  else XF_FMC_HP(false);
+  if (TW.nz != nullptr) XF_FMC_HF(XF_OPT_FTRL);
+  else XF_FMC_HF(XF_OPT_SGD);
+#undef XF_FMC_HF
+#undef XF_FMC_HP
 }
 
 // gradient + both Pushes for the tables on this GPU.  rows_w / rows_v: the keys' state rows,
 // d_wu / d_vu: the rows the Pull returned (current: the step has not written them yet).  gw[U]
 // is written for every key (the capture hook); d_hpart: fmc_heavy_doubles(b, k) doubles.
+// d_coo_val: the values in key-grouped order, null for a binary minibatch.
 int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uint32_t *d_rows_w,
                     const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
                     const float *d_S, const float *d_loss, float *d_gw, double *d_hpart,
-                    hipStream_t s) {
+                    const float *d_coo_val, hipStream_t s) {
   XF_REQUIRE(tw && tv && b && d_rows_w && d_rows_v && d_wu && d_vu && d_S && d_loss && d_gw,
              "fm canonical gradient: null argument");
   if (b->U == 0) return XF_OK;
@@ -392,10 +401,15 @@ int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uin
   XF_REQUIRE(!b->H || (b->heavy_chunk_ptr && d_hpart),
              "fm canonical gradient: heavy keys without their chunks or scratch");
   const dim3 gt((unsigned)std::min<uint32_t>(b->ntiles, 1u << 16)), blk(kBlock);
-#define XF_FMC_GU(OPTV, KK)                                                                     \
-  hipLaunchKernelGGL((k_fmc_grad_tiled<OPTV, KK>), gt, blk, 0, s, TW, TV, b->tile_ptr, b->ntiles, \
-                     b->segptr, b->coo_row, d_loss, d_S, d_wu, d_vu, d_rows_w, d_rows_v, b->R, k, \
-                     d_gw)
+#define XF_FMC_GU_V(OPTV, KK, VAL)                                                               \
+  hipLaunchKernelGGL((k_fmc_grad_tiled<OPTV, KK, VAL>), gt, blk, 0, s, TW, TV, b->tile_ptr,      \
+                     b->ntiles, b->segptr, b->coo_row, d_loss, d_S, d_wu, d_vu, d_rows_w, d_rows_v, \
+                     b->R, k, d_gw, d_coo_val)
+#define XF_FMC_GU(OPTV, KK)                        \
+  do {                                             \
+    if (d_coo_val) XF_FMC_GU_V(OPTV, KK, true);    \
+    else XF_FMC_GU_V(OPTV, KK, false);             \
+  } while (0)
 #define XF_FMC_GU_K(OPTV)                 \
   switch (k) {                            \
     case 4: XF_FMC_GU(OPTV, 4); break;    \
@@ -412,12 +426,11 @@ int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uin
   }
 #undef XF_FMC_GU_K
 #undef XF_FMC_GU
+#undef XF_FMC_GU_V
   XF_HIP(hipGetLastError());
   if (b->H) {
-    hipLaunchKernelGGL(k_fmc_heavy_partial, dim3(b->n_heavy_chunks), blk, 0, s, b->heavy,
-                       b->heavy_chunk_ptr, b->H, b->segptr, b->coo_row, d_loss, d_S, d_vu, k,
-                       d_hpart);
-    fmc_heavy_finish(TW, TV, k, b, d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, d_gw, s);
+    fmc_heavy_update(TW, TV, k, b, d_rows_w, d_rows_v, d_wu, d_vu, d_S, d_loss, d_gw, d_hpart,
+                     d_coo_val, s);
     XF_HIP(hipGetLastError());
   }
   return XF_OK;

@@ -29,6 +29,7 @@
 #include "xf_cells.h"
 #include "xf_common.h"
 #include "xf_device.h"
+#include "xf_fm_canonical.h"
 #include "xf_scratch.h"
 #include "xf_wave.h"
 
@@ -51,26 +52,6 @@ int cells_lr_grad_update(const xf_cells *c, const xf_table *t, const float *d_lo
 int gather_f32(const float *src, const uint32_t *rows, size_t n, float *dst, hipStream_t s);
 int batch_sorted_uidx(xf_batch *b, hipStream_t s);
 int batch_reference_coo(xf_batch *b, hipStream_t s);
-// feature values (xf_valued.hip)
-int val_fm_forward(const xf_dev_batch *b, const float *d_xval, int k, const float *d_wu,
-                   const float *d_vu, float *d_S, float *d_loss, float *d_pctr, hipStream_t s);
-int val_lr_forward(const xf_dev_batch *b, const float *d_xval, const float *d_wu, float *d_loss,
-                   float *d_pctr, hipStream_t s);
-int val_fm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const float *d_coo_val,
-                       const uint32_t *d_rows_w, const uint32_t *d_rows_v, const float *d_wu,
-                       const float *d_vu, const float *d_S, const float *d_loss, float *d_gw,
-                       double *d_hpart, hipStream_t s);
-int val_lr_grad_update(xf_table *tw, const xf_dev_batch *b, const float *d_coo_val,
-                       const uint32_t *d_rows_w, const float *d_wu, const float *d_loss,
-                       float *d_gw, double *d_hpart, hipStream_t s);
-// canonical FM (xf_fm_canonical.hip)
-size_t fmc_heavy_doubles(const xf_dev_batch *b, int k);
-int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_vu, float *d_S,
-                float *d_loss, float *d_pctr, hipStream_t s);
-int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uint32_t *d_rows_w,
-                    const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
-                    const float *d_S, const float *d_loss, float *d_gw, double *d_hpart,
-                    hipStream_t s);
 }  // namespace xf
 
 namespace {
@@ -2140,7 +2121,8 @@ static int fmc_reserve(xf_workspace *ws, const xf_batch *b, int k) {
   return XF_OK;
 }
 
-// a valued minibatch (feature_values = on) has the exact-sums kernels of xf_valued.hip only
+// a valued minibatch (feature_values = on) has exact-sums kernels only (canonical FM with VAL,
+// xf_fm_canonical.hip; LR, xf_valued.hip)
 static int valued_check(const xf_workspace *ws, const char *who) {
   XF_REQUIRE(ws->parity == XF_PARITY_EXACT_SUMS,
              "%s: a minibatch with feature values (feature_values) has no reference-order parity "
@@ -2160,6 +2142,13 @@ static int fmc_check_batch(const xf_batch *b, const char *who) {
   return XF_OK;
 }
 
+// the kernels read a null value array as a binary minibatch: an uploaded valued one has its own
+static int fmc_check_values(const xf_batch *b, const char *who) {
+  XF_REQUIRE(!b->valued || b->NNZ == 0 || (b->d_xval && b->d_coo_val),
+             "%s: a minibatch with feature values (feature_values) without its value arrays", who);
+  return XF_OK;
+}
+
 // One canonical FM update: the two Pulls (w gathered with the rows, v rows gathered), the
 // forward (loss, S), the gradient + both Pushes.  Both tables are written by kernels that keep no
 // per-row records: the reference-mode records of any minibatch are rebuilt before they are read.
@@ -2170,6 +2159,7 @@ static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
   if (b->valued) XF_TRY(valued_check(ws, "xf_fm_step"));
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, stream));
+  XF_TRY(fmc_check_values(b, "xf_fm_step"));
   XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
   XF_TRY(fmc_reserve(ws, b, k));
   ws->rec = ws->profiling && ws->step_no++ % xf_workspace::kProfileEvery == 0;
@@ -2184,21 +2174,15 @@ static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
   XF_END(kEvResolve);
   if (v.U) XF_TRY(xf_table_gather_dev(vt, rows_v, v.U, ws->fmc_vu, stream));
   XF_END(kEvGather);
-  if (b->valued)
-    XF_TRY(xf::val_fm_forward(&v, b->d_xval, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr,
-                              S(stream)));
-  else
-    XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr, S(stream)));
+  XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr,
+                         b->valued ? b->d_xval : nullptr, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {
     xf::table_note_write(w);
     xf::table_note_write(vt);
-    if (b->valued)
-      XF_TRY(xf::val_fm_grad_update(w, vt, &v, b->d_coo_val, rows_w, rows_v, ws->wu, ws->fmc_vu,
-                                    ws->fmc_S, ws->loss, ws->g, ws->fmc_hpart, S(stream)));
-    else
-      XF_TRY(xf::fmc_grad_update(w, vt, &v, rows_w, rows_v, ws->wu, ws->fmc_vu, ws->fmc_S,
-                                 ws->loss, ws->g, ws->fmc_hpart, S(stream)));
+    XF_TRY(xf::fmc_grad_update(w, vt, &v, rows_w, rows_v, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss,
+                               ws->g, ws->fmc_hpart, b->valued ? b->d_coo_val : nullptr,
+                               S(stream)));
   }
   XF_END(kEvGrad);
   if (ws->rec) ws->sets[ws->cur].pending = true;
@@ -2211,17 +2195,15 @@ static int fm_canonical_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_works
   XF_TRY(fmc_check_batch(b, "xf_fm_predict"));
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, nullptr));
+  XF_TRY(fmc_check_values(b, "xf_fm_predict"));
   XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
   XF_TRY(fmc_reserve(ws, b, k));
   const xf_dev_batch &v = b->view;
   XF_TRY(xf_table_pull_dev(w, v.ukeys, v.U, ws->slots, ws->wu, nullptr));
   XF_TRY(xf_table_resolve_dev(vt, v.ukeys, v.U, ws->slots2, nullptr));
   XF_TRY(xf_table_gather_dev(vt, ws->slots2, v.U, ws->fmc_vu, nullptr));
-  if (b->valued)
-    XF_TRY(xf::val_fm_forward(&v, b->d_xval, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr,
-                              nullptr));
-  else
-    XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr, nullptr));
+  XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr,
+                         b->valued ? b->d_xval : nullptr, nullptr));
   if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
   XF_TRY(xf_table_check(w, nullptr));
   return xf_table_check(vt, nullptr);
