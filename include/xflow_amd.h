@@ -194,6 +194,28 @@ int xf_batch_compile_valued_gpu(xf_batch **out, const uint64_t *rowptr, const ui
                                 size_t row_end, void *stream);
 int xf_batch_values_dev(const xf_batch *b, const float **xval, const float **coo_val);
 int xf_batch_values_host(const xf_batch *b, const float **xval, const float **coo_val);
+/* The generic build of a minibatch WITH ITS FIELDS (fgid[] / d_fgid[] beside keys[], the first
+ * field of fgid:fid:val; vals / d_vals may be NULL: a binary minibatch): the arrays above plus
+ * xfg[NNZ] in CSR order (beside uidx) and coo_pos[NNZ] in key-grouped order (beside coo_row): the
+ * CSR position of every occurrence — its field is xfg[coo_pos[j]], and "self" in its row is that
+ * position.  Both live in an allocation of their own (xf_dev_batch is unchanged) and come from
+ * xf_batch_fields_dev / _host (fields = 0 and NULLs for a minibatch compiled without fields).
+ * fields must be in 1 .. 64; a nonzero whose fgid lies outside [0, fields) is XF_EINVAL (the
+ * message names the fgid and fields), before anything is built.  What XF_FM_FIELD_AWARE steps. */
+int xf_batch_compile_fielded(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
+                             const int32_t *fgid, const float *vals, const int32_t *labels,
+                             size_t row_begin, size_t row_end, int fields);
+int xf_batch_compile_fielded_dev(xf_batch **out, const uint64_t *d_keys, const int32_t *d_fgid,
+                                 const float *d_vals, const uint32_t *d_rowptr,
+                                 const int32_t *d_labels, uint32_t R, uint32_t NNZ, int fields,
+                                 void *stream);
+int xf_batch_compile_fielded_gpu(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
+                                 const int32_t *fgid, const float *vals, const int32_t *labels,
+                                 size_t row_begin, size_t row_end, int fields, void *stream);
+int xf_batch_fields_dev(const xf_batch *b, int *fields, const uint32_t **xfg,
+                        const uint32_t **coo_pos);
+int xf_batch_fields_host(const xf_batch *b, int *fields, const uint32_t **xfg,
+                         const uint32_t **coo_pos);
 /* The FM key build (fm_worker.cc:205-225) against the tables themselves: when every key of the
  * minibatch sits in the v table's settled tier (xf_table_defrag) and the w table numbers its rows
  * the same way, the key list comes with its state rows, the key-grouped occurrence lists and
@@ -477,10 +499,28 @@ int xf_workspace_parity(xf_workspace *ws, int mode);
  *                    gw = (sum_occ loss) / R, gv[u,f] = (sum_occ loss (S[r,f] - v[u,f])) / R.
  *                    Exact fp64 sums of fp32 terms, as XF_PARITY_EXACT_SUMS.  Needs a minibatch
  *                    with a key list (xf_batch_compile / _gpu / _dev, not the keyed build of
- *                    xf_batch_compile_fm*); refused together with XF_PARITY_REFERENCE_ORDER. */
+ *                    xf_batch_compile_fm*); refused together with XF_PARITY_REFERENCE_ORDER.
+ *   XF_FM_FIELD_AWARE  the field-aware FM (Juan et al.): a key keeps one k-vector per field, the
+ *                    v table is F k wide (F = xf_workspace_fm_fields, set first; coordinate
+ *                    (h, f) at h k + f) and a pair interacts through the vectors each holds for
+ *                    the other's field.  Nonzero j: key u_j, field g_j, x_j (1 without values),
+ *                    a_j[h,f] = v[u_j,h,f] x_j:
+ *                      y2 = sum_{i<j} sum_f a_i[g_j,f] a_j[g_i,f]   (pairs of POSITIONS)
+ *                      gw = (sum_occ loss x) / R
+ *                      gv[u,h,f] = (sum_{occ i of u} sum_{j != i, g_j = h} loss x_i a_j[g_i,f]) / R
+ *                    Exact fp64 sums of fp32 products.  Only TOUCHED coordinates of v are stepped
+ *                    ((u, h): some occurrence of u has another nonzero of field h in its row);
+ *                    the others keep w, n, z bit for bit — an FTRL step with g = 0 would zero a
+ *                    fresh weight for good.  Needs a minibatch compiled with the same number of
+ *                    fields (xf_batch_compile_fielded*) and a v table of dim F k <= 4096; refused
+ *                    with XF_PARITY_REFERENCE_ORDER and with xf_workspace_capture (the step
+ *                    leaves the pulled w and gw for xf_workspace_fetch as it is). */
 #define XF_FM_REFERENCE 0
 #define XF_FM_CANONICAL 1
+#define XF_FM_FIELD_AWARE 2
 int xf_workspace_fm_mode(xf_workspace *ws, int mode);
+/* fields of XF_FM_FIELD_AWARE: 1 .. 64 (a key's touched fields are one 64-bit mask) */
+int xf_workspace_fm_fields(xf_workspace *ws, int fields);
 /* copies of the last step's intermediates to host (parity hook): any pointer may be NULL */
 int xf_workspace_fetch(xf_workspace *ws, float *wu, float *loss, float *g, size_t U,
                        size_t R);
@@ -648,6 +688,17 @@ int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const uint64_t *r
 int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out, const uint64_t *d_keys,
                                   const float *d_vals, const uint32_t *d_rowptr,
                                   const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep);
+/* The same with the nonzeros' fields (xf_batch_compile_fielded / _gpu / _dev; vals / d_vals may
+ * be NULL) for a one-rank FM trainer after xf_sharded_set_fm_fields +
+ * xf_sharded_set_fm_mode(XF_FM_FIELD_AWARE).  With feature values the trainer obeys the rules of
+ * xf_sharded_compile_valued. */
+int xf_sharded_compile_fielded(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
+                               const uint64_t *keys, const int32_t *fgid, const float *vals,
+                               const int32_t *labels, size_t row_begin, size_t row_end, int keep);
+int xf_sharded_compile_fielded_dev(xf_sharded *st, xf_sbatch **out, const uint64_t *d_keys,
+                                   const int32_t *d_fgid, const float *d_vals,
+                                   const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
+                                   uint32_t NNZ, int keep);
 int xf_sbatch_free(xf_sbatch *b);
 int xf_sbatch_dims(const xf_sbatch *b, uint32_t *R, uint32_t *NNZ, uint32_t *U,
                    uint64_t *n_owned /* keys of this minibatch (all ranks) this rank owns */);
@@ -671,8 +722,12 @@ int xf_sharded_set_parity(xf_sharded *st, int mode);
 /* the FM form (xf_workspace_fm_mode) of a one-rank FM trainer, accepted only while its tables
  * hold no key.  XF_FM_CANONICAL also starts an SGD v table from the hash-normal init (a constant
  * init would keep a key's k factors equal forever), and minibatches compiled from then on carry
- * a key list (xf_batch_compile_gpu / _dev).  A trainer of more than one rank: XF_EINVAL. */
+ * a key list (xf_batch_compile_gpu / _dev).  A trainer of more than one rank: XF_EINVAL.
+ * XF_FM_FIELD_AWARE needs xf_sharded_set_fm_fields first; the trainer's k (xf_sharded_config) is
+ * then the WIDTH of a v row, fields x (factors per field), at most 4096; the v table starts
+ * hash-normal for both optimizers, and minibatches come from xf_sharded_compile_fielded*. */
 int xf_sharded_set_fm_mode(xf_sharded *st, int mode);
+int xf_sharded_set_fm_fields(xf_sharded *st, int fields);
 int xf_sharded_tables(xf_sharded *st, xf_table **w, xf_table **v);
 int xf_sharded_stream(xf_sharded *st, void **stream);
 /* ms_sum[6] = owner pull, weights exchange, forward, gradient, gradients exchange, owner
@@ -707,9 +762,13 @@ int XFDestroy(void **h);
  *        parity(exact|reference_order: the forward's row sums in the reference's own fp32
  *        order — one worker, checking mode)
  *        fm_mode(reference|canonical: FM's second-order term as the reference writes it, or
- *        Rendle's per-factor form — xf_workspace_fm_mode; canonical: model 1, one worker)
+ *        Rendle's per-factor form — xf_workspace_fm_mode; canonical: model 1, one worker —
+ *        |field_aware: a key keeps k factors per field and a pair interacts through the vectors
+ *        each holds for the other's field; model 1, one worker, parity=exact, with fields=N)
+ *        fields(1 .. 64, fields x k <= 4096: the number of field-group ids, fgid in [0, fields))
  *        feature_values(off|on: a nonzero contributes x = val, the third field of
- *        fgid:fid:val, instead of 1 — model 0, or model 1 with fm_mode=canonical; one worker,
+ *        fgid:fid:val, instead of 1 — model 0, or model 1 with fm_mode=canonical or
+ *        field_aware; one worker,
  *        parity=exact, block_cache=0, ingest=host)
  *        model_in model_out (model file to load before / save after training)
  *        block_cache(0|1) block_cache_dir (binarized block cache of the text files)

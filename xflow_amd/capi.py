@@ -15,8 +15,8 @@ XF_OK = 0
 OPT_FTRL, OPT_SGD = 0, 1
 INIT_ZERO, INIT_CONST, INIT_HASHNORM = 0, 1, 2
 HEAVY_SEG = 64
-FM_REFERENCE, FM_CANONICAL = 0, 1
-FM_MODES = {"reference": FM_REFERENCE, "canonical": FM_CANONICAL}
+FM_REFERENCE, FM_CANONICAL, FM_FIELD_AWARE = 0, 1, 2
+FM_MODES = {"reference": FM_REFERENCE, "canonical": FM_CANONICAL, "field_aware": FM_FIELD_AWARE}
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -101,6 +101,21 @@ SIGNATURES = {
                                               C.c_uint32, vp]),
     "xf_batch_compile_valued_gpu": (C.c_int, [C.POINTER(vp), u64p, u64p, f32p, i32p, C.c_size_t,
                                               C.c_size_t, vp]),
+    "xf_batch_compile_fielded": (C.c_int, [C.POINTER(vp), u64p, u64p, i32p, f32p, i32p, C.c_size_t,
+                                           C.c_size_t, C.c_int]),
+    "xf_batch_compile_fielded_dev": (C.c_int, [C.POINTER(vp), vp, vp, vp, vp, vp, C.c_uint32,
+                                               C.c_uint32, C.c_int, vp]),
+    "xf_batch_compile_fielded_gpu": (C.c_int, [C.POINTER(vp), u64p, u64p, i32p, f32p, i32p,
+                                               C.c_size_t, C.c_size_t, C.c_int, vp]),
+    "xf_batch_fields_dev": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(vp)]),
+    "xf_batch_fields_host": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(u32p),
+                                       C.POINTER(u32p)]),
+    "xf_sharded_compile_fielded": (C.c_int, [vp, C.POINTER(vp), u64p, u64p, i32p, f32p, i32p,
+                                             C.c_size_t, C.c_size_t, C.c_int]),
+    "xf_sharded_compile_fielded_dev": (C.c_int, [vp, C.POINTER(vp), vp, vp, vp, vp, vp,
+                                                 C.c_uint32, C.c_uint32, C.c_int]),
+    "xf_sharded_set_fm_fields": (C.c_int, [vp, C.c_int]),
+    "xf_workspace_fm_fields": (C.c_int, [vp, C.c_int]),
     "xf_batch_values_dev": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "xf_batch_values_host": (C.c_int, [vp, C.POINTER(f32p), C.POINTER(f32p)]),
     "xf_sharded_compile_valued": (C.c_int, [vp, C.POINTER(vp), u64p, u64p, f32p, i32p,
@@ -473,10 +488,12 @@ class Batch:
     """A compiled minibatch (host arrays; device mirror after upload())."""
 
     def __init__(self, rowptr, keys, labels, row_begin=0, row_end=None, on_gpu=False,
-                 values=None):
+                 values=None, fields=None, fgid=None):
         """on_gpu=False: host key build (xf_batch_compile); True: the GPU one
         (xf_batch_compile_gpu), the batch is then already device-resident.  values (float32,
-        beside keys): a minibatch with feature values (xf_batch_compile_valued / _gpu)."""
+        beside keys): a minibatch with feature values (xf_batch_compile_valued / _gpu).
+        fields (1 .. 64) with fgid (int32, beside keys): a minibatch with its fields, for
+        field-aware FM (xf_batch_compile_fielded / _gpu; with or without values)."""
         rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
@@ -484,11 +501,28 @@ class Batch:
             row_end = len(rowptr) - 1
         self.h = vp()
         self.valued = values is not None
+        self.fields = int(fields) if fields is not None else 0
         if self.valued:
             values = np.ascontiguousarray(values, dtype=np.float32)
             assert len(values) == len(keys), "one value per key"
             if len(values) == 0:
                 values = np.zeros(1, np.float32)   # a non-null pointer
+        if fields is not None:
+            assert fgid is not None, "fields needs the nonzeros' fgid"
+            fgid = np.ascontiguousarray(fgid, dtype=np.int32)
+            assert len(fgid) == len(keys), "one fgid per key"
+            if len(fgid) == 0:
+                fgid = np.zeros(1, np.int32)
+            vptr = _p(values, f32p) if self.valued else None
+            if on_gpu:
+                check(lib().xf_batch_compile_fielded_gpu(
+                    C.byref(self.h), _p(rowptr, u64p), _p(keys, u64p), _p(fgid, i32p), vptr,
+                    _p(labels, i32p), row_begin, row_end, self.fields, None))
+            else:
+                check(lib().xf_batch_compile_fielded(
+                    C.byref(self.h), _p(rowptr, u64p), _p(keys, u64p), _p(fgid, i32p), vptr,
+                    _p(labels, i32p), row_begin, row_end, self.fields))
+        elif self.valued:
             if on_gpu:
                 check(lib().xf_batch_compile_valued_gpu(
                     C.byref(self.h), _p(rowptr, u64p), _p(keys, u64p), _p(values, f32p),
@@ -537,6 +571,16 @@ class Batch:
             return np.zeros(0, np.float32), np.zeros(0, np.float32)
         return (np.ctypeslib.as_array(xv, (self.NNZ,)).copy(),
                 np.ctypeslib.as_array(cv, (self.NNZ,)).copy())
+
+    def field_arrays(self):
+        """(xfg, coo_pos) of a minibatch compiled with fields: the nonzeros' fields in CSR order
+        and the occurrences' CSR positions grouped by key"""
+        F, xg, cp = C.c_int(0), u32p(), u32p()
+        check(lib().xf_batch_fields_host(self.h, C.byref(F), C.byref(xg), C.byref(cp)))
+        if not F.value or self.NNZ == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        return (np.ctypeslib.as_array(xg, (self.NNZ,)).copy(),
+                np.ctypeslib.as_array(cp, (self.NNZ,)).copy())
 
     def panels(self):
         P, pp, pi = C.c_uint32(0), u32p(), u32p()
@@ -804,6 +848,10 @@ class Workspace:
         second-order term) or 'canonical' (Rendle's per-factor sums)"""
         check(lib().xf_workspace_fm_mode(self.h, FM_MODES[mode]))
 
+    def fm_fields(self, fields):
+        """the number of fields of 'field_aware' (1 .. 64): before fm_mode('field_aware')"""
+        check(lib().xf_workspace_fm_fields(self.h, int(fields)))
+
     def fetch(self, U, R):
         wu = np.empty(U, np.float32)
         loss = np.empty(R, np.float32)
@@ -959,14 +1007,19 @@ class Sharded:
 
     def __init__(self, group=None, model="lr", optimizer="ftrl", k=10, capacity=1 << 22,
                  schedule="sequential", seed=0, host_key_build=False, update="rank_ordered",
-                 fm_mode="reference", **hyper):
-        """fm_mode="canonical": Rendle's FM on a one-rank trainer (xf_sharded_set_fm_mode)"""
+                 fm_mode="reference", fields=None, **hyper):
+        """fm_mode="canonical": Rendle's FM on a one-rank trainer (xf_sharded_set_fm_mode);
+        fm_mode="field_aware" with fields=F: k factors per field, v rows F k wide"""
         require_gpu()
         c = ShardedConfig()
         lib().xf_sharded_config_default(C.byref(c))
         c.model = 0 if model == "lr" else 1
         c.optimizer = OPT_FTRL if optimizer == "ftrl" else OPT_SGD
-        c.k, c.capacity, c.seed = k, capacity, seed
+        self.fields = int(fields) if fields is not None else 0
+        assert fm_mode != "field_aware" or 1 <= self.fields <= 64, \
+            "fm_mode='field_aware' needs fields=F, 1 .. 64"
+        vdim = k * self.fields if fm_mode == "field_aware" else k
+        c.k, c.capacity, c.seed = vdim, capacity, seed
         c.schedule = _SCHEDULES[schedule]
         c.host_key_build = 1 if host_key_build else 0
         c.update_rule = {"rank_ordered": 0, "sum_then_step": 1}[update]
@@ -980,12 +1033,14 @@ class Sharded:
         w, v = vp(), vp()
         check(lib().xf_sharded_tables(self.h, C.byref(w), C.byref(v)))
         self.w = Table.from_handle(w, 1, c.optimizer)
-        self.v = Table.from_handle(v, k, c.optimizer) if v else None
+        self.v = Table.from_handle(v, vdim, c.optimizer) if v else None
+        if fm_mode == "field_aware":
+            check(lib().xf_sharded_set_fm_fields(self.h, self.fields))
         if fm_mode != "reference":
             self.set_fm_mode(fm_mode)
 
     def set_fm_mode(self, mode):
-        """'reference' or 'canonical': before the first step, one rank only"""
+        """'reference', 'canonical' or 'field_aware': before the first step, one rank only"""
         check(lib().xf_sharded_set_fm_mode(self.h, FM_MODES[mode]))
 
     def close(self):
@@ -995,8 +1050,10 @@ class Sharded:
 
     __del__ = close
 
-    def compile(self, rowptr, keys, labels, row_begin=0, row_end=None, keep=True, values=None):
-        """values (float32, beside keys): a minibatch with feature values, one rank only"""
+    def compile(self, rowptr, keys, labels, row_begin=0, row_end=None, keep=True, values=None,
+                fgid=None):
+        """values (float32, beside keys): a minibatch with feature values, one rank only; fgid
+        (int32, beside keys): a minibatch with its fields, for fm_mode='field_aware'"""
         rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
@@ -1010,6 +1067,17 @@ class Sharded:
             assert len(values) == len(keys), "one value per key"
             if len(values) == 0:
                 values = np.zeros(1, np.float32)
+        if fgid is not None:
+            fgid = np.ascontiguousarray(fgid, dtype=np.int32)
+            assert len(fgid) == len(keys), "one fgid per key"
+            if len(fgid) == 0:
+                fgid = np.zeros(1, np.int32)
+            check(lib().xf_sharded_compile_fielded(
+                self.h, C.byref(h), _p(rowptr, u64p), _p(keys, u64p), _p(fgid, i32p),
+                _p(values, f32p) if values is not None else None, _p(labels, i32p), row_begin,
+                row_end, 1 if keep else 0))
+            return ShardedBatch(h, self)
+        if values is not None:
             check(lib().xf_sharded_compile_valued(
                 self.h, C.byref(h), _p(rowptr, u64p), _p(keys, u64p), _p(values, f32p),
                 _p(labels, i32p), row_begin, row_end, 1 if keep else 0))

@@ -337,13 +337,18 @@ extern "C" int xf_batch_panels(const xf_batch *b, uint32_t *P, const uint32_t **
 
 static int batch_compile_host(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
                               const float *vals, const int32_t *labels, size_t row_begin,
-                              size_t row_end) {
+                              size_t row_end, const int32_t *fgid = nullptr, int fields = 0) {
   XF_REQUIRE(out && rowptr && labels && row_end >= row_begin, "xf_batch_compile: bad argument");
   const size_t R = row_end - row_begin;
   const uint64_t base = rowptr[row_begin];
   const size_t NNZ = (size_t)(rowptr[row_end] - base);
   XF_REQUIRE(NNZ == 0 || keys, "xf_batch_compile: null keys");
   XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile: batch too large");
+  if (fields)  // before anything is built: a field the v rows have no vector for
+    for (size_t j = 0; j < NNZ; ++j)
+      XF_REQUIRE(fgid[base + j] >= 0 && fgid[base + j] < fields,
+                 "xf_batch_compile_fielded: nonzero %zu has fgid %d, outside [0, fields = %d)", j,
+                 (int)fgid[base + j], fields);
   xf_batch *b = new xf_batch;
   b->R = (uint32_t)R;
   b->NNZ = (uint32_t)NNZ;
@@ -380,6 +385,15 @@ static int batch_compile_host(xf_batch **out, const uint64_t *rowptr, const uint
     b->coo_val.resize(NNZ);
     for (size_t j = 0; j < NNZ; ++j) b->coo_val[j] = b->xval[kp[j].pos];
   }
+  if (fields) {
+    b->fields = fields;
+    b->xfg.resize(NNZ);
+    b->coo_pos.resize(NNZ);
+    for (size_t j = 0; j < NNZ; ++j) {
+      b->xfg[j] = (uint32_t)fgid[base + j];
+      b->coo_pos[j] = kp[j].pos;
+    }
+  }
   b->segptr.push_back((uint32_t)NNZ);
   b->U = (uint32_t)b->ukeys.size();
   for (uint32_t u = 0; u < b->U; ++u)
@@ -410,6 +424,41 @@ extern "C" int xf_batch_compile_valued(xf_batch **out, const uint64_t *rowptr, c
   return batch_compile_host(out, rowptr, keys, vals ? vals : none, labels, row_begin, row_end);
 }
 
+// the same with the nonzeros' field-group ids (fgid[] runs beside keys[], every one in
+// [0, fields)); vals may be null: a binary minibatch
+extern "C" int xf_batch_compile_fielded(xf_batch **out, const uint64_t *rowptr,
+                                        const uint64_t *keys, const int32_t *fgid,
+                                        const float *vals, const int32_t *labels, size_t row_begin,
+                                        size_t row_end, int fields) {
+  XF_REQUIRE(fields >= 1 && fields <= 64,
+             "xf_batch_compile_fielded: fields must be in 1 .. 64, not %d", fields);
+  XF_REQUIRE(fgid || (rowptr && row_end >= row_begin && rowptr[row_end] == rowptr[row_begin]),
+             "xf_batch_compile_fielded: null fgid");
+  return batch_compile_host(out, rowptr, keys, vals, labels, row_begin, row_end, fgid, fields);
+}
+
+// fields the minibatch was compiled with (0: none) and its field arrays: on the device (after
+// xf_batch_upload for a host-built batch) and their host views
+extern "C" int xf_batch_fields_dev(const xf_batch *b, int *fields, const uint32_t **xfg,
+                                   const uint32_t **coo_pos) {
+  XF_REQUIRE(b, "xf_batch_fields_dev: null batch");
+  XF_REQUIRE(!b->fields || b->d_blob, "xf_batch_fields_dev: batch not uploaded");
+  if (fields) *fields = b->fields;
+  if (xfg) *xfg = b->fields ? b->d_xfg : nullptr;
+  if (coo_pos) *coo_pos = b->fields ? b->d_coo_pos : nullptr;
+  return XF_OK;
+}
+
+extern "C" int xf_batch_fields_host(const xf_batch *b, int *fields, const uint32_t **xfg,
+                                    const uint32_t **coo_pos) {
+  XF_REQUIRE(b, "xf_batch_fields_host: null batch");
+  XF_TRY(need_host(b));
+  if (fields) *fields = b->fields;
+  if (xfg) *xfg = b->fields ? b->xfg.data() : nullptr;
+  if (coo_pos) *coo_pos = b->fields ? b->coo_pos.data() : nullptr;
+  return XF_OK;
+}
+
 // device arrays of a valued minibatch (null, null for a binary one); host views likewise
 extern "C" int xf_batch_values_dev(const xf_batch *b, const float **xval, const float **coo_val) {
   XF_REQUIRE(b, "xf_batch_values_dev: null batch");
@@ -433,14 +482,15 @@ void cells_free(xf_cells *c);
 
 extern "C" int xf_batch_free(xf_batch *b) {
   if (!b) return XF_OK;
-  if (b->d_blob || b->cells || b->d_raw || b->d_rows_u || b->d_fm_rows[0] || b->d_uidx_sorted ||
-      b->d_ref_coo) {
+  if (b->d_blob || b->d_fld || b->cells || b->d_raw || b->d_rows_u || b->d_fm_rows[0] ||
+      b->d_uidx_sorted || b->d_ref_coo) {
     // kernels still running on the batch must finish first (hipFree used to imply that)
     (void)hipDeviceSynchronize();
   }
   if (b->d_blob) xf::blob_free(b->d_blob, b->d_blob_bytes);
   if (b->d_blob2) xf::blob_free(b->d_blob2, b->d_blob2_bytes);
   if (b->d_vals) xf::blob_free(b->d_vals, b->d_vals_bytes);
+  if (b->d_fld) xf::blob_free(b->d_fld, b->d_fld_bytes);
   if (b->cells) xf::cells_free(b->cells);
   if (b->d_raw) xf::blob_free(b->d_raw, b->d_raw_bytes);
   if (b->d_rows_u) (void)hipFree(b->d_rows_u);
@@ -532,6 +582,17 @@ extern "C" int xf_batch_upload(xf_batch *b, void *stream) {
     if (b->NNZ) {
       XF_HIP(hipMemcpyAsync(b->d_vals, b->xval.data(), (size_t)b->NNZ * 4, hipMemcpyHostToDevice, s));
       XF_HIP(hipMemcpyAsync((char *)b->d_vals + vb, b->coo_val.data(), (size_t)b->NNZ * 4,
+                            hipMemcpyHostToDevice, s));
+    }
+  }
+  if (b->fields) {
+    const size_t fb = al((size_t)b->NNZ * 4);
+    XF_TRY(xf::blob_alloc((void **)&b->d_fld, 2 * fb + 256, &b->d_fld_bytes));
+    b->d_xfg = b->d_fld;
+    b->d_coo_pos = (const uint32_t *)((const char *)b->d_fld + fb);
+    if (b->NNZ) {
+      XF_HIP(hipMemcpyAsync(b->d_fld, b->xfg.data(), (size_t)b->NNZ * 4, hipMemcpyHostToDevice, s));
+      XF_HIP(hipMemcpyAsync((char *)b->d_fld + fb, b->coo_pos.data(), (size_t)b->NNZ * 4,
                             hipMemcpyHostToDevice, s));
     }
   }

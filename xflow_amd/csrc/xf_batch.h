@@ -29,6 +29,15 @@ struct xf_batch {
   float *d_vals = nullptr;  // xval | coo_val
   size_t d_vals_bytes = 0;
   const float *d_xval = nullptr, *d_coo_val = nullptr;
+  // fields (xf_batch_compile_fielded*, field-aware FM): xfg[NNZ] the nonzeros' field-group ids in
+  // CSR order beside uidx, every one in [0, fields); coo_pos[NNZ] the occurrences' CSR positions
+  // in key-grouped order beside coo_row (an occurrence's field and the identity of "self" come
+  // from it).  On the device in an allocation of their own, as the values are.
+  int fields = 0;  // 0: compiled without fields
+  std::vector<uint32_t> xfg, coo_pos;
+  uint32_t *d_fld = nullptr;  // xfg | coo_pos
+  size_t d_fld_bytes = 0;
+  const uint32_t *d_xfg = nullptr, *d_coo_pos = nullptr;
   bool on_device_only = false;  // built by xf_batch_compile_dev and not downloaded yet
   void *d_blob = nullptr;  // one device allocation holding all arrays
   size_t d_blob_bytes = 0;
@@ -95,7 +104,8 @@ int sort_key_pos(const uint64_t *d_keys, uint32_t n, uint64_t lo, uint64_t span,
 // xf_batch_compile_dev, with or without the panel-major forward view (xf_batch_dev.hip)
 int batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint32_t *d_rowptr,
                          const int32_t *d_labels, uint32_t R, uint32_t NNZ, hipStream_t stream,
-                         bool panels, const float *d_vals = nullptr);
+                         bool panels, const float *d_vals = nullptr,
+                         const int32_t *d_fgid = nullptr, int fields = 0);
 // LR, the worker side of the weight / gradient exchange (xf_keybuild.hip): a minibatch with its
 // sorted unique keys, row offsets and labels on the device — nothing else — and its cells over
 // the unique-key index.  *done = false: beyond that build's limits, nothing was built.

@@ -428,6 +428,17 @@ extern "C" int xf_sort_key_pos(const uint64_t *d_keys, uint32_t n, uint64_t lo, 
   return XF_OK;
 }
 
+namespace {
+// a fielded minibatch: the smallest position whose field-group id lies outside [0, fields)
+__global__ void k_fgid_check(const int32_t *__restrict__ fgid, size_t n, int fields,
+                             uint32_t *__restrict__ first_bad) {
+  XF_GRID_STRIDE(j, n) {
+    const int32_t g = fgid[j];
+    if (g < 0 || g >= fields) atomicMin(first_bad, (uint32_t)j);
+  }
+}
+}  // namespace
+
 // Device key build.  d_keys[NNZ], d_rowptr[R+1] (row-relative, d_rowptr[0] == 0),
 // d_labels[R] are device pointers; the compiled batch stays on the device
 // (xf_batch_download brings the arrays to the host for inspection).
@@ -442,11 +453,27 @@ extern "C" int xf_batch_compile_dev(xf_batch **out, const uint64_t *d_keys,
 // nonzero build)
 int xf::batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint32_t *d_rowptr,
                              const int32_t *d_labels, uint32_t R, uint32_t NNZ, hipStream_t stream,
-                             bool panels, const float *d_vals) {
+                             bool panels, const float *d_vals, const int32_t *d_fgid,
+                             int fields) {
   XF_REQUIRE(out && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || d_keys),
              "xf_batch_compile_dev: null argument");
   hipStream_t s = (hipStream_t)stream;
   Scratch sc;
+  if (fields && NNZ) {  // before anything is built: a field the v rows have no vector for
+    uint32_t *d_bad = nullptr, bad = 0xFFFFFFFFu;
+    XF_TRY(sc.get(&d_bad, 1));
+    XF_HIP(hipMemcpyAsync(d_bad, &bad, 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_fgid_check, dim3(grid_for(NNZ)), dim3(kBlock), 0, s, d_fgid, (size_t)NNZ,
+                       fields, d_bad);
+    XF_HIP(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s));
+    XF_HIP(hipStreamSynchronize(s));
+    if (bad != 0xFFFFFFFFu) {
+      int32_t g = 0;
+      XF_HIP(hipMemcpy(&g, d_fgid + bad, 4, hipMemcpyDeviceToHost));
+      return xf::set_error(XF_EINVAL, "xf_batch_compile_fielded: nonzero %u has fgid %d, outside "
+                           "[0, fields = %d)", bad, (int)g, fields);
+    }
+  }
   xf_batch *b = new xf_batch;
   b->R = R;
   b->NNZ = NNZ;
@@ -456,8 +483,17 @@ int xf::batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint3
     ~Guard() {
       if (b) xf_batch_free(b);
     }
-  } guard{d_vals ? b : nullptr};
+  } guard{(d_vals || fields) ? b : nullptr};
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  if (fields) {  // xfg | coo_pos, an allocation of the batch's own
+    const size_t fb = al((size_t)NNZ * 4);
+    b->fields = fields;
+    XF_TRY(xf::blob_alloc((void **)&b->d_fld, 2 * fb + 256, &b->d_fld_bytes));
+    b->d_xfg = b->d_fld;
+    b->d_coo_pos = (const uint32_t *)((const char *)b->d_fld + fb);
+    if (NNZ)  // (checked above: non-negative, so the bits are the unsigned ids)
+      XF_HIP(hipMemcpyAsync(b->d_fld, d_fgid, (size_t)NNZ * 4, hipMemcpyDeviceToDevice, s));
+  }
   if (d_vals) {  // xval | coo_val, an allocation of the batch's own
     const size_t vb = al((size_t)NNZ * 4);
     b->valued = true;
@@ -502,6 +538,8 @@ int xf::batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint3
     if (d_vals)
       hipLaunchKernelGGL(k_coo_val, dim3(grid_for(NNZ)), dim3(kBlock), 0, s, spos, d_vals,
                          (size_t)NNZ, (float *)b->d_coo_val);
+    if (fields)  // an occurrence's CSR position is what the sort carried along
+      XF_HIP(hipMemcpyAsync((void *)b->d_coo_pos, spos, (size_t)NNZ * 4, hipMemcpyDeviceToDevice, s));
   } else {
     XF_HIP(hipMemsetAsync(segptr, 0, 4, s));
   }
@@ -690,6 +728,10 @@ extern "C" int xf_batch_download(xf_batch *b) {
   if (b->valued) {
     XF_HIP(get(b->xval, b->d_xval, v.NNZ));
     XF_HIP(get(b->coo_val, b->d_coo_val, v.NNZ));
+  }
+  if (b->fields) {
+    XF_HIP(get(b->xfg, b->d_xfg, v.NNZ));
+    XF_HIP(get(b->coo_pos, b->d_coo_pos, v.NNZ));
   }
   b->on_device_only = false;
   return XF_OK;
@@ -985,6 +1027,59 @@ extern "C" int xf_batch_compile_valued_gpu(xf_batch **out, const uint64_t *rowpt
   XF_HIP(hipStreamSynchronize(s));
   return xf_batch_compile_valued_dev(out, d_keys, d_vals, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ,
                                      stream);
+}
+
+// The generic build with the nonzeros' field-group ids: d_fgid[NNZ] runs beside d_keys, every id
+// in [0, fields) (else XF_EINVAL, before anything is built); d_vals may be null (binary).  The
+// batch gains xfg (CSR order) and coo_pos (key-grouped order) — xf_batch_fields_dev.
+extern "C" int xf_batch_compile_fielded_dev(xf_batch **out, const uint64_t *d_keys,
+                                            const int32_t *d_fgid, const float *d_vals,
+                                            const uint32_t *d_rowptr, const int32_t *d_labels,
+                                            uint32_t R, uint32_t NNZ, int fields, void *stream) {
+  XF_REQUIRE(fields >= 1 && fields <= 64,
+             "xf_batch_compile_fielded_dev: fields must be in 1 .. 64, not %d", fields);
+  XF_REQUIRE(d_fgid || NNZ == 0, "xf_batch_compile_fielded_dev: null fgid");
+  return xf::batch_compile_dev_ex(out, d_keys, d_rowptr, d_labels, R, NNZ, (hipStream_t)stream,
+                                  false, d_vals, d_fgid, fields);
+}
+
+// host-array front end of xf_batch_compile_fielded_dev
+extern "C" int xf_batch_compile_fielded_gpu(xf_batch **out, const uint64_t *rowptr,
+                                            const uint64_t *keys, const int32_t *fgid,
+                                            const float *vals, const int32_t *labels,
+                                            size_t row_begin, size_t row_end, int fields,
+                                            void *stream) {
+  XF_REQUIRE(out && rowptr && labels && row_end >= row_begin,
+             "xf_batch_compile_fielded_gpu: bad argument");
+  const size_t R = row_end - row_begin;
+  const uint64_t base = rowptr[row_begin];
+  const size_t NNZ = (size_t)(rowptr[row_end] - base);
+  XF_REQUIRE(NNZ == 0 || (keys && fgid), "xf_batch_compile_fielded_gpu: null keys or fgid");
+  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile_fielded_gpu: batch too large");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<uint32_t> rp(R + 1);
+  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
+  Scratch sc;
+  uint64_t *d_keys = nullptr;
+  int32_t *d_fg = nullptr;
+  float *d_vals = nullptr;
+  uint32_t *d_rp = nullptr;
+  int32_t *d_lab = nullptr;
+  XF_TRY(sc.get(&d_keys, NNZ));
+  XF_TRY(sc.get(&d_fg, NNZ + 1));
+  if (vals) XF_TRY(sc.get(&d_vals, NNZ + 1));
+  XF_TRY(sc.get(&d_rp, R + 1));
+  XF_TRY(sc.get(&d_lab, R));
+  if (NNZ) {
+    XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
+    XF_HIP(hipMemcpyAsync(d_fg, fgid + base, NNZ * 4, hipMemcpyHostToDevice, s));
+    if (vals) XF_HIP(hipMemcpyAsync(d_vals, vals + base, NNZ * 4, hipMemcpyHostToDevice, s));
+  }
+  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
+  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
+  XF_HIP(hipStreamSynchronize(s));
+  return xf_batch_compile_fielded_dev(out, d_keys, d_fg, d_vals, d_rp, d_lab, (uint32_t)R,
+                                      (uint32_t)NNZ, fields, stream);
 }
 
 // host-array front end of xf_batch_compile_fm_dev (the reader's block arrays and a row slice)

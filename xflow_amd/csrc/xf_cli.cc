@@ -20,8 +20,10 @@ int main(int argc, char *argv[]) {
               << "LR model example: xflow_lr data/small_train data/small_test 0 100\n"
               << "FM model example: xflow_lr data/small_train data/small_test 1 100\n"
               << "Rendle's FM (per-factor second-order term, one worker): append fm_mode=canonical\n"
+              << "field-aware FM (k factors per field, one worker; fgid in [0, N)): append "
+                 "fm_mode=field_aware fields=N\n"
               << "feature values (x = val of fgid:fid:val instead of 1; LR, or FM with "
-                 "fm_mode=canonical; one worker): append feature_values=on\n";
+                 "fm_mode=canonical or field_aware; one worker): append feature_values=on\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler

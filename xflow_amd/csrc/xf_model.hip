@@ -29,6 +29,7 @@
 #include "xf_cells.h"
 #include "xf_common.h"
 #include "xf_device.h"
+#include "xf_ffm.h"
 #include "xf_fm_canonical.h"
 #include "xf_scratch.h"
 #include "xf_wave.h"
@@ -1588,6 +1589,7 @@ struct xf_workspace {
   int parity = 0;
   // FM form: XF_FM_REFERENCE (pooled sums, as fm_worker.cc) or XF_FM_CANONICAL (per-factor)
   int fm_mode = XF_FM_REFERENCE;
+  int fm_fields = 0;           // field-aware FM: F (the v rows are F x k wide); 0: not set
   float *fmc_S = nullptr;      // canonical FM: the per-factor row sums, R x k
   size_t capS = 0;
   float *fmc_vu = nullptr;     // canonical FM: the pulled factor rows, U x k
@@ -1767,21 +1769,39 @@ static int ws_reserve_cells(xf_workspace *ws, const xf_cells *c, bool dense_g) {
 extern "C" int xf_workspace_parity(xf_workspace *ws, int mode) {
   XF_REQUIRE(ws && (mode == XF_PARITY_EXACT_SUMS || mode == XF_PARITY_REFERENCE_ORDER),
              "xf_workspace_parity: bad argument");
-  XF_REQUIRE(mode == XF_PARITY_EXACT_SUMS || ws->fm_mode != XF_FM_CANONICAL,
+  XF_REQUIRE(mode == XF_PARITY_EXACT_SUMS || ws->fm_mode == XF_FM_REFERENCE,
              "xf_workspace_parity: the reference-order mode is the reference form's; this "
-             "workspace runs canonical FM (xf_workspace_fm_mode), whose sums are exact only");
+             "workspace runs canonical or field-aware FM (xf_workspace_fm_mode), whose sums are "
+             "exact only");
   ws->parity = mode;
   return XF_OK;
 }
 
 extern "C" int xf_workspace_fm_mode(xf_workspace *ws, int mode) {
   XF_REQUIRE(ws, "xf_workspace_fm_mode: null workspace");
-  XF_REQUIRE(mode == XF_FM_REFERENCE || mode == XF_FM_CANONICAL,
-             "xf_workspace_fm_mode: mode must be XF_FM_REFERENCE (0) or XF_FM_CANONICAL (1)");
+  XF_REQUIRE(mode == XF_FM_REFERENCE || mode == XF_FM_CANONICAL || mode == XF_FM_FIELD_AWARE,
+             "xf_workspace_fm_mode: mode must be XF_FM_REFERENCE (0), XF_FM_CANONICAL (1) or "
+             "XF_FM_FIELD_AWARE (2)");
   XF_REQUIRE(mode == XF_FM_REFERENCE || ws->parity == XF_PARITY_EXACT_SUMS,
-             "xf_workspace_fm_mode: canonical FM has no reference-order parity mode; this "
-             "workspace is in XF_PARITY_REFERENCE_ORDER (xf_workspace_parity)");
+             "xf_workspace_fm_mode: canonical and field-aware FM have no reference-order parity "
+             "mode; this workspace is in XF_PARITY_REFERENCE_ORDER (xf_workspace_parity)");
+  XF_REQUIRE(mode != XF_FM_FIELD_AWARE || !ws->capture,
+             "xf_workspace_fm_mode: field-aware FM is not stepped with xf_workspace_capture on: "
+             "its step leaves the pulled weights and the w gradients for xf_workspace_fetch as it "
+             "is");
+  XF_REQUIRE(mode != XF_FM_FIELD_AWARE || ws->fm_fields,
+             "xf_workspace_fm_mode: field-aware FM needs its number of fields first "
+             "(xf_workspace_fm_fields)");
   ws->fm_mode = mode;
+  return XF_OK;
+}
+
+extern "C" int xf_workspace_fm_fields(xf_workspace *ws, int fields) {
+  XF_REQUIRE(ws, "xf_workspace_fm_fields: null workspace");
+  XF_REQUIRE(fields >= 1 && fields <= 64,
+             "xf_workspace_fm_fields: fields must be in 1 .. 64 (a key's touched fields are one "
+             "64-bit mask), not %d", fields);
+  ws->fm_fields = fields;
   return XF_OK;
 }
 
@@ -1811,6 +1831,10 @@ static int fm_forward_reforder(xf_batch *b, int k, const float *wu, const float 
 
 extern "C" int xf_workspace_capture(xf_workspace *ws, int enable) {
   XF_REQUIRE(ws, "xf_workspace_capture: null workspace");
+  XF_REQUIRE(!enable || ws->fm_mode != XF_FM_FIELD_AWARE,
+             "xf_workspace_capture: field-aware FM (xf_workspace_fm_mode) is not stepped with "
+             "capture on: its step leaves the pulled weights and the w gradients for "
+             "xf_workspace_fetch as it is");
   ws->capture = enable != 0;
   return XF_OK;
 }
@@ -2209,6 +2233,118 @@ static int fm_canonical_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_works
   return xf_table_check(vt, nullptr);
 }
 
+// ---- field-aware FM (xf_workspace_fm_mode + xf_workspace_fm_fields; kernels in xf_ffm.hip)
+static int ffm_check(const xf_table *vt, const xf_batch *b, const xf_workspace *ws,
+                     const char *who, int *k) {
+  XF_REQUIRE(!b->fm_keyed || b->U == 0,
+             "%s: field-aware FM needs a minibatch compiled with its fields "
+             "(xf_batch_compile_fielded*); this one comes from the keyed build against the "
+             "tables' settled tiers (xf_batch_compile_fm*)", who);
+  XF_REQUIRE(b->fields > 0,
+             "%s: field-aware FM needs a minibatch compiled with its fields "
+             "(xf_batch_compile_fielded*): this one was compiled without fields", who);
+  XF_REQUIRE(b->fields == ws->fm_fields,
+             "%s: the minibatch was compiled with fields = %d, the workspace runs fields = %d "
+             "(xf_workspace_fm_fields)", who, b->fields, ws->fm_fields);
+  XF_REQUIRE(ws->parity == XF_PARITY_EXACT_SUMS && !ws->capture,
+             "%s: field-aware FM with a parity mode or capture", who);
+  const int dim = xf::table_dim(vt), F = ws->fm_fields;
+  XF_REQUIRE(dim >= F && dim % F == 0 && dim <= 4096,
+             "%s: the v table's dim (%d) is not fields (%d) x k with fields x k <= 4096", who,
+             dim, F);
+  *k = dim / F;
+  return XF_OK;
+}
+
+// the pulled F k wide rows and the heavy keys' chunk sums (no S: the forward keeps no row sums)
+static int ffm_reserve(xf_workspace *ws, const xf_batch *b, int dim) {
+  const size_t nV = std::max<size_t>((size_t)b->U * dim, 1);
+  if (nV > ws->capVu) {
+    if (ws->fmc_vu) XF_HIP(hipFree(ws->fmc_vu));
+    ws->fmc_vu = nullptr;
+    ws->capVu = 0;
+    XF_HIP(hipMalloc((void **)&ws->fmc_vu, (nV + nV / 8 + 1024) * 4));
+    ws->capVu = nV + nV / 8 + 1024;
+  }
+  const size_t nH = std::max<size_t>(xf::ffm_heavy_doubles(&b->view, dim), 1);
+  if (nH > ws->capHpart) {
+    if (ws->fmc_hpart) XF_HIP(hipFree(ws->fmc_hpart));
+    ws->fmc_hpart = nullptr;
+    ws->capHpart = 0;
+    XF_HIP(hipMalloc((void **)&ws->fmc_hpart, (nH + nH / 8 + 1024) * 8));
+    ws->capHpart = nH + nH / 8 + 1024;
+  }
+  return XF_OK;
+}
+
+static int ffm_check_arrays(const xf_batch *b, const char *who) {
+  XF_REQUIRE(b->NNZ == 0 || (b->d_xfg && b->d_coo_pos),
+             "%s: a minibatch with fields without its field arrays", who);
+  return XF_OK;
+}
+
+// One field-aware FM update: the two Pulls (w gathered with the rows, the F k wide v rows
+// gathered), the forward, the gradient + both Pushes.  Both tables are marked written, as the
+// canonical step does.
+static int fm_field_aware_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
+                               void *stream) {
+  int k = 0;
+  XF_TRY(ffm_check(vt, b, ws, "xf_fm_step", &k));
+  const int F = ws->fm_fields, dim = F * k;
+  XF_TRY(xf_batch_upload(b, stream));
+  XF_TRY(fmc_check_values(b, "xf_fm_step"));
+  XF_TRY(ffm_check_arrays(b, "xf_fm_step"));
+  XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
+  XF_TRY(ffm_reserve(ws, b, dim));
+  ws->rec = ws->profiling && ws->step_no++ % xf_workspace::kProfileEvery == 0;
+  if (ws->rec) XF_TRY(ws_next_set(ws));
+  const xf_dev_batch &v = b->view;
+  ws->lastU = b->U;
+  ws->lastR = b->R;
+  XF_BEGIN();
+  XF_TRY(fm_resolve_rows(w, vt, b, ws, stream, true, nullptr));
+  const uint32_t *rows_w = v.U ? b->d_fm_rows[0] : ws->slots;
+  const uint32_t *rows_v = v.U ? b->d_fm_rows[1] : ws->slots2;
+  XF_END(kEvResolve);
+  if (v.U) XF_TRY(xf_table_gather_dev(vt, rows_v, v.U, ws->fmc_vu, stream));
+  XF_END(kEvGather);
+  XF_TRY(xf::ffm_forward(&v, k, F, ws->wu, ws->fmc_vu, b->d_xfg, ws->loss, nullptr,
+                         b->valued ? b->d_xval : nullptr, S(stream)));
+  XF_END(kEvForward);
+  if (v.U && v.R) {
+    xf::table_note_write(w);
+    xf::table_note_write(vt);
+    XF_TRY(xf::ffm_grad_update(w, vt, &v, F, rows_w, rows_v, ws->wu, ws->fmc_vu, b->d_xfg,
+                               b->d_coo_pos, ws->loss, ws->g, ws->fmc_hpart,
+                               b->valued ? b->d_xval : nullptr, S(stream)));
+  }
+  XF_END(kEvGrad);
+  if (ws->rec) ws->sets[ws->cur].pending = true;
+  return XF_OK;
+}
+
+// forward only: pulls (and so inserts) the keys, as the other forms' predict does
+static int fm_field_aware_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
+                                  float *pctr_out) {
+  int k = 0;
+  XF_TRY(ffm_check(vt, b, ws, "xf_fm_predict", &k));
+  const int F = ws->fm_fields;
+  XF_TRY(xf_batch_upload(b, nullptr));
+  XF_TRY(fmc_check_values(b, "xf_fm_predict"));
+  XF_TRY(ffm_check_arrays(b, "xf_fm_predict"));
+  XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
+  XF_TRY(ffm_reserve(ws, b, F * k));
+  const xf_dev_batch &v = b->view;
+  XF_TRY(xf_table_pull_dev(w, v.ukeys, v.U, ws->slots, ws->wu, nullptr));
+  XF_TRY(xf_table_resolve_dev(vt, v.ukeys, v.U, ws->slots2, nullptr));
+  XF_TRY(xf_table_gather_dev(vt, ws->slots2, v.U, ws->fmc_vu, nullptr));
+  XF_TRY(xf::ffm_forward(&v, k, F, ws->wu, ws->fmc_vu, b->d_xfg, ws->loss, ws->pctr,
+                         b->valued ? b->d_xval : nullptr, nullptr));
+  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(xf_table_check(w, nullptr));
+  return xf_table_check(vt, nullptr);
+}
+
 // ---- feature values, LR (kernels in xf_valued.hip): the w half of the canonical step on a
 // valued generic minibatch — Pull of the key list (rows kept with the minibatch for its
 // replays), forward over the CSR, gradient + Push over the gradient tiles
@@ -2265,6 +2401,7 @@ extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *
   XF_REQUIRE(w && vt && b && ws, "xf_fm_step: null argument");
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_fm_step: the w table must have dim 1");
   XF_REQUIRE(!b->local, "xf_fm_step: needs a minibatch with a key list (xf_batch_compile*)");
+  if (ws->fm_mode == XF_FM_FIELD_AWARE) return fm_field_aware_step(w, vt, b, ws, stream);
   if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_step(w, vt, b, ws, stream);
   XF_REQUIRE(!b->valued,
              "xf_fm_step: a minibatch with feature values (feature_values) needs fm_mode = "
@@ -2543,6 +2680,7 @@ extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
                              float *pctr_out) {
   XF_REQUIRE(w && vt && b && ws && pctr_out, "xf_fm_predict: null argument");
   XF_REQUIRE(!b->local, "xf_fm_predict: needs a minibatch with a key list (xf_batch_compile*)");
+  if (ws->fm_mode == XF_FM_FIELD_AWARE) return fm_field_aware_predict(w, vt, b, ws, pctr_out);
   if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_predict(w, vt, b, ws, pctr_out);
   XF_REQUIRE(!b->valued,
              "xf_fm_predict: a minibatch with feature values (feature_values) needs fm_mode = "

@@ -214,6 +214,7 @@ struct xf_sharded {
   xf_workspace *ws = nullptr;  // world 1: the fused step's scratch
   int parity_mode = XF_PARITY_EXACT_SUMS;  // (what xf_sharded_set_parity last set)
   int fm_mode = XF_FM_REFERENCE;           // (what xf_sharded_set_fm_mode last set)
+  int fm_fields = 0;                       // (what xf_sharded_set_fm_fields last set)
   uint64_t seen_upper = 0;     // world 1: host-side upper bound on the keys in the table
   Dev<double> partial;         // LR forward scratch
   // the owner-compute compile's staging: the worker's nonzeros grouped by owner (sent from
@@ -1537,8 +1538,8 @@ static int valued_trainer_check(const xf_sharded *st, const char *who) {
   XF_REQUIRE(st->world == 1 && st->fused && st->ws,
              "%s: feature values (feature_values) run on one worker only (world %d)", who,
              st->world);
-  XF_REQUIRE(st->cfg.model == 0 || st->fm_mode == XF_FM_CANONICAL,
-             "%s: feature values (feature_values) with FM need fm_mode = canonical "
+  XF_REQUIRE(st->cfg.model == 0 || st->fm_mode != XF_FM_REFERENCE,
+             "%s: feature values (feature_values) with FM need fm_mode = canonical or field_aware "
              "(xf_sharded_set_fm_mode)", who);
   XF_REQUIRE(st->parity_mode == XF_PARITY_EXACT_SUMS,
              "%s: feature values (feature_values) have no reference-order parity mode", who);
@@ -1593,6 +1594,75 @@ extern "C" int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out,
   } guard{b};
   b->owner = st;
   XF_TRY(xf_batch_compile_valued_dev(&b->b, d_keys, d_vals, d_rowptr, d_labels, R, NNZ, st->main));
+  XF_TRY(fused_room(st, b));
+  guard.b = nullptr;
+  *out = b;
+  return XF_OK;
+}
+
+// Fields: a fielded minibatch always takes the generic build and steps on a one-rank trainer in
+// the field-aware form
+static int fielded_trainer_check(const xf_sharded *st, bool valued, const char *who) {
+  XF_REQUIRE(st->world == 1 && st->fused && st->ws,
+             "%s: field-aware FM runs on one worker only (world %d)", who, st->world);
+  XF_REQUIRE(st->cfg.model == 1 && st->fm_mode == XF_FM_FIELD_AWARE,
+             "%s: a minibatch with fields is for fm_mode = field_aware (xf_sharded_set_fm_fields, "
+             "xf_sharded_set_fm_mode)", who);
+  if (valued) XF_TRY(valued_trainer_check(st, who));
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_compile_fielded(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
+                                          const uint64_t *keys, const int32_t *fgid,
+                                          const float *vals, const int32_t *labels,
+                                          size_t row_begin, size_t row_end, int keep) {
+  (void)keep;  // (the generic minibatch is replayable as it is)
+  XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
+             "xf_sharded_compile_fielded: bad argument");
+  XF_ALIVE(st);
+  XF_TRY(fielded_trainer_check(st, vals != nullptr, "xf_sharded_compile_fielded"));
+  xf_sbatch *b = new xf_sbatch;
+  struct Guard {
+    xf_sbatch *b;
+    ~Guard() {
+      if (b) xf_sbatch_free(b);
+    }
+  } guard{b};
+  b->owner = st;
+  if (st->cfg.host_key_build)
+    XF_TRY(xf_batch_compile_fielded(&b->b, rowptr, keys, fgid, vals, labels, row_begin, row_end,
+                                    st->fm_fields));
+  else
+    XF_TRY(xf_batch_compile_fielded_gpu(&b->b, rowptr, keys, fgid, vals, labels, row_begin,
+                                        row_end, st->fm_fields, st->main));
+  XF_TRY(fused_room(st, b));
+  guard.b = nullptr;
+  *out = b;
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_compile_fielded_dev(xf_sharded *st, xf_sbatch **out,
+                                              const uint64_t *d_keys, const int32_t *d_fgid,
+                                              const float *d_vals, const uint32_t *d_rowptr,
+                                              const int32_t *d_labels, uint32_t R, uint32_t NNZ,
+                                              int keep) {
+  (void)keep;
+  XF_REQUIRE(st && out && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || (d_keys && d_fgid)),
+             "xf_sharded_compile_fielded_dev: null argument");
+  XF_ALIVE(st);
+  XF_TRY(fielded_trainer_check(st, d_vals != nullptr, "xf_sharded_compile_fielded_dev"));
+  XF_REQUIRE(!st->cfg.host_key_build, "xf_sharded_compile_fielded_dev: the trainer builds its "
+             "keys on the host (host_key_build): hand it host arrays");
+  xf_sbatch *b = new xf_sbatch;
+  struct Guard {
+    xf_sbatch *b;
+    ~Guard() {
+      if (b) xf_sbatch_free(b);
+    }
+  } guard{b};
+  b->owner = st;
+  XF_TRY(xf_batch_compile_fielded_dev(&b->b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ,
+                                      st->fm_fields, st->main));
   XF_TRY(fused_room(st, b));
   guard.b = nullptr;
   *out = b;
@@ -1844,12 +1914,22 @@ extern "C" int xf_sharded_set_parity(xf_sharded *st, int mode) {
 
 extern "C" int xf_sharded_set_fm_mode(xf_sharded *st, int mode) {
   XF_REQUIRE(st, "xf_sharded_set_fm_mode: null trainer");
-  XF_REQUIRE(mode == XF_FM_REFERENCE || mode == XF_FM_CANONICAL,
-             "xf_sharded_set_fm_mode: mode must be XF_FM_REFERENCE (0) or XF_FM_CANONICAL (1)");
+  XF_REQUIRE(mode == XF_FM_REFERENCE || mode == XF_FM_CANONICAL || mode == XF_FM_FIELD_AWARE,
+             "xf_sharded_set_fm_mode: mode must be XF_FM_REFERENCE (0), XF_FM_CANONICAL (1) or "
+             "XF_FM_FIELD_AWARE (2)");
   XF_REQUIRE(st->cfg.model == 1 && st->tv, "xf_sharded_set_fm_mode: not an FM trainer");
   XF_REQUIRE(st->world == 1 && st->fused && st->ws,
-             "xf_sharded_set_fm_mode: canonical FM runs on one rank only (world %d): the "
-             "exchanges of several ranks carry the reference form's row sums", st->world);
+             "xf_sharded_set_fm_mode: canonical and field-aware FM run on one rank only (world "
+             "%d): the exchanges of several ranks carry the reference form's row sums", st->world);
+  if (mode == XF_FM_FIELD_AWARE) {
+    XF_REQUIRE(st->fm_fields, "xf_sharded_set_fm_mode: field-aware FM needs its number of fields "
+               "first (xf_sharded_set_fm_fields)");
+    XF_REQUIRE(st->cfg.k % st->fm_fields == 0 && st->cfg.k <= 4096,
+               "xf_sharded_set_fm_mode: the v rows' width (%d) is not fields (%d) x k with "
+               "fields x k <= 4096", (int)st->cfg.k, st->fm_fields);
+    XF_REQUIRE(st->parity_mode == XF_PARITY_EXACT_SUMS,
+               "xf_sharded_set_fm_mode: field-aware FM has no reference-order parity mode");
+  }
   uint64_t nw = 0, nv = 0;
   XF_TRY(xf_table_size(st->tw, &nw));
   XF_TRY(xf_table_size(st->tv, &nv));
@@ -1860,11 +1940,22 @@ extern "C" int xf_sharded_set_fm_mode(xf_sharded *st, int mode) {
   // canonical: hash-normal factors for both optimizers (SGD's constant init would give every
   // factor of a key the same gradient forever); the reference form keeps sgd.h:67-72
   if (st->cfg.optimizer == XF_OPT_SGD) {
-    if (mode == XF_FM_CANONICAL) xf::table_set_init(st->tv, XF_INIT_HASHNORM, 0.0f, st->cfg.seed);
+    if (mode != XF_FM_REFERENCE) xf::table_set_init(st->tv, XF_INIT_HASHNORM, 0.0f, st->cfg.seed);
     else
       xf::table_set_init(st->tv, XF_INIT_CONST, 0.001f, 0);
   }
   st->fm_mode = mode;
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_set_fm_fields(xf_sharded *st, int fields) {
+  XF_REQUIRE(st, "xf_sharded_set_fm_fields: null trainer");
+  XF_REQUIRE(st->cfg.model == 1 && st->tv && st->ws, "xf_sharded_set_fm_fields: not a one-rank FM trainer");
+  XF_REQUIRE(st->fm_mode != XF_FM_FIELD_AWARE,
+             "xf_sharded_set_fm_fields: the trainer runs field-aware FM already: set the fields "
+             "before the form");
+  XF_TRY(xf_workspace_fm_fields(st->ws, fields));
+  st->fm_fields = fields;
   return XF_OK;
 }
 

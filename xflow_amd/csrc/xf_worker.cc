@@ -87,7 +87,7 @@ int Worker::create_tables() {
   xf_sharded_config_default(&c);
   c.model = model_;
   c.optimizer = optimizer;
-  c.k = v_dim_;
+  c.k = v_width();  // (field_aware: fields x k)
   c.schedule = schedule;
   c.capacity = capacity;
   c.seed = seed;
@@ -100,6 +100,7 @@ int Worker::create_tables() {
   c.update_rule = update_rule;
   XF_TRY(xf_sharded_create(&sharded_, group_, &c));
   if (parity != XF_PARITY_EXACT_SUMS) XF_TRY(xf_sharded_set_parity(sharded_, parity));
+  if (fm_mode == XF_FM_FIELD_AWARE) XF_TRY(xf_sharded_set_fm_fields(sharded_, fields));
   if (fm_mode != XF_FM_REFERENCE) XF_TRY(xf_sharded_set_fm_mode(sharded_, fm_mode));
   XF_TRY(xf_sharded_tables(sharded_, &table_w_, &table_v_));
   // One update() and one predict of a two-row minibatch on a private single-shard trainer: the
@@ -116,8 +117,14 @@ int Worker::create_tables() {
     float p[2];
     xf_sbatch *b = nullptr;
     const float vals[4] = {1.0f, 0.5f, 0.25f, 2.0f};
-    int rc = fm_mode != XF_FM_REFERENCE ? xf_sharded_set_fm_mode(warm, fm_mode) : XF_OK;
-    if (rc == XF_OK)
+    const int32_t fg[4] = {0, fields - 1, 0, fields - 1};
+    const bool ffm = fm_mode == XF_FM_FIELD_AWARE;
+    int rc = ffm ? xf_sharded_set_fm_fields(warm, fields) : XF_OK;
+    if (rc == XF_OK && fm_mode != XF_FM_REFERENCE) rc = xf_sharded_set_fm_mode(warm, fm_mode);
+    if (rc == XF_OK && ffm)
+      rc = xf_sharded_compile_fielded(warm, &b, rp, keys, fg, feature_values ? vals : nullptr, lab,
+                                      0, 2, 1);
+    else if (rc == XF_OK)
       rc = feature_values ? xf_sharded_compile_valued(warm, &b, rp, keys, vals, lab, 0, 2, 1)
                           : xf_sharded_compile(warm, &b, rp, keys, lab, 0, 2, 1);
     if (rc == XF_OK) rc = xf_sharded_step(warm, b);
@@ -211,7 +218,7 @@ int Worker::batch_training() {
     const float zero = 0.0f;
     XF_TRY(xf_table_push(table_w_, &key0, 1, &zero));
     if (model_ == 1) {
-      std::vector<float> zv(v_dim_, 0.0f);
+      std::vector<float> zv(v_width(), 0.0f);
       XF_TRY(xf_table_push(table_v_, &key0, 1, zv.data()));
     }
   }
@@ -273,6 +280,7 @@ int Worker::batch_training() {
         size_t rows = 0, nnz = 0;
         const uint64_t *rowptr = nullptr, *keys = nullptr;
         const int32_t *labels = nullptr;
+        const int32_t *fgid = nullptr;  // (fm_mode = field_aware)
         const float *vals = nullptr;  // (feature_values)
         int rc = XF_OK;
         std::string err;
@@ -304,8 +312,7 @@ int Worker::batch_training() {
             if (stop) return;
           }
           Parsed &p = slot[k];
-          const int32_t *fgid = nullptr;
-          p.rc = xf_reader_next_into(rd, p.blk, &p.rows, &p.nnz, &p.rowptr, &p.keys, &fgid,
+          p.rc = xf_reader_next_into(rd, p.blk, &p.rows, &p.nnz, &p.rowptr, &p.keys, &p.fgid,
                                      &p.labels);
           if (p.rc == XF_OK && feature_values) p.rc = xf_block_values(p.blk, &p.vals);
           if (p.rc != XF_OK) p.err = xf_last_error();  // the message is thread-local
@@ -348,7 +355,11 @@ int Worker::batch_training() {
           xf_sbatch *b = nullptr;
           const double tc0 = now_s();
           // a rank without rows of its own still takes part in the (collective) step
-          if (feature_values)  // (one worker: a block without rows ended the loop above)
+          if (fm_mode == XF_FM_FIELD_AWARE)  // (one worker, as with feature values)
+            rc = xf_sharded_compile_fielded(sharded_, &b, p->rowptr, p->keys, p->fgid,
+                                            feature_values ? p->vals : nullptr, p->labels, start,
+                                            end, keep);
+          else if (feature_values)  // (one worker: a block without rows ended the loop above)
             rc = xf_sharded_compile_valued(sharded_, &b, p->rowptr, p->keys, p->vals, p->labels,
                                            start, end, keep);
           else if (end > start)
@@ -650,7 +661,10 @@ int Worker::predict(int rank, int block, bool reader) {
       const size_t start = i * thread_size, end = (i + 1) * thread_size;
       if (end == start && world <= 1) continue;
       xf_sbatch *b = nullptr;
-      if (feature_values)
+      if (fm_mode == XF_FM_FIELD_AWARE)
+        XF_TRY(xf_sharded_compile_fielded(sharded_, &b, rowptr, keys, fgid,
+                                          feature_values ? vals : nullptr, labels, start, end, 0));
+      else if (feature_values)
         XF_TRY(xf_sharded_compile_valued(sharded_, &b, rowptr, keys, vals, labels, start, end, 0));
       else if (end > start) XF_TRY(xf_sharded_compile(sharded_, &b, rowptr, keys, labels, start, end, 0));
       else
@@ -697,10 +711,30 @@ int Worker::train() {
     XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS,
                "XFStartTrain: fm_mode=canonical has no parity=reference_order mode");
   }
+  if (fm_mode == XF_FM_FIELD_AWARE && !sharded_) {  // before any rendezvous of a group
+    XF_REQUIRE(model_ == 1, "XFStartTrain: fm_mode=field_aware needs model 1 (FM), not model %d",
+               model_);
+    XF_REQUIRE(fields >= 1 && fields <= 64,
+               "XFStartTrain: fm_mode=field_aware needs fields in 1 .. 64 (a key's touched fields "
+               "are one 64-bit mask), not fields=%d", fields);
+    XF_REQUIRE(v_dim_ >= 1 && (long)fields * v_dim_ <= 4096,
+               "XFStartTrain: fm_mode=field_aware: fields x k = %d x %d exceeds 4096, the widest "
+               "row of a table", fields, v_dim_);
+    int w = world;
+    if (w <= 0) {
+      const char *v = env_first({"WORLD_SIZE", "XF_WORLD", "DMLC_NUM_WORKER"});
+      w = v ? atoi(v) : 1;
+    }
+    XF_REQUIRE(w <= 1, "XFStartTrain: fm_mode=field_aware runs on one worker only (world %d)", w);
+    XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS,
+               "XFStartTrain: fm_mode=field_aware has no parity=reference_order mode");
+    XF_REQUIRE(!ingest_gpu, "XFStartTrain: fm_mode=field_aware together with ingest=gpu: the GPU "
+               "tokeniser hands out no fgid");
+  }
   if (feature_values && !sharded_) {  // next to the canonical mode's: before any rendezvous
-    XF_REQUIRE(model_ == 0 || fm_mode == XF_FM_CANONICAL,
-               "XFStartTrain: feature_values=on with model 1 (FM) needs fm_mode=canonical (the "
-               "reference form's pooled sums have no meaning with values)");
+    XF_REQUIRE(model_ == 0 || fm_mode != XF_FM_REFERENCE,
+               "XFStartTrain: feature_values=on with model 1 (FM) needs fm_mode=canonical or "
+               "field_aware (the reference form's pooled sums have no meaning with values)");
     int w = world;
     if (w <= 0) {
       const char *v = env_first({"WORLD_SIZE", "XF_WORLD", "DMLC_NUM_WORKER"});
@@ -737,7 +771,7 @@ int Worker::train() {
 int Worker::save_model(const char *path) {
   if (world > 1) return xf_sharded_save(sharded_, path);
   XF_TRY(xf_sharded_flush(sharded_));
-  XF_TRY(xf::model_write(path, table_w_, table_v_, v_dim_));
+  XF_TRY(xf::model_write(path, table_w_, table_v_, v_width()));
   // a sharded checkpoint saved under the same name earlier is stale now: without this its
   // manifest would send a later load to the old shard files
   (void)unlink((std::string(path) + ".manifest").c_str());
@@ -816,8 +850,13 @@ int Worker::set_param(const char *name, const char *value) {
     XF_REQUIRE(!sharded_, "XFSetParam: fm_mode cannot change after training started");
     if (!strcmp(value, "reference")) fm_mode = XF_FM_REFERENCE;
     else if (!strcmp(value, "canonical")) fm_mode = XF_FM_CANONICAL;
+    else if (!strcmp(value, "field_aware")) fm_mode = XF_FM_FIELD_AWARE;
     else
-      return xf::set_error(XF_EINVAL, "XFSetParam: fm_mode must be reference or canonical");
+      return xf::set_error(XF_EINVAL,
+                           "XFSetParam: fm_mode must be reference, canonical or field_aware");
+  } else if (n == "fields") {
+    XF_REQUIRE(!sharded_, "XFSetParam: fields cannot change after training started");
+    fields = atoi(value);
   } else if (n == "feature_values") {
     XF_REQUIRE(!sharded_, "XFSetParam: feature_values cannot change after training started");
     if (!strcmp(value, "on")) feature_values = true;

@@ -49,7 +49,9 @@ class Worker {
   int cache_batches = 1;
   bool key_build_gpu = true;  // key build of update() on the GPU (xf_batch_compile_gpu)
   int parity = 0;             // XF_PARITY_*: the forward's row sums (one worker)
-  int fm_mode = 0;            // XF_FM_*: FM's second-order term (canonical: one worker)
+  int fm_mode = 0;            // XF_FM_*: FM's second-order term (canonical, field_aware: one worker)
+  int fields = 0;             // fm_mode = field_aware: field-group ids, 1 .. 64 (fgid in [0, fields))
+  int v_width() const { return fm_mode == XF_FM_FIELD_AWARE ? fields * v_dim_ : v_dim_; }
   bool feature_values = false;  // a nonzero contributes x = val, not 1 (one worker)
   int update_rule = 0;        // XF_UPDATE_*: how an owner applies the workers' pushes of a step
   std::string pred_path;
