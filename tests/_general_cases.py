@@ -1,0 +1,167 @@
+"""Minibatch streams in general position, for tests/_general_checker.py.
+
+Row structure, keys, labels and fields are those of the exact tests' generators
+(tests/_valued_cases.py ragged / zipf, tests/_ffm_checker.py stream): heavy keys, heavy keys of
+several chunks, a key twice in a row, empty rows, rows of 331 nonzeros.  The VALUES are drawn
+anew — exp(N(0, 1)) as fp32 (full mantissas), negated with probability 0.3 nonzero by nonzero
+(signs mix inside a row, S[r,f] cancels), one in ten an exact zero, about 2 % scaled by 2^-20 and
+about 1 % by 2^5; the long-rows stream an eighth of that, for _ffm_checker.stream's reason — and
+the STATE is fresh: w zero, v hash-normal, STEPS steps whose keys overlap, so steps 2 .. see what
+FTRL and SGD really leave (L1 zeros, factors of any magnitude).
+
+Every minibatch is (rowptr, keys, fgid or None, values, labels)."""
+import numpy as np
+
+from oracle import pyoracle as O
+from tests import _ffm_checker as F
+from tests import _general_checker as G
+from tests import _valued_cases as Cs
+
+STEPS = 4
+OPTS = ("ftrl", "sgd")
+SEED = 7                # of the hash-normal init, the GPU tables' too
+
+# valued LR: (case)
+LR_CASES = ("ragged", "zipf_chunks")
+# valued canonical FM: (case, k) — k in {1, 4, 7, 16, 64, 80} x the three cases, thinned as
+# _ffm_checker.GRID is: every k and every case at least twice but k = 1 and 64, heavy keys with a
+# compile-time and with a runtime k, the chunked heavy keys with an odd k
+FM_GRID = (("ragged", 1), ("ragged", 4), ("ragged", 7), ("ragged", 16), ("ragged", 80),
+           ("zipf_heavy", 4), ("zipf_heavy", 64), ("zipf_heavy", 80),
+           ("zipf_chunks", 7), ("zipf_chunks", 16))
+# field-aware: (case, fields, k)
+FFM_GRID = (("ragged", 18, 4), ("ragged", 39, 7), ("ragged", 64, 16), ("ragged", 1, 8),
+            ("zipf_heavy", 18, 7), ("zipf_chunks", 18, 4), ("long_rows", 39, 4),
+            ("ragged", 3, 24), ("zipf_heavy", 3, 70))
+
+
+def values(rng, n, scale=1.0):
+    x = np.exp(rng.randn(n)).astype(np.float32)
+    x[rng.rand(n) < 0.3] *= np.float32(-1.0)
+    u = rng.rand(n)
+    x[u < 0.02] *= np.float32(2.0 ** -20)
+    x[(u >= 0.02) & (u < 0.03)] *= np.float32(32.0)
+    x[rng.rand(n) < 0.1] = 0.0
+    return (x * np.float32(scale)).astype(np.float32)
+
+
+def _structure(case, Fd, i):
+    """minibatch i of a case: (rowptr, keys, fgid or None, labels) of the exact tests' streams"""
+    if case == "long_rows":
+        rowptr, keys, fg, _, labels = F.stream(case, Fd, seed=i)[0]
+        return rowptr, keys, fg, labels
+    if case == "ragged":
+        rowptr, keys, _, labels = Cs.ragged(i)
+    elif case == "zipf_heavy":      # head keys beyond XF_HEAVY_SEG, every one in one chunk
+        rowptr, keys, _, labels = Cs.zipf(i, 400, 14, 3000)
+    elif case == "zipf_chunks":     # the head key spans several chunks of XF_TILE_NNZ
+        rowptr, keys, _, labels = Cs.zipf(i, 2500, 20, 5000)
+    else:
+        raise KeyError(case)
+    fg = F._fields_of(np.random.RandomState(7 + i), keys, Fd) if Fd else None
+    return rowptr, keys, fg, labels
+
+
+def stream(case, fields=0, steps=STEPS):
+    out = []
+    for i in range(steps):
+        rowptr, keys, fg, labels = _structure(case, fields, i)
+        rng = np.random.RandomState(5000 + i)
+        out.append((rowptr, keys, fg,
+                    values(rng, len(keys), 0.125 if case == "long_rows" else 1.0), labels))
+    return out
+
+
+def underflow_stream(fields=0):
+    """two ragged minibatches; the second is the underflow one: one row in ten carries values
+    2^-63 of the others' (v x near 2^-70: the squares fp32((v x)^2), fp32(S^2) and the pair
+    products land in fp32's denormal range and below it, an exact 0) or 2^-120 of them (w x,
+    loss x and v x themselves do).  Whole rows, not single values: a tiny addend beside a row sum
+    that sits half way between two fp32 values decides the rounding of S[r,f] in exact arithmetic
+    and is absorbed in fp64 — with single tiny values 5 to 17 of 3600 S were open, and no S may
+    be.  The tiny rows' keys occur in other rows too, so gw and gv mix both magnitudes."""
+    mbs = stream("ragged", fields, steps=2)
+    rowptr, keys, fg, vals, labels = mbs[1]
+    rng = np.random.RandomState(77)
+    u = rng.rand(len(labels))
+    scale = np.where(u < 0.05, 2.0 ** -63, np.where(u < 0.1, 2.0 ** -120, 1.0)).astype(np.float32)
+    vals = vals * np.repeat(scale, np.diff(rowptr.astype(np.int64)))
+    mbs[1] = (rowptr, keys, fg, vals.astype(np.float32), labels)
+    return mbs
+
+
+def stores(form, opt, fields, k, seed=SEED):
+    """fresh oracle stores: w from zero, v (k or fields k wide) hash-normal"""
+    o = O.OPT_FTRL if opt == "ftrl" else O.OPT_SGD
+    ws = O.Store(o, 1)
+    if form == "lr":
+        return ws, None
+    return ws, O.Store(o, (fields if form == "ffm" else 1) * k, O.INIT_HASHNORM, 0.0, seed)
+
+
+def binary(mbs):
+    return [(rp, keys, fg, None, labels) for rp, keys, fg, _, labels in mbs]
+
+
+# The seed of the hash-normal init per case, where SEED does not do.  long_rows: a 331-long row's
+# y2 is one sum of 218 460 products of either sign (n 2^-53 = 2.4e-11 of sum |a|, and sum |a| is
+# some hundred times |y2|, beside fp32's half step of 3e-8 of |y2|): such a row is open with
+# a probability of tens of per cent whatever the scale, and 12 of a minibatch's 40 rows are long.
+# Over the four runs (both optimizers, binary and valued) seeds 7, 9 .. 13 give up to 3 .. 5 open
+# y2 of 200, at or beyond the cap of 4; seed 8 gives 2, 1, 2, 2.
+INIT_SEED = {"long_rows": 8}
+
+
+def init_seed(case):
+    return INIT_SEED.get(case, SEED)
+
+
+def gpu_stream(form, case, fields):
+    """the stream of a GPU test: a case of the grids, or 'underflow'"""
+    return underflow_stream(fields) if case == "underflow" else stream(case, fields)
+
+
+def run_cpu(form, opt, fields, k, mbs, judge, seed=SEED):
+    """the checker alone, following its low candidates: -> the Run and the steps' results"""
+    ws, vs = stores(form, opt, fields, k, seed)
+    run = G.Run(form, ws, vs, judge, fields)
+    steps = [run.step(mb) for mb in mbs]
+    run.predict(mbs[-1])
+    return run, steps
+
+
+# the worker end to end on the golden sample files, from fresh tables, FTRL included
+E2E_EPOCHS = 2
+
+
+def run_files(form, opt, fields, k, train_path, test_path, judge, valued=True,
+              block_bytes=2 << 20):
+    """XFlow(model=1, core_num=1) in the canonical ('fm') or the field-aware ('ffm') form: the
+    key-0 init push, one update per block and epoch, then the test file block by block (a block's
+    Pull inserts its unseen keys) -> the stores, (labels, pctr), the metrics.  The low candidates
+    throughout: a caller that compares anything with these asserts judge.open_count() == 0
+    first, after which they are the only candidates."""
+    ws, vs = stores(form, opt, fields, k, seed=0)           # the worker's seed: 0
+    ws.push(np.zeros(1, np.uint64), np.zeros(1, np.float32))
+    vs.push(np.zeros(1, np.uint64), np.zeros(vs.dim, np.float32))
+    run = G.Run(form, ws, vs, judge, fields)
+
+    def blocks(path):
+        if form == "ffm":
+            return [(rp, keys, fg, vals, labels)
+                    for rp, keys, fg, labels, vals in F.file_blocks(path, block_bytes, valued)]
+        assert valued
+        from tests import _valued_checker as V
+        return [(rp, keys, None, vals, labels)
+                for rp, keys, labels, vals in V.file_blocks(path, block_bytes)]
+
+    train = blocks(train_path)
+    for _ in range(E2E_EPOCHS):
+        for mb in train:
+            run.step(mb)
+    labels_all, pctr_all = [], []
+    for mb in blocks(test_path):
+        pctr_all.append(run.predict(mb)[:, 0])
+        labels_all.append(mb[4])
+    lab, p = np.concatenate(labels_all), np.concatenate(pctr_all)
+    return ws, vs, lab, p, O.auc_logloss(lab, p)

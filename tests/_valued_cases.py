@@ -143,7 +143,8 @@ def run_checker(model, opt, k, mbs, audit):
 # first step leaves factors of any magnitude (w = -(z -+ l1) / (...) with z near l1) and the
 # sums of their squares are not (k = 4: 10 of 2400 row sums and 49 of 600 sums over the factors
 # depend on the order of their addends) — an input that cannot meet the condition, so not one
-# the checker may judge.
+# this checker may judge; tests/test_gpu_values.py adds (1, "ftrl", 4) under the interval rule of
+# tests/_interval.py.
 E2E = ((0, "ftrl", 1), (0, "sgd", 1), (1, "sgd", 4))
 E2E_EPOCHS = 2
 

@@ -230,7 +230,8 @@ def test_golden_files_from_fresh_tables(valued):
     """fields = 18, k = 4, two epochs from fresh hash-normal tables: under SGD every sum is exact
     (what the worker test on the GPU relies on).  Under FTRL the y2 sums are not: 27 of 600
     (binary) and 40 of 600 (valued) depend on the order of their addends, so FTRL is not a case
-    the worker test may judge."""
+    the worker test may judge under this audit (it judges it under the interval rule:
+    tests/test_general_position_cpu.py::test_golden_files_under_ftrl_have_no_open_sum)."""
     audit = []
     F.run_checker_files("sgd", TRAIN, TEST, audit, valued)
     F.assert_exact(audit)

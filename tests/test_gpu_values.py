@@ -13,6 +13,8 @@ from oracle import pyoracle as O
 from xflow_amd import build, capi
 from xflow_amd.single import SingleGpuTrainer
 
+from . import _general_cases as GC
+from . import _interval as I
 from . import _valued_cases as Cs
 from . import _valued_checker as V
 
@@ -225,13 +227,23 @@ def test_sharded_one_rank_and_single_gpu_trainer(model, opt, k):
 
 
 # ------------------------------------------------------------------- the worker, the CLI
-@pytest.mark.parametrize("model,opt,k", Cs.E2E)
+@pytest.mark.parametrize("model,opt,k", Cs.E2E + ((1, "ftrl", 4),))
 def test_worker_end_to_end(sample_prefixes, tmp_path, model, opt, k):
+    """Cs.E2E: every sum of the checker is exact (assert_exact).  FM + FTRL from fresh tables
+    fails that audit; there the interval rule of tests/_interval.py pins every sum to one fp32
+    value — no open sum, asserted here and in tests/test_general_position_cpu.py — and the
+    comparison is as exact as for the others"""
     tr, te = sample_prefixes
-    audit = []
-    sw, sv, lab, p, (ll, auc, tp, fp) = Cs.run_checker_files(model, opt, k, tr + "-00000",
-                                                             te + "-00000", audit)
-    V.assert_exact(audit)
+    if (model, opt) == (1, "ftrl"):
+        judge = I.Judge()
+        sw, sv, lab, p, (ll, auc, tp, fp) = GC.run_files("fm", opt, 0, k, tr + "-00000",
+                                                         te + "-00000", judge)
+        assert judge.open_count() == 0, judge.table()
+    else:
+        audit = []
+        sw, sv, lab, p, (ll, auc, tp, fp) = Cs.run_checker_files(model, opt, k, tr + "-00000",
+                                                                 te + "-00000", audit)
+        V.assert_exact(audit)
     extra = {"fm_mode": "canonical"} if model == 1 else {}
     pred = str(tmp_path / "p.txt")
     x = capi.XFlow(tr, te, model=model, epochs=Cs.E2E_EPOCHS, k=k, optimizer=opt, capacity=4096,
