@@ -92,8 +92,8 @@ int xf_reader_next_into(xf_reader *r, xf_block *blk, size_t *rows_out, size_t *n
  * not finite, is XF_EPARSE.  Labels, keys, block boundaries and row order do not change.  The
  * values run beside the keys (nnz floats): xf_reader_values for the reader-owned arrays of
  * xf_reader_next, xf_block_values for a block of xf_reader_next_into / xf_reader_parse_text.  The
- * block cache and the GPU tokeniser carry no values: a reader opened with xf_reader_open_cached
- * refuses (XF_EINVAL). */
+ * block cache carries no values: a reader opened with xf_reader_open_cached refuses (XF_EINVAL).
+ * (The GPU tokeniser carries them after xf_ingest_set_fields.) */
 int xf_reader_set_values(xf_reader *r, int on);
 int xf_reader_values(xf_reader *r, const float **vals);
 int xf_block_values(xf_block *blk, const float **vals);
@@ -136,6 +136,17 @@ int xf_ingest_upload(xf_ingest *g, size_t len, void *stream);
 int xf_ingest_block(xf_ingest *g, const char *text, size_t len, void *stream,
                     const uint64_t **d_keys, const uint32_t **d_rowptr, const int32_t **d_labels,
                     uint32_t *rows, uint32_t *nnz, int *ok);
+/* The tokeniser also reads field0 as the token's fgid (want_fgid) and / or the third field as its
+ * feature value (want_vals), for the blocks that follow; the arrays are allocated on first use.
+ * The common shape narrows to what the host parser converts without atof: field0 of 1 .. 9
+ * decimal digits; a third field — up to the blank or the end of the line, one CR before the
+ * newline dropped — that is empty (+0) or ['-'] digits ['.' digits] with 1 .. 15 digits in all,
+ * value = (float)(+-(double)digits / 10^fraction digits), bit for bit xf_reader_set_values'.
+ * Every other token (exponents, '+', nan, inf, a further colon, ...) hands its block back.
+ * xf_ingest_fields: d_fgid [nnz] i32, d_vals [nnz] f32 of the last accepted block, beside d_keys,
+ * valid until the next xf_ingest_block; NULL for an array that was not asked for. */
+int xf_ingest_set_fields(xf_ingest *g, int want_fgid, int want_vals);
+int xf_ingest_fields(xf_ingest *g, const int32_t **d_fgid, const float **d_vals);
 
 /* device memory -> host, blocking (the tokeniser's arrays in tests and small tools) */
 int xf_copy_to_host(void *dst, const void *d_src, size_t bytes);
@@ -774,7 +785,8 @@ int XFDestroy(void **h);
  *        block_cache(0|1) block_cache_dir (binarized block cache of the text files)
  *        ingest(host|gpu: the text of a block tokenised and hashed on the GPU, xf_ingest_*;
  *        blocks that are not of the common shape go to the host parser; core_num 1, no block
- *        cache).  XFGetMetric: ... blocks_gpu blocks_host (how the blocks were parsed) */
+ *        cache.  gpu_fields: the same, and the tokeniser also reads fgid and the feature value
+ *        when fm_mode=field_aware / feature_values=on need them, xf_ingest_set_fields).  XFGetMetric: ... blocks_gpu blocks_host (how the blocks were parsed) */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

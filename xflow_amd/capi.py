@@ -89,6 +89,8 @@ SIGNATURES = {
     "xf_ingest_block": (C.c_int, [vp, vp, C.c_size_t, vp, C.POINTER(vp), C.POINTER(vp),
                                   C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                   C.POINTER(C.c_int)]),
+    "xf_ingest_set_fields": (C.c_int, [vp, C.c_int, C.c_int]),
+    "xf_ingest_fields": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp)]),
     "xf_reader_next": (C.c_int, [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                  C.POINTER(u64p), C.POINTER(u64p), C.POINTER(i32p),
                                  C.POINTER(i32p)]),
@@ -423,9 +425,10 @@ def read_text_blocks(path, cap_bytes):
         L.xf_reader_close(r)
 
 
-def parse_text_block(text, cap_bytes=1 << 26):
+def parse_text_block(text, cap_bytes=1 << 26, values=False):
     """(rowptr, keys, fgid, labels) of one block's text through the HOST parser
-    (xf_reader_parse_text); raises XFError where the host parser rejects the block."""
+    (xf_reader_parse_text); raises XFError where the host parser rejects the block.
+    values=True: the feature values (float32, beside keys) as a fifth array."""
     import tempfile
     L = lib()
     r, blk = vp(), vp()
@@ -435,23 +438,31 @@ def parse_text_block(text, cap_bytes=1 << 26):
         check(L.xf_reader_open(C.byref(r), f.name.encode(), cap_bytes))
     check(L.xf_block_create(C.byref(blk)))
     try:
+        if values:
+            check(L.xf_reader_set_values(r, 1))
         rows, nnz = C.c_size_t(), C.c_size_t()
         rp, ks, fg, lb = u64p(), u64p(), i32p(), i32p()
         buf = C.create_string_buffer(text, len(text) + 16)
         check(L.xf_reader_parse_text(r, buf, len(text), blk, C.byref(rows), C.byref(nnz),
                                      C.byref(rp), C.byref(ks), C.byref(fg), C.byref(lb)))
         R, N = rows.value, nnz.value
-        return (np.ctypeslib.as_array(rp, (R + 1,)).copy(),
-                np.ctypeslib.as_array(ks, (max(N, 1),))[:N].copy(),
-                np.ctypeslib.as_array(fg, (max(N, 1),))[:N].copy(),
-                np.ctypeslib.as_array(lb, (max(R, 1),))[:R].copy())
+        out = (np.ctypeslib.as_array(rp, (R + 1,)).copy(),
+               np.ctypeslib.as_array(ks, (max(N, 1),))[:N].copy(),
+               np.ctypeslib.as_array(fg, (max(N, 1),))[:N].copy(),
+               np.ctypeslib.as_array(lb, (max(R, 1),))[:R].copy())
+        if values:
+            vs = f32p()
+            check(L.xf_block_values(blk, C.byref(vs)))
+            out += (np.ctypeslib.as_array(vs, (N,)).copy() if N else np.zeros(0, np.float32),)
+        return out
     finally:
         L.xf_block_destroy(blk)
         L.xf_reader_close(r)
 
 
 class Ingest:
-    """The GPU tokeniser (xf_ingest_*): text block -> device arrays (keys, rowptr, labels)."""
+    """The GPU tokeniser (xf_ingest_*): text block -> device arrays (keys, rowptr, labels; after
+    fields(): also fgid and the feature values)."""
 
     def __init__(self, max_text_bytes=1 << 26):
         self.h = vp()
@@ -482,6 +493,29 @@ class Ingest:
             if a.nbytes:
                 check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
         return True, rp, ks, lb
+
+    def fields(self, fgid=False, values=False):
+        """the blocks that follow: field0 read as fgid and / or the third field as the feature
+        value (xf_ingest_set_fields); tokens outside the two classes hand their block back"""
+        check(lib().xf_ingest_set_fields(self.h, 1 if fgid else 0, 1 if values else 0))
+        return self
+
+    def block_fields(self, text):
+        """(ok, rowptr, keys, labels, fgid, vals): block() with the arrays fields() asked for
+        (int32 / float32 beside keys; None for one that was not asked for, all None when the
+        block was handed back)"""
+        ok, R, N, dk, dr, dl = self.block_dev(text)
+        if not ok:
+            return False, None, None, None, None, None
+        dfg, dv = vp(), vp()
+        check(lib().xf_ingest_fields(self.h, C.byref(dfg), C.byref(dv)))
+        rp, ks, lb = np.zeros(R + 1, np.uint32), np.zeros(N, np.uint64), np.zeros(R, np.int32)
+        fg = np.zeros(N, np.int32) if dfg.value else None
+        vs = np.zeros(N, np.float32) if dv.value else None
+        for a, ptr in ((rp, dr), (ks, dk), (lb, dl), (fg, dfg.value), (vs, dv.value)):
+            if a is not None and a.nbytes:
+                check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
+        return True, rp, ks, lb, fg, vs
 
 
 class Batch:

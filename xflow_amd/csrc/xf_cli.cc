@@ -23,7 +23,9 @@ int main(int argc, char *argv[]) {
               << "field-aware FM (k factors per field, one worker; fgid in [0, N)): append "
                  "fm_mode=field_aware fields=N\n"
               << "feature values (x = val of fgid:fid:val instead of 1; LR, or FM with "
-                 "fm_mode=canonical or field_aware; one worker): append feature_values=on\n";
+                 "fm_mode=canonical or field_aware; one worker): append feature_values=on\n"
+              << "text tokenised on the GPU: append ingest=gpu (keys only) or ingest=gpu_fields "
+                 "(also fgid and val, for field_aware and feature_values)\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler

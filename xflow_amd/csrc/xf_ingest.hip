@@ -27,6 +27,19 @@
 //                 — first and second ':' — and its fid hashed; rowptr at the newlines, labels
 //                 at the line starts; the shape checks
 // Byte work, HBM-bound (text in once per pass, 8 bytes of key out per token), no MFMA.
+//
+// xf_ingest_set_fields: k_tok_emit<FG, VAL> also reads field0 (FG: the token's fgid) and the third
+// field (VAL: its feature value) and writes fgid[NNZ] / val[NNZ] beside the keys.  The common
+// shape narrows to what the host parser converts without atof, so that the results stay its own:
+//     FG   field0 = 1 .. 9 decimal digits (field_atof's and the one-pass token path's class)
+//     VAL  the third field — up to the next ' ' or '\n', ONE '\r' right before the '\n' dropped
+//          (the CR of a CR LF file: atof ignores it) — is empty (+0.0f) or ['-'] digits ['.' digits]
+//          with 1 .. 15 digits in all (hence at most 17 bytes): (float)(+-(double)m / 10^nf),
+//          field_value's arithmetic (xf_io.cc) — m and 10^nf exact doubles, one correctly rounded
+//          fp64 division, one round-to-nearest conversion (this file is built with
+//          -ffp-contract=off and without fast-math)
+// Every other token (a sign or '.' in field0, exponents, '+', nan, inf, hex, a further colon, a
+// lone '-' or '.', 16 digits, trailing bytes) raises the flag as any other defect does.
 #include <hip/hip_runtime.h>
 
 #include <string.h>
@@ -40,9 +53,19 @@ namespace {
 constexpr int kTok = 256;                   // threads per workgroup
 constexpr uint32_t kTokB = 16;              // bytes per thread and tile
 constexpr uint32_t kTile = kTok * kTokB;    // 4 KiB of text per tile
-constexpr uint32_t kHalo = 64;              // bytes read past a tile (a token's head)
 constexpr uint32_t kMaxField0 = 16, kMaxFid = 32;
+// the third field as the kernel reads it: 17 bytes of value, the CR, and the byte that ends it
+constexpr uint32_t kMaxVal = 17, kValScan = kMaxVal + 2;
+// bytes read past a tile: a token that starts behind the tile's last byte — field0 ':' fid ':'
+// val '\r' and the terminator, 1 + 16 + 1 + 32 + 1 + 19 = 70 — in whole 16-byte loads
+constexpr uint32_t kHalo = 80;
+static_assert(kHalo % 16 == 0 && kHalo >= 1 + kMaxField0 + 1 + kMaxFid + 1 + kValScan,
+              "the halo holds a whole token head and value");
 constexpr uint32_t kMaxWG = 1024;
+
+// 10^nf, nf = 0 .. 15: exact doubles (field_value's table, xf_io.cc)
+__constant__ double kPow10[16] = {1e0, 1e1, 1e2,  1e3,  1e4,  1e5,  1e6,  1e7,
+                                  1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15};
 
 struct TokCounts {
   uint32_t rows, nnz, bad, pad;
@@ -171,11 +194,15 @@ k_tok_scan(uint2 *__restrict__ wgcnt, uint32_t nwg, uint32_t cap_rows, uint32_t 
   }
 }
 
+// FG: field0 -> fgid[sp]; VAL: the third field -> val[sp] (the classes above).  <false, false>
+// reads neither field and takes no pointer for them.
+template <bool FG, bool VAL>
 __global__ void __launch_bounds__(kTok)
 k_tok_emit(const uint8_t *__restrict__ text, uint32_t n, uint32_t span,
            const uint2 *__restrict__ wgbase, uint32_t cap_rows, uint32_t cap_nnz,
            uint64_t *__restrict__ keys, uint32_t *__restrict__ rowptr,
-           int32_t *__restrict__ labels, TokCounts *__restrict__ out) {
+           int32_t *__restrict__ labels, int32_t *__restrict__ fgid, float *__restrict__ val,
+           TokCounts *__restrict__ out) {
   // [16 bytes: the two bytes before the tile at their end | the tile | the halo]
   __shared__ __attribute__((aligned(16))) uint8_t lt[16 + kTile + kHalo];
   __shared__ uint32_t wsum[kTok / 64];
@@ -252,6 +279,7 @@ k_tok_emit(const uint8_t *__restrict__ text, uint32_t n, uint32_t span,
         // before the token ends: load_data_from_disk.cc:147-153)
         uint32_t j = (uint32_t)i + 1, c1 = 0, c2 = 0;
         const uint32_t stop = j + kMaxField0 + 1 + kMaxFid + 1;  // < kTile + kHalo
+        uint32_t fg = 0, fg_bad = 0;  // FG: field0 as a decimal integer; a byte that is no digit
         for (; j < stop; ++j) {
           const uint32_t x = T[j];
           if (x == ' ' || x == '\n') break;
@@ -261,11 +289,53 @@ k_tok_emit(const uint8_t *__restrict__ text, uint32_t n, uint32_t span,
               c2 = j;
               break;
             }
+          } else if (FG && !c1) {
+            const uint32_t d = x - '0';
+            fg_bad |= d > 9u ? 1u : 0u;
+            fg = fg * 10u + d;  // (wraps past 9 digits: rejected by the length below)
           }
         }
-        const bool ok = c1 && c2 && c1 - ((uint32_t)i + 1) <= kMaxField0 && c2 - c1 - 1 <= kMaxFid;
+        bool ok = c1 && c2 && c1 - ((uint32_t)i + 1) <= kMaxField0 && c2 - c1 - 1 <= kMaxFid;
+        if (FG) ok = ok && !fg_bad && c1 - ((uint32_t)i + 1) >= 1 && c1 - ((uint32_t)i + 1) <= 9;
+        float v = 0.0f;
+        if (VAL && ok) {
+          // ['-'] digits ['.' digits] up to ' ' | '\n' | "\r\n", all inside the halo: c2 + 1 is
+          // at most 51 bytes behind the separator, the last byte read (q + 1) 70
+          uint32_t q = c2 + 1, nd = 0, nf = 0, dot = 0, junk = 0, ended = 0;
+          const uint32_t vstop = q + kValScan;
+          const uint32_t neg = T[q] == '-' ? 1u : 0u;
+          q += neg;
+          uint64_t m = 0;
+          for (; q < vstop; ++q) {
+            const uint32_t x = T[q];
+            if (x == ' ' || x == '\n' || (x == '\r' && T[q + 1] == '\n')) {
+              ended = 1;
+              break;
+            }
+            const uint32_t d = x - '0';
+            if (d <= 9u) {
+              m = m * 10u + d;  // (19 digits at most: no wrap; more than 15 are rejected)
+              ++nd;
+              nf += dot;
+            } else if (x == '.' && !dot) {
+              dot = 1;
+            } else {
+              junk = 1;
+            }
+          }
+          // the empty field is +0; a lone '-' or '.' is atof's business
+          ok = ended && !junk && (nd ? nd <= 15u : !(neg | dot));
+          if (ok) {
+            const double dv = (double)m / kPow10[nf];
+            v = (float)(neg ? -dv : dv);  // ("-0": -0.0f, as on the host)
+          }
+        }
         bad |= ok ? 0u : 1u;
-        if (ok && sp < cap_nnz) keys[sp] = hash_lds(T + c1 + 1, c2 - c1 - 1);
+        if (ok && sp < cap_nnz) {
+          keys[sp] = hash_lds(T + c1 + 1, c2 - c1 - 1);
+          if (FG) fgid[sp] = (int32_t)fg;
+          if (VAL) val[sp] = v;
+        }
         ++sp;
       }
       if (ch == '\n') {
@@ -293,6 +363,9 @@ struct xf_ingest {
   uint8_t *d_text = nullptr;    // [cap_text rounded up + kTile + kHalo]
   uint8_t *h_text = nullptr;    // pinned staging of the same size
   uint64_t *d_keys = nullptr;
+  int32_t *d_fgid = nullptr;    // [cap_nnz], xf_ingest_set_fields: allocated on first use
+  float *d_vals = nullptr;      // [cap_nnz], the same
+  bool want_fgid = false, want_vals = false;  // the instantiation of k_tok_emit
   uint32_t *d_rowptr = nullptr;
   int32_t *d_labels = nullptr;
   uint2 *d_wgcnt = nullptr;
@@ -305,6 +378,8 @@ extern "C" int xf_ingest_destroy(xf_ingest *g) {
   if (g->d_text) (void)hipFree(g->d_text);
   if (g->h_text) (void)hipHostFree(g->h_text);
   if (g->d_keys) (void)hipFree(g->d_keys);
+  if (g->d_fgid) (void)hipFree(g->d_fgid);
+  if (g->d_vals) (void)hipFree(g->d_vals);
   if (g->d_rowptr) (void)hipFree(g->d_rowptr);
   if (g->d_labels) (void)hipFree(g->d_labels);
   if (g->d_wgcnt) (void)hipFree(g->d_wgcnt);
@@ -425,15 +500,40 @@ extern "C" int xf_ingest_block(xf_ingest *g, const char *text, size_t len, void 
                      g->d_wgcnt);
   hipLaunchKernelGGL(k_tok_scan, dim3(1), dim3(kMaxWG), 0, s, g->d_wgcnt, nwg, g->cap_rows,
                      g->cap_nnz, g->d_counts);
-  hipLaunchKernelGGL(k_tok_emit, dim3(nwg), dim3(kTok), 0, s, g->d_text, (uint32_t)n, span,
+  auto emit = g->want_fgid ? (g->want_vals ? k_tok_emit<true, true> : k_tok_emit<true, false>)
+                            : (g->want_vals ? k_tok_emit<false, true> : k_tok_emit<false, false>);
+  hipLaunchKernelGGL(emit, dim3(nwg), dim3(kTok), 0, s, g->d_text, (uint32_t)n, span,
                      (const uint2 *)g->d_wgcnt, g->cap_rows, g->cap_nnz, g->d_keys, g->d_rowptr,
-                     g->d_labels, g->d_counts);
+                     g->d_labels, g->want_fgid ? g->d_fgid : nullptr,
+                     g->want_vals ? g->d_vals : nullptr, g->d_counts);
   XF_HIP(hipGetLastError());
   XF_HIP(hipMemcpyAsync(g->h_counts, g->d_counts, sizeof(TokCounts), hipMemcpyDeviceToHost, s));
   XF_HIP(hipStreamSynchronize(s));
   *ok = g->h_counts->bad ? 0 : 1;
   *rows = g->h_counts->rows;
   *nnz = g->h_counts->nnz;
+  return XF_OK;
+}
+
+// Which fields of a token the next blocks' tokeniser reads beside the fid: field0 as fgid
+// (want_fgid) and the third field as the feature value (want_vals) — the classes at the top of
+// this file; a token outside them hands its block back.  Between blocks; the arrays are allocated
+// on first use.  Neither: the tokeniser as xf_ingest_create leaves it.
+extern "C" int xf_ingest_set_fields(xf_ingest *g, int want_fgid, int want_vals) {
+  XF_REQUIRE(g, "xf_ingest_set_fields: null argument");
+  if (want_fgid && !g->d_fgid) XF_HIP(hipMalloc((void **)&g->d_fgid, (size_t)g->cap_nnz * 4));
+  if (want_vals && !g->d_vals) XF_HIP(hipMalloc((void **)&g->d_vals, (size_t)g->cap_nnz * 4));
+  g->want_fgid = want_fgid != 0;
+  g->want_vals = want_vals != 0;
+  return XF_OK;
+}
+
+// d_fgid [nnz] i32, d_vals [nnz] f32 of the last accepted block, beside its keys: valid until the
+// next xf_ingest_block; null for an array xf_ingest_set_fields did not ask for
+extern "C" int xf_ingest_fields(xf_ingest *g, const int32_t **d_fgid, const float **d_vals) {
+  XF_REQUIRE(g, "xf_ingest_fields: null argument");
+  if (d_fgid) *d_fgid = g->want_fgid ? g->d_fgid : nullptr;
+  if (d_vals) *d_vals = g->want_vals ? g->d_vals : nullptr;
   return XF_OK;
 }
 

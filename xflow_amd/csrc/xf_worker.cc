@@ -136,18 +136,27 @@ int Worker::create_tables() {
   return XF_OK;
 }
 
+// ingest = gpu_fields: what the tokeniser reads beside the fid is what the model needs — fgid for
+// field-aware FM, the third field with feature values; neither: the tokeniser of ingest = gpu
+int Worker::set_ingest_fields(xf_ingest *g) {
+  return xf_ingest_set_fields(g, ingest_fields && fm_mode == XF_FM_FIELD_AWARE,
+                              ingest_fields && feature_values);
+}
+
 // ingest = gpu: the two staging buffers (pinning 2 x block_size of host memory costs tens of ms)
 // and the tokeniser's first launches: start-up work like the two-row update of create_tables
 int Worker::start_ingest() {
   if (!gpu_ingest_applies()) return XF_OK;  // (nothing is pinned for a path that will not run)
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < 2; ++i) {
     if (!ingest_[i] && xf_ingest_create(&ingest_[i], (size_t)block_size << 20) != XF_OK) {
       // (a block size the tokeniser does not take, or no memory to pin: the host parser's run)
-      fprintf(stderr, "xflow_amd: ingest=gpu is not available (%s): the host parser reads the text\n",
-              xf_last_error());
-      ingest_gpu = false;
+      fprintf(stderr, "xflow_amd: ingest=%s is not available (%s): the host parser reads the text\n",
+              ingest_fields ? "gpu_fields" : "gpu", xf_last_error());
+      ingest_gpu = ingest_fields = false;
       return XF_OK;
     }
+    XF_TRY(set_ingest_fields(ingest_[i]));
+  }
   static const char two_rows[] = "0\t1:2:0.5 3:4:1\n1\t5:6:0.25\n";
   void *stream = nullptr;
   XF_TRY(xf_sharded_stream(sharded_, &stream));
@@ -435,14 +444,16 @@ int Worker::batch_training() {
   return XF_OK;
 }
 
-// One epoch from the text with the GPU tokeniser (ingest = gpu).  A staging thread copies the
+// One epoch from the text with the GPU tokeniser (ingest = gpu, gpu_fields).  A staging thread copies the
 // next block's text from the mapped file into pinned memory (several host threads: a 64 MiB
 // block is ~2 ms) while the GPU tokenises, compiles and steps the current one; two staging /
 // tokeniser buffers go round between the two threads.  A block the tokeniser hands back (not of
 // the common shape, xf_ingest.hip) is parsed from the staged text by the host parser: the same
 // arrays, the reference's quirks in one place.  Block boundaries are the reader's (a1).
 // the conditions of the GPU tokeniser's epoch that do not depend on the file
-bool Worker::gpu_ingest_applies() const { return ingest_gpu && core_num == 1 && !block_cache; }
+bool Worker::gpu_ingest_applies() const {
+  return (ingest_gpu || ingest_fields) && core_num == 1 && !block_cache;
+}
 
 // *took = false: this rank's shard file is not a mapped regular file — nothing was done
 int Worker::text_epoch(int epoch, int keep, bool *took) {
@@ -463,8 +474,13 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
     if (!mapped) return XF_OK;  // (xf_reader_peek_text / copy_text work on a mapping)
   }
   *took = true;
-  for (int i = 0; i < 2; ++i)
+  // (the blocks the tokeniser hands back are parsed through this reader: with their values)
+  if (feature_values) XF_TRY(xf_reader_set_values(rd, 1));
+  const bool ffm = fm_mode == XF_FM_FIELD_AWARE;
+  for (int i = 0; i < 2; ++i) {
     if (!ingest_[i]) XF_TRY(xf_ingest_create(&ingest_[i], (size_t)block_size << 20));
+    XF_TRY(set_ingest_fields(ingest_[i]));
+  }
   if (!blocks_[0]) XF_TRY(xf_block_create(&blocks_[0]));
   void *stream = nullptr;
   XF_TRY(xf_sharded_stream(sharded_, &stream));
@@ -552,7 +568,16 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
       int ok = 0;
       rc = xf_ingest_block(ingest_[k], nullptr, p->len, stream, &dk, &drp, &dl, &R, &NNZ, &ok);
       if (rc == XF_OK && ok) {
-        rc = xf_sharded_compile_dev(sharded_, &b, dk, drp, dl, R, NNZ, keep);
+        const int32_t *dfg = nullptr;
+        const float *dv = nullptr;
+        rc = xf_ingest_fields(ingest_[k], &dfg, &dv);
+        if (rc == XF_OK && ffm)
+          rc = xf_sharded_compile_fielded_dev(sharded_, &b, dk, dfg, feature_values ? dv : nullptr,
+                                              drp, dl, R, NNZ, keep);
+        else if (rc == XF_OK && feature_values)
+          rc = xf_sharded_compile_valued_dev(sharded_, &b, dk, dv, drp, dl, R, NNZ, keep);
+        else if (rc == XF_OK)
+          rc = xf_sharded_compile_dev(sharded_, &b, dk, drp, dl, R, NNZ, keep);
         rows = R;
         on_gpu = true;
         ++blocks_gpu;
@@ -561,11 +586,19 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
         size_t nnz = 0;
         const uint64_t *rowptr = nullptr, *keys = nullptr;
         const int32_t *fgid = nullptr, *labels = nullptr;
+        const float *vals = nullptr;
         rc = xf_ingest_staging(ingest_[k], &buf, nullptr);
         if (rc == XF_OK)
           rc = xf_reader_parse_text(rd, buf, p->len, blocks_[0], &rows, &nnz, &rowptr, &keys,
                                     &fgid, &labels);
-        if (rc == XF_OK)
+        if (rc == XF_OK && feature_values) rc = xf_block_values(blocks_[0], &vals);
+        // (with fields or values — one worker — a block without rows is no minibatch: b stays null)
+        if (rc == XF_OK && ffm && rows)
+          rc = xf_sharded_compile_fielded(sharded_, &b, rowptr, keys, fgid, vals, labels, 0, rows,
+                                          keep);
+        else if (rc == XF_OK && feature_values && rows)
+          rc = xf_sharded_compile_valued(sharded_, &b, rowptr, keys, vals, labels, 0, rows, keep);
+        else if (rc == XF_OK && !ffm && !feature_values)
           rc = rows ? xf_sharded_compile(sharded_, &b, rowptr, keys, labels, 0, rows, keep)
                     : xf_sharded_compile(sharded_, &b, kNoRows, nullptr,
                                          (const int32_t *)kNoRows, 0, 0, keep);
@@ -575,15 +608,15 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
       rc = xf_sharded_compile(sharded_, &b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0, keep);
     }
     const double tc1 = now_s();
-    if (rc == XF_OK) rc = xf_sharded_step(sharded_, b);
+    if (rc == XF_OK && b) rc = xf_sharded_step(sharded_, b);
     if (rc == XF_OK) rc = xf_sharded_check(sharded_);
     if (rc != XF_OK) {
       if (b) xf_sbatch_free(b);
       break;
     }
     rows_trained_ += (long)rows;
-    if (keep) cache_.push_back(b);
-    else
+    if (keep && b) cache_.push_back(b);
+    else if (b)
       xf_sbatch_free(b);
     if (world <= 1 && model_ == 0) rc = defrag_if_grown(30);
     if (trace)
@@ -729,7 +762,7 @@ int Worker::train() {
     XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS,
                "XFStartTrain: fm_mode=field_aware has no parity=reference_order mode");
     XF_REQUIRE(!ingest_gpu, "XFStartTrain: fm_mode=field_aware together with ingest=gpu: the GPU "
-               "tokeniser hands out no fgid");
+               "tokeniser hands out no fgid (use ingest=gpu_fields)");
   }
   if (feature_values && !sharded_) {  // next to the canonical mode's: before any rendezvous
     XF_REQUIRE(model_ == 0 || fm_mode != XF_FM_REFERENCE,
@@ -746,7 +779,7 @@ int Worker::train() {
     XF_REQUIRE(!block_cache, "XFStartTrain: feature_values=on together with block_cache=1: the "
                "block cache carries no values");
     XF_REQUIRE(!ingest_gpu, "XFStartTrain: feature_values=on together with ingest=gpu: the GPU "
-               "tokeniser carries no values");
+               "tokeniser carries no values (use ingest=gpu_fields)");
   }
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
@@ -827,10 +860,11 @@ int Worker::set_param(const char *name, const char *value) {
   else if (n == "cache_batches") cache_batches = atoi(value);
   else if (n == "parse_threads") return xf_tune("parse_threads", atof(value));
   else if (n == "ingest") {
-    if (!strcmp(value, "gpu")) ingest_gpu = true;
-    else if (!strcmp(value, "host")) ingest_gpu = false;
+    if (!strcmp(value, "gpu")) ingest_gpu = true, ingest_fields = false;
+    else if (!strcmp(value, "gpu_fields")) ingest_gpu = false, ingest_fields = true;
+    else if (!strcmp(value, "host")) ingest_gpu = ingest_fields = false;
     else
-      return xf::set_error(XF_EINVAL, "XFSetParam: ingest must be gpu or host");
+      return xf::set_error(XF_EINVAL, "XFSetParam: ingest must be gpu, gpu_fields or host");
   }
   else if (n == "block_cache") block_cache = atoi(value);
   else if (n == "block_cache_dir") block_cache_dir = value;

@@ -65,6 +65,11 @@ class Worker {
   // compiled from device arrays; a block that is not of the common shape is parsed on the host
   // as before.  Needs core_num = 1 and no block cache (both checked where the epoch starts).
   bool ingest_gpu = false;
+  // ingest = gpu_fields: the same epoch, and the tokeniser also reads what the model needs beside
+  // the fid — field0 as fgid (fm_mode = field_aware), the third field as the value
+  // (feature_values) — so those two modes train from text tokenised on the GPU; with neither it
+  // is ingest = gpu
+  bool ingest_fields = false;
   long blocks_gpu = 0, blocks_host = 0;  // how the blocks of the last training run were parsed
 
  private:
@@ -88,6 +93,7 @@ class Worker {
   xf_ingest *ingest_[2] = {nullptr, nullptr};  // ingest = gpu: two staging / tokeniser buffers
   int start_ingest();                          // the buffers + first launches, before the clock
   bool gpu_ingest_applies() const;
+  int set_ingest_fields(xf_ingest *g);         // the tokeniser's modes from fm_mode / feature_values
   int text_epoch(int epoch, int keep, bool *took);  // one epoch from the text, tokenised on the GPU
   std::vector<std::thread> closers_;  // readers being closed (munmap of the text) off the clock
   long rows_trained_ = 0;
