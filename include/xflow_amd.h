@@ -691,8 +691,13 @@ int xf_sharded_compile_dev(xf_sharded *st, xf_sbatch **out, const uint64_t *d_ke
                            const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
                            uint32_t NNZ, int keep);
 /* The same with feature values (xf_batch_compile_valued_gpu / _dev; the host build with
- * host_key_build): LR, and FM after xf_sharded_set_fm_mode(XF_FM_CANONICAL), on a trainer of one
- * rank — more than one: XF_EINVAL.  xf_sharded_step / _predict take the result as any other. */
+ * host_key_build): LR, and FM after xf_sharded_set_fm_mode(XF_FM_CANONICAL or _FIELD_AWARE).  One
+ * rank: the fused step.  Several ranks (COLLECTIVE): the generic build, then the static part of
+ * the weight / gradient exchange as xf_sharded_compile — on XF_SCHEDULE_SEQUENTIAL and
+ * XF_SCHEDULE_STALE1; the owner-compute schedules exchange the reference form's pooled row sums
+ * and refuse (XF_EINVAL, the message names the schedule).  No LR cells are built.  A minibatch of
+ * zero rows compiles and steps: a rank without rows still serves the others' Pulls.
+ * xf_sharded_step / _predict take the result as any other. */
 int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
                               const uint64_t *keys, const float *vals, const int32_t *labels,
                               size_t row_begin, size_t row_end, int keep);
@@ -700,9 +705,12 @@ int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out, const uint64_
                                   const float *d_vals, const uint32_t *d_rowptr,
                                   const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep);
 /* The same with the nonzeros' fields (xf_batch_compile_fielded / _gpu / _dev; vals / d_vals may
- * be NULL) for a one-rank FM trainer after xf_sharded_set_fm_fields +
- * xf_sharded_set_fm_mode(XF_FM_FIELD_AWARE).  With feature values the trainer obeys the rules of
- * xf_sharded_compile_valued. */
+ * be NULL) for an FM trainer after xf_sharded_set_fm_fields +
+ * xf_sharded_set_fm_mode(XF_FM_FIELD_AWARE); one rank or several, as xf_sharded_compile_valued
+ * (whose rules the trainer obeys with feature values).  The fgid range check comes before any
+ * exchange, and the ranks agree on its outcome: an fgid outside [0, fields) on ONE rank is
+ * XF_EINVAL on EVERY rank (the offender's message names the fgid, the others' the rank), and no
+ * rank is left waiting in a collective. */
 int xf_sharded_compile_fielded(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
                                const uint64_t *keys, const int32_t *fgid, const float *vals,
                                const int32_t *labels, size_t row_begin, size_t row_end, int keep);
@@ -730,10 +738,13 @@ int xf_sharded_set_schedule(xf_sharded *st, int schedule);
  * (xf_sbatch_fm_keyed) has no index of its key list, and the reference-order kernels refuse it
  * (the call says so and names this remedy) */
 int xf_sharded_set_parity(xf_sharded *st, int mode);
-/* the FM form (xf_workspace_fm_mode) of a one-rank FM trainer, accepted only while its tables
- * hold no key.  XF_FM_CANONICAL also starts an SGD v table from the hash-normal init (a constant
+/* the FM form of an FM trainer (one rank: xf_workspace_fm_mode of its fused step; several: kept
+ * in the trainer, which picks the forward, the emitting gradient kernels and — field-aware — the
+ * masked owner push by it), accepted only while its tables hold no key.  XF_FM_CANONICAL also starts an SGD v table from the hash-normal init (a constant
  * init would keep a key's k factors equal forever), and minibatches compiled from then on carry
- * a key list (xf_batch_compile_gpu / _dev).  A trainer of more than one rank: XF_EINVAL.
+ * a key list (xf_batch_compile_gpu / _dev).  Several ranks (or XF_SHARDED_GENERAL=1): on
+ * XF_SCHEDULE_SEQUENTIAL and XF_SCHEDULE_STALE1, any world size, both optimizers; on the
+ * owner-compute schedules (and so with XF_UPDATE_SUM_THEN_STEP): XF_EINVAL naming the schedule.
  * XF_FM_FIELD_AWARE needs xf_sharded_set_fm_fields first; the trainer's k (xf_sharded_config) is
  * then the WIDTH of a v row, fields x (factors per field), at most 4096; the v table starts
  * hash-normal for both optimizers, and minibatches come from xf_sharded_compile_fielded*. */

@@ -1042,8 +1042,11 @@ class Sharded:
     def __init__(self, group=None, model="lr", optimizer="ftrl", k=10, capacity=1 << 22,
                  schedule="sequential", seed=0, host_key_build=False, update="rank_ordered",
                  fm_mode="reference", fields=None, **hyper):
-        """fm_mode="canonical": Rendle's FM on a one-rank trainer (xf_sharded_set_fm_mode);
-        fm_mode="field_aware" with fields=F: k factors per field, v rows F k wide"""
+        """fm_mode="canonical": Rendle's FM (xf_sharded_set_fm_mode); fm_mode="field_aware" with
+        fields=F: k factors per field, v rows F k wide.  Both, and minibatches with feature values
+        (compile(values=)), run on one rank and on a group of several ranks with schedule
+        "sequential" or "stale1" (the weight / gradient exchange moves whole rows); the
+        owner-compute schedules ("owner", "owner_stale1") and update="sum_then_step" refuse them"""
         require_gpu()
         c = ShardedConfig()
         lib().xf_sharded_config_default(C.byref(c))
@@ -1074,7 +1077,8 @@ class Sharded:
             self.set_fm_mode(fm_mode)
 
     def set_fm_mode(self, mode):
-        """'reference', 'canonical' or 'field_aware': before the first step, one rank only"""
+        """'reference', 'canonical' or 'field_aware': before the first step (the tables empty);
+        several ranks: schedules 'sequential' and 'stale1' only"""
         check(lib().xf_sharded_set_fm_mode(self.h, FM_MODES[mode]))
 
     def close(self):
@@ -1086,8 +1090,10 @@ class Sharded:
 
     def compile(self, rowptr, keys, labels, row_begin=0, row_end=None, keep=True, values=None,
                 fgid=None):
-        """values (float32, beside keys): a minibatch with feature values, one rank only; fgid
-        (int32, beside keys): a minibatch with its fields, for fm_mode='field_aware'"""
+        """values (float32, beside keys): a minibatch with feature values; fgid (int32, beside
+        keys): a minibatch with its fields, for fm_mode='field_aware'.  COLLECTIVE on a group: every
+        rank compiles (a rank without rows: empty arrays), and an fgid outside [0, fields) on one
+        rank is an XFError on every rank"""
         rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         labels = np.ascontiguousarray(labels, dtype=np.int32)

@@ -202,6 +202,12 @@ __device__ __forceinline__ void step_coord(const TableDev &T, size_t o, float w_
   step_coord<OPT>(T, o, w_old, g, n, z);
 }
 
+// A third value of the gradient kernels' OPT parameter, beside XF_OPT_FTRL and XF_OPT_SGD: no
+// step.  The gradient leaves the kernel — gv[u dim + c] next to gw[u], for field-aware FM the
+// key's touched mask too — and the key's owner steps it when the Push arrives (xf_sharded.hip).
+// Such an instantiation reads no state row, no table and no pulled w.
+constexpr int kOptEmit = 2;
+
 // x / R exactly as the reference computes it — `float /= 1.0 * line_num`, i.e. the fp32 value
 // divided in double and rounded back to fp32 (lr_worker.cc:117, fm_worker.cc:150-156) — at the
 // price of an fp32 division: for x an fp32 number and R an integer below 2^24 the exact

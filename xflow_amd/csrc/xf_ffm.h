@@ -23,6 +23,12 @@ int ffm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, int F,
                     const float *d_vu, const uint32_t *d_xfg, const uint32_t *d_coo_pos,
                     const float *d_loss, float *d_gw, double *d_hpart, const float *d_xval,
                     hipStream_t s);
+// the gradient alone (a worker of a sharded trainer: the keys' owners step): d_gw[U],
+// d_gv[U x F k] (untouched coordinates 0) and d_mask[U] (bit h: field h of the key touched),
+// every entry written; no table, state row or pulled w is read
+int ffm_grad_emit(const xf_dev_batch *b, int k, int F, const float *d_vu, const uint32_t *d_xfg,
+                  const uint32_t *d_coo_pos, const float *d_loss, float *d_gw, float *d_gv,
+                  uint64_t *d_mask, double *d_hpart, const float *d_xval, hipStream_t s);
 
 }  // namespace xf
 #endif  // XF_FFM_H_

@@ -207,6 +207,9 @@ __device__ __forceinline__ float ffm_lx(uint32_t j, const uint32_t *__restrict__
 // occurrences).  w: one lane per key, as k_fmc_grad_tiled.  v: the tile's keys in groups of
 // kAcc / dim; a wavefront per key walks its occurrences (ffm_occ), then a lane per (key,
 // coordinate) steps the touched ones in place (the pulled value is the current weight).
+// OPT = xf::kOptEmit: nothing is stepped — gv[u dim + c] leaves with the gradient of a touched
+// coordinate and 0 for an untouched one, mask[u] with the key's touched mask, beside gw[u]; the
+// state rows, the tables and wu are not read (the worker of a sharded trainer: the owner steps).
 template <int OPT, int K /* compile-time factor count, 0 = k_rt */, bool VAL>
 __global__ void __launch_bounds__(kBlock)
 k_ffm_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ tile_ptr,
@@ -217,8 +220,10 @@ k_ffm_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
                  const float *__restrict__ wu, const float *__restrict__ vu,
                  const uint32_t *__restrict__ rows_w, const uint32_t *__restrict__ rows_v,
                  uint32_t R, int k_rt, int kp_rt, uint32_t dim, float *__restrict__ gw,
-                 const float *__restrict__ xval) {
+                 const float *__restrict__ xval, float *__restrict__ gv,
+                 unsigned long long *__restrict__ mask) {
 #pragma clang fp contract(off)
+  constexpr bool kEmit = OPT == xf::kOptEmit;
   __shared__ double acc[kAcc];
   __shared__ unsigned long long msk[XF_GRAD_TILE_KEYS];
   const uint32_t k = K > 0 ? (uint32_t)K : (uint32_t)k_rt;
@@ -235,7 +240,7 @@ k_ffm_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
         aw += (double)ffm_lx<VAL>(j, coo_row, coo_pos, xval, loss);
       const float g1 = xf::div_by_rows((float)aw, R);
       gw[ua + q] = g1;
-      xf::step_coord<OPT>(TW, rows_w[ua + q], wu[ua + q], g1);
+      if constexpr (!kEmit) xf::step_coord<OPT>(TW, rows_w[ua + q], wu[ua + q], g1);
     }
     for (uint32_t q0 = 0; q0 < nk; q0 += kpg) {
       const uint32_t nq = min(kpg, nk - q0), nel = nq * dim;
@@ -248,15 +253,23 @@ k_ffm_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
           m |= ffm_occ<VAL>(j, lane, k, kp, dim, coo_row, coo_pos, rowptr, uidx, xfg, xval, loss,
                             vu, acc + (size_t)q * dim);
         m = wave_or(m);
-        if (lane == 0) msk[q] = m;
+        if (lane == 0) {
+          msk[q] = m;
+          if constexpr (kEmit) mask[u] = m;
+        }
       }
       __syncthreads();
       for (uint32_t el = tid; el < nel; el += kBlock) {
         const uint32_t q = el / dim, c = el - q * dim;
-        if (!((msk[q] >> (c / k)) & 1ull)) continue;  // untouched: w, n, z stay as they are
-        const uint32_t u = ua + q0 + q;
-        const float g = xf::div_by_rows((float)acc[el], R);
-        xf::step_coord<OPT>(TV, (size_t)rows_v[u] * dim + c, vu[(size_t)u * dim + c], g);
+        if constexpr (kEmit) {  // an untouched coordinate leaves as 0: the buffer is fully defined
+          gv[(size_t)(ua + q0 + q) * dim + c] =
+              ((msk[q] >> (c / k)) & 1ull) ? xf::div_by_rows((float)acc[el], R) : 0.0f;
+        } else {
+          if (!((msk[q] >> (c / k)) & 1ull)) continue;  // untouched: w, n, z stay as they are
+          const uint32_t u = ua + q0 + q;
+          const float g = xf::div_by_rows((float)acc[el], R);
+          xf::step_coord<OPT>(TV, (size_t)rows_v[u] * dim + c, vu[(size_t)u * dim + c], g);
+        }
       }
       __syncthreads();
     }
@@ -308,15 +321,18 @@ k_ffm_heavy_partial(const uint32_t *__restrict__ heavy, const uint32_t *__restri
 }
 
 // one workgroup per heavy key: its chunks' sums added per column and their masks joined, then
-// the optimizer steps of its touched coordinates and of its w
+// the optimizer steps of its touched coordinates and of its w (OPT = xf::kOptEmit: gv, mask[u] and
+// gw[u] written as k_ffm_grad_tiled does, nothing stepped)
 template <int OPT>
 __global__ void __launch_bounds__(kBlock)
 k_ffm_heavy_finish(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ heavy,
                    const uint32_t *__restrict__ hch, const double *__restrict__ partial,
                    const uint32_t *__restrict__ rows_w, const uint32_t *__restrict__ rows_v,
                    const float *__restrict__ wu, const float *__restrict__ vu, uint32_t R,
-                   int k_rt, uint32_t dim, float *__restrict__ gw) {
+                   int k_rt, uint32_t dim, float *__restrict__ gw, float *__restrict__ gv,
+                   unsigned long long *__restrict__ mask) {
 #pragma clang fp contract(off)
+  constexpr bool kEmit = OPT == xf::kOptEmit;
   __shared__ unsigned long long msk;
   const uint32_t tid = threadIdx.x, h = blockIdx.x, k = (uint32_t)k_rt;
   const uint32_t u = heavy[h], c0 = hch[h], c1 = hch[h + 1];
@@ -326,6 +342,7 @@ k_ffm_heavy_finish(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict_
     for (uint32_t c = c0; c < c1; ++c)
       m |= ((const unsigned long long *)partial)[(size_t)c * ncol + dim + 1];
     msk = m;
+    if constexpr (kEmit) mask[u] = m;
   }
   __syncthreads();
   for (uint32_t col = tid; col <= dim; col += kBlock) {
@@ -333,11 +350,15 @@ k_ffm_heavy_finish(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict_
     for (uint32_t c = c0; c < c1; ++c) a += partial[(size_t)c * ncol + col];
     const float g = xf::div_by_rows((float)a, R);
     if (col < dim) {
-      if ((msk >> (col / k)) & 1ull)
-        xf::step_coord<OPT>(TV, (size_t)rows_v[u] * dim + col, vu[(size_t)u * dim + col], g);
+      if constexpr (kEmit) {
+        gv[(size_t)u * dim + col] = ((msk >> (col / k)) & 1ull) ? g : 0.0f;
+      } else {
+        if ((msk >> (col / k)) & 1ull)
+          xf::step_coord<OPT>(TV, (size_t)rows_v[u] * dim + col, vu[(size_t)u * dim + col], g);
+      }
     } else {
       gw[u] = g;
-      xf::step_coord<OPT>(TW, rows_w[u], wu[u], g);
+      if constexpr (!kEmit) xf::step_coord<OPT>(TW, rows_w[u], wu[u], g);
     }
   }
 }
@@ -395,25 +416,17 @@ int ffm_forward(const xf_dev_batch *b, int k, int F, const float *d_wu, const fl
   return XF_OK;
 }
 
-// gradient + both Pushes for the tables on this GPU.  rows_w / rows_v: the keys' state rows,
-// d_wu / d_vu: the rows the Pull returned (current: the step has not written them yet).  gw[U]
-// is written for every key; d_hpart: ffm_heavy_doubles(b, F k) doubles.
-int ffm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, int F,
-                    const uint32_t *d_rows_w, const uint32_t *d_rows_v, const float *d_wu,
-                    const float *d_vu, const uint32_t *d_xfg, const uint32_t *d_coo_pos,
-                    const float *d_loss, float *d_gw, double *d_hpart, const float *d_xval,
-                    hipStream_t s) {
-  XF_REQUIRE(tw && tv && b && d_rows_w && d_rows_v && d_wu && d_vu && d_xfg && d_coo_pos &&
-                 d_loss && d_gw, "field-aware FM gradient: null argument");
-  if (b->U == 0) return XF_OK;
-  const xf::TableDev &TW = xf::table_dev(tw), &TV = xf::table_dev(tv);
-  const uint32_t dim = (uint32_t)TV.dim;
+// the tile kernel and the heavy keys' two for one OPT (an optimizer, or kOptEmit with d_gv, d_mask)
+static int ffm_grad_launch(int opt, const TableDev &TW, const TableDev &TV, uint32_t dim,
+                           const xf_dev_batch *b, int F, const uint32_t *d_rows_w,
+                           const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
+                           const uint32_t *d_xfg, const uint32_t *d_coo_pos, const float *d_loss,
+                           float *d_gw, float *d_gv, unsigned long long *d_mask, double *d_hpart,
+                           const float *d_xval, hipStream_t s) {
   XF_REQUIRE(F >= 1 && F <= 64 && dim >= 1 && dim <= kAcc && dim % (uint32_t)F == 0,
              "field-aware FM gradient: the v table's dim (%u) is not fields (%d) x k, or exceeds "
              "%u", dim, F, kAcc);
   const int k = (int)(dim / (uint32_t)F), kp = lanes_for(k);
-  const bool ftrl = TV.nz != nullptr;
-  XF_REQUIRE((TW.nz != nullptr) == ftrl, "field-aware FM gradient: w and v use different optimizers");
   XF_REQUIRE(b->ntiles && b->tile_ptr, "field-aware FM gradient: the minibatch has no gradient tiles");
   XF_REQUIRE(!b->H || (b->heavy_chunk_ptr && d_hpart),
              "field-aware FM gradient: heavy keys without their chunks or scratch");
@@ -421,7 +434,8 @@ int ffm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, int F,
 #define XF_FFM_GU_V(OPTV, KK, VAL)                                                              \
   hipLaunchKernelGGL((k_ffm_grad_tiled<OPTV, KK, VAL>), gt, blk, 0, s, TW, TV, b->tile_ptr,     \
                      b->ntiles, b->segptr, b->coo_row, d_coo_pos, b->rowptr, b->uidx, d_xfg,    \
-                     d_loss, d_wu, d_vu, d_rows_w, d_rows_v, b->R, k, kp, dim, d_gw, d_xval)
+                     d_loss, d_wu, d_vu, d_rows_w, d_rows_v, b->R, k, kp, dim, d_gw, d_xval,    \
+                     d_gv, d_mask)
 #define XF_FFM_GU(OPTV, KK)                      \
   do {                                           \
     if (d_xval) XF_FFM_GU_V(OPTV, KK, true);     \
@@ -434,7 +448,9 @@ int ffm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, int F,
     case 16: XF_FFM_GU(OPTV, 16); break;  \
     default: XF_FFM_GU(OPTV, 0); break;   \
   }
-  if (ftrl) {
+  if (opt == kOptEmit) {
+    XF_FFM_GU_K(kOptEmit)
+  } else if (opt == XF_OPT_FTRL) {
     XF_FFM_GU_K(XF_OPT_FTRL)
   } else {
     XF_FFM_GU_K(XF_OPT_SGD)
@@ -451,16 +467,54 @@ int ffm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, int F,
                      kp, dim, d_hpart, d_xval)
 #define XF_FFM_HF(OPTV)                                                                          \
   hipLaunchKernelGGL(k_ffm_heavy_finish<OPTV>, gf, blk, 0, s, TW, TV, b->heavy, b->heavy_chunk_ptr, \
-                     d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k, dim, d_gw)
+                     d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k, dim, d_gw, d_gv, d_mask)
     if (d_xval) XF_FFM_HP(true);
     else XF_FFM_HP(false);
-    if (ftrl) XF_FFM_HF(XF_OPT_FTRL);
+    if (opt == kOptEmit) XF_FFM_HF(kOptEmit);
+    else if (opt == XF_OPT_FTRL) XF_FFM_HF(XF_OPT_FTRL);
     else XF_FFM_HF(XF_OPT_SGD);
 #undef XF_FFM_HF
 #undef XF_FFM_HP
     XF_HIP(hipGetLastError());
   }
   return XF_OK;
+}
+
+// gradient + both Pushes for the tables on this GPU.  rows_w / rows_v: the keys' state rows,
+// d_wu / d_vu: the rows the Pull returned (current: the step has not written them yet).  gw[U]
+// is written for every key; d_hpart: ffm_heavy_doubles(b, F k) doubles.
+int ffm_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, int F,
+                    const uint32_t *d_rows_w, const uint32_t *d_rows_v, const float *d_wu,
+                    const float *d_vu, const uint32_t *d_xfg, const uint32_t *d_coo_pos,
+                    const float *d_loss, float *d_gw, double *d_hpart, const float *d_xval,
+                    hipStream_t s) {
+  XF_REQUIRE(tw && tv && b && d_rows_w && d_rows_v && d_wu && d_vu && d_xfg && d_coo_pos &&
+                 d_loss && d_gw, "field-aware FM gradient: null argument");
+  if (b->U == 0) return XF_OK;
+  const xf::TableDev &TW = xf::table_dev(tw), &TV = xf::table_dev(tv);
+  const bool ftrl = TV.nz != nullptr;
+  XF_REQUIRE((TW.nz != nullptr) == ftrl, "field-aware FM gradient: w and v use different optimizers");
+  return ffm_grad_launch(ftrl ? XF_OPT_FTRL : XF_OPT_SGD, TW, TV, (uint32_t)TV.dim, b, F, d_rows_w,
+                         d_rows_v, d_wu, d_vu, d_xfg, d_coo_pos, d_loss, d_gw, nullptr, nullptr,
+                         d_hpart, d_xval, s);
+}
+
+// The gradient alone, for a worker whose keys live on other ranks: gw[U], gv[U x F k] and
+// mask[U] (bit h: the minibatch touched field h of the key) from the pulled d_vu[U x F k] and the
+// forward's d_loss.  Every entry of the three is written, an untouched coordinate of gv as 0; no
+// table, state row or pulled w is read.  The keys' owners step what the Push brings them, v
+// through the masks (table_update_heads_masked).  d_hpart: ffm_heavy_doubles(b, F k) doubles.
+int ffm_grad_emit(const xf_dev_batch *b, int k, int F, const float *d_vu, const uint32_t *d_xfg,
+                  const uint32_t *d_coo_pos, const float *d_loss, float *d_gw, float *d_gv,
+                  uint64_t *d_mask, double *d_hpart, const float *d_xval, hipStream_t s) {
+  XF_REQUIRE(b && k >= 1, "field-aware FM gradient (emit): bad argument");
+  if (b->U == 0) return XF_OK;  // (no key: nothing to write, and the arrays may be empty)
+  XF_REQUIRE(d_vu && d_xfg && d_coo_pos && d_loss && d_gw && d_gv && d_mask,
+             "field-aware FM gradient (emit): bad argument");
+  const TableDev none{};
+  return ffm_grad_launch(kOptEmit, none, none, (uint32_t)F * (uint32_t)k, b, F, nullptr, nullptr,
+                         nullptr, d_vu, d_xfg, d_coo_pos, d_loss, d_gw, d_gv,
+                         (unsigned long long *)d_mask, d_hpart, d_xval, s);
 }
 
 }  // namespace xf

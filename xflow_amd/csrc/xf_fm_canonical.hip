@@ -120,6 +120,8 @@ k_fmc_forward(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ 
 // weight: nothing touched the row since the Pull).  One lane per key does the same for w.
 // VAL: the occurrences' values staged beside their rows — lx = loss x (what the w gradient sums),
 // xs = x (for a = v x); binary: lx is the plain loss and xs is not there.
+// OPT = xf::kOptEmit: the gradient goes out instead — gv[u k + f] beside gw[u] — and neither the
+// state rows nor the tables nor wu are read (the worker of a sharded trainer: the owner steps).
 template <int OPT, int K /* compile-time factor count, 0 = k_rt */, bool VAL>
 __global__ void __launch_bounds__(kBlock)
 k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ tile_ptr,
@@ -128,8 +130,10 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
                  const float *__restrict__ S, const float *__restrict__ wu,
                  const float *__restrict__ vu, const uint32_t *__restrict__ rows_w,
                  const uint32_t *__restrict__ rows_v, uint32_t R, int k_rt,
-                 float *__restrict__ gw, const float *__restrict__ coo_val) {
+                 float *__restrict__ gw, const float *__restrict__ coo_val,
+                 float *__restrict__ gv) {
 #pragma clang fp contract(off)
+  constexpr bool kEmit = OPT == xf::kOptEmit;
   __shared__ float lx[XF_GRAD_TILE_NNZ];
   __shared__ float xs[VAL ? XF_GRAD_TILE_NNZ : 1];
   __shared__ uint32_t ss[XF_GRAD_TILE_NNZ];
@@ -166,7 +170,9 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
 #pragma unroll
       for (int i = 0; i < kUn; ++i) {
         v[i] = on[i] ? vu[(size_t)(ua + kq[i]) * k + kk[i]] : 0.0f;
-        to[i] = on[i] ? (size_t)rows_v[ua + kq[i]] * k + kk[i] : 0;
+        if constexpr (kEmit) to[i] = (size_t)(ua + kq[i]) * k + kk[i];  // (its place in gv)
+        else
+          to[i] = on[i] ? (size_t)rows_v[ua + kq[i]] * k + kk[i] : 0;
       }
       if (OPT == XF_OPT_FTRL) {
 #pragma unroll
@@ -193,7 +199,9 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
           acc += (double)(lx[j] * (S[(size_t)ss[j] * k + kk[i]] - (VAL ? v[i] * xs[j] : v[i])));
         const float g = xf::div_by_rows((float)acc, R);
         constexpr bool kNZ = OPT == XF_OPT_FTRL;  // (vn, vz: requested above, FTRL only)
-        xf::step_coord<OPT>(TV, to[i], v[i], g, kNZ ? vn[i] : 0.0f, kNZ ? vz[i] : 0.0f);
+        if constexpr (kEmit) gv[to[i]] = g;
+        else
+          xf::step_coord<OPT>(TV, to[i], v[i], g, kNZ ? vn[i] : 0.0f, kNZ ? vz[i] : 0.0f);
       }
     }
     // the keys' w: the true gradient (sum of the occurrences' losses) / R, one lane per key
@@ -202,7 +210,7 @@ k_fmc_grad_tiled(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ 
       for (uint32_t j = sp[q]; j < sp[q + 1]; ++j) aw += (double)lx[j];
       const float g1 = xf::div_by_rows((float)aw, R);
       gw[ua + q] = g1;
-      xf::step_coord<OPT>(TW, rows_w[ua + q], wu[ua + q], g1);
+      if constexpr (!kEmit) xf::step_coord<OPT>(TW, rows_w[ua + q], wu[ua + q], g1);
     }
     __syncthreads();
   }
@@ -279,15 +287,16 @@ k_fmc_heavy_partial(const uint32_t *__restrict__ heavy, const uint32_t *__restri
 }
 
 // one workgroup per heavy key: its chunks' partial sums added per column, then the optimizer
-// steps of its k factors and of its w
+// steps of its k factors and of its w (OPT = xf::kOptEmit: gv[u k + col] and gw[u] written, no step)
 template <int OPT>
 __global__ void __launch_bounds__(kBlock)
 k_fmc_heavy_finish(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict__ heavy,
                    const uint32_t *__restrict__ hch, const double *__restrict__ partial,
                    const uint32_t *__restrict__ rows_w, const uint32_t *__restrict__ rows_v,
                    const float *__restrict__ wu, const float *__restrict__ vu, uint32_t R,
-                   int k_rt, float *__restrict__ gw) {
+                   int k_rt, float *__restrict__ gw, float *__restrict__ gv) {
 #pragma clang fp contract(off)
+  constexpr bool kEmit = OPT == xf::kOptEmit;
   __shared__ double red[kBlock];
   const uint32_t tid = threadIdx.x, h = blockIdx.x, k = (uint32_t)k_rt;
   const uint32_t u = heavy[h], c0h = hch[h], c1h = hch[h + 1];
@@ -304,10 +313,12 @@ k_fmc_heavy_finish(xf::TableDev TW, xf::TableDev TV, const uint32_t *__restrict_
       for (uint32_t q = 1; q < nsl; ++q) acc += red[q * cpp + cl];
       const float g = xf::div_by_rows((float)acc, R);
       if (col < k) {
-        xf::step_coord<OPT>(TV, (size_t)rows_v[u] * k + col, vu[(size_t)u * k + col], g);
+        if constexpr (kEmit) gv[(size_t)u * k + col] = g;
+        else
+          xf::step_coord<OPT>(TV, (size_t)rows_v[u] * k + col, vu[(size_t)u * k + col], g);
       } else {
         gw[u] = g;
-        xf::step_coord<OPT>(TW, rows_w[u], wu[u], g);
+        if constexpr (!kEmit) xf::step_coord<OPT>(TW, rows_w[u], wu[u], g);
       }
     }
     __syncthreads();
@@ -363,40 +374,34 @@ int fmc_forward(const xf_dev_batch *b, int k, const float *d_wu, const float *d_
 // the heavy keys' two kernels: the chunk sums, then a key's chunks added and its k + 1 coordinates
 // stepped.  k = 0 steps w alone (valued LR, xf_valued.hip: d_S, d_vu, d_rows_v and TV are not
 // read).  d_coo_val: null for a binary minibatch.  d_hpart: fmc_heavy_doubles(b, k) doubles.
-void fmc_heavy_update(const TableDev &TW, const TableDev &TV, int k, const xf_dev_batch *b,
+// opt: XF_OPT_* — the tables' optimizer — or kOptEmit: d_gw[u] and d_gv[u k + col] written and
+// nothing stepped (the tables, the state rows and d_wu are not read).
+void fmc_heavy_update(int opt, const TableDev &TW, const TableDev &TV, int k, const xf_dev_batch *b,
                       const uint32_t *d_rows_w, const uint32_t *d_rows_v, const float *d_wu,
                       const float *d_vu, const float *d_S, const float *d_loss, float *d_gw,
-                      double *d_hpart, const float *d_coo_val, hipStream_t s) {
+                      float *d_gv, double *d_hpart, const float *d_coo_val, hipStream_t s) {
   const dim3 gp(b->n_heavy_chunks), gf(b->H), blk(kBlock);
 #define XF_FMC_HP(VAL)                                                                         \
   hipLaunchKernelGGL(k_fmc_heavy_partial<VAL>, gp, blk, 0, s, b->heavy, b->heavy_chunk_ptr, b->H, \
                      b->segptr, b->coo_row, d_loss, d_S, d_vu, k, d_hpart, d_coo_val)
 #define XF_FMC_HF(OPTV)                                                                         \
   hipLaunchKernelGGL(k_fmc_heavy_finish<OPTV>, gf, blk, 0, s, TW, TV, b->heavy, b->heavy_chunk_ptr, \
-                     d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k, d_gw)
+                     d_hpart, d_rows_w, d_rows_v, d_wu, d_vu, b->R, k, d_gw, d_gv)
   if (d_coo_val) XF_FMC_HP(true);
   else XF_FMC_HP(false);
-  if (TW.nz != nullptr) XF_FMC_HF(XF_OPT_FTRL);
+  if (opt == kOptEmit) XF_FMC_HF(kOptEmit);
+  else if (opt == XF_OPT_FTRL) XF_FMC_HF(XF_OPT_FTRL);
   else XF_FMC_HF(XF_OPT_SGD);
 #undef XF_FMC_HF
 #undef XF_FMC_HP
 }
 
-// gradient + both Pushes for the tables on this GPU.  rows_w / rows_v: the keys' state rows,
-// d_wu / d_vu: the rows the Pull returned (current: the step has not written them yet).  gw[U]
-// is written for every key (the capture hook); d_hpart: fmc_heavy_doubles(b, k) doubles.
-// d_coo_val: the values in key-grouped order, null for a binary minibatch.
-int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uint32_t *d_rows_w,
-                    const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
-                    const float *d_S, const float *d_loss, float *d_gw, double *d_hpart,
-                    const float *d_coo_val, hipStream_t s) {
-  XF_REQUIRE(tw && tv && b && d_rows_w && d_rows_v && d_wu && d_vu && d_S && d_loss && d_gw,
-             "fm canonical gradient: null argument");
-  if (b->U == 0) return XF_OK;
-  const xf::TableDev &TW = xf::table_dev(tw), &TV = xf::table_dev(tv);
-  const int k = TV.dim;
-  const bool ftrl = TV.nz != nullptr;
-  XF_REQUIRE((TW.nz != nullptr) == ftrl, "fm canonical gradient: w and v use different optimizers");
+// the tile kernel and the heavy keys' two for one OPT (an optimizer, or kOptEmit with d_gv)
+static int fmc_grad_launch(int opt, const TableDev &TW, const TableDev &TV, int k,
+                           const xf_dev_batch *b, const uint32_t *d_rows_w,
+                           const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
+                           const float *d_S, const float *d_loss, float *d_gw, float *d_gv,
+                           double *d_hpart, const float *d_coo_val, hipStream_t s) {
   XF_REQUIRE(b->ntiles && b->tile_ptr, "fm canonical gradient: the minibatch has no gradient tiles");
   XF_REQUIRE(!b->H || (b->heavy_chunk_ptr && d_hpart),
              "fm canonical gradient: heavy keys without their chunks or scratch");
@@ -404,7 +409,7 @@ int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uin
 #define XF_FMC_GU_V(OPTV, KK, VAL)                                                               \
   hipLaunchKernelGGL((k_fmc_grad_tiled<OPTV, KK, VAL>), gt, blk, 0, s, TW, TV, b->tile_ptr,      \
                      b->ntiles, b->segptr, b->coo_row, d_loss, d_S, d_wu, d_vu, d_rows_w, d_rows_v, \
-                     b->R, k, d_gw, d_coo_val)
+                     b->R, k, d_gw, d_coo_val, d_gv)
 #define XF_FMC_GU(OPTV, KK)                        \
   do {                                             \
     if (d_coo_val) XF_FMC_GU_V(OPTV, KK, true);    \
@@ -419,7 +424,9 @@ int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uin
     case 64: XF_FMC_GU(OPTV, 64); break;  \
     default: XF_FMC_GU(OPTV, 0); break;   \
   }
-  if (ftrl) {
+  if (opt == kOptEmit) {
+    XF_FMC_GU_K(kOptEmit)
+  } else if (opt == XF_OPT_FTRL) {
     XF_FMC_GU_K(XF_OPT_FTRL)
   } else {
     XF_FMC_GU_K(XF_OPT_SGD)
@@ -429,11 +436,44 @@ int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uin
 #undef XF_FMC_GU_V
   XF_HIP(hipGetLastError());
   if (b->H) {
-    fmc_heavy_update(TW, TV, k, b, d_rows_w, d_rows_v, d_wu, d_vu, d_S, d_loss, d_gw, d_hpart,
-                     d_coo_val, s);
+    fmc_heavy_update(opt, TW, TV, k, b, d_rows_w, d_rows_v, d_wu, d_vu, d_S, d_loss, d_gw, d_gv,
+                     d_hpart, d_coo_val, s);
     XF_HIP(hipGetLastError());
   }
   return XF_OK;
+}
+
+// gradient + both Pushes for the tables on this GPU.  rows_w / rows_v: the keys' state rows,
+// d_wu / d_vu: the rows the Pull returned (current: the step has not written them yet).  gw[U]
+// is written for every key (the capture hook); d_hpart: fmc_heavy_doubles(b, k) doubles.
+// d_coo_val: the values in key-grouped order, null for a binary minibatch.
+int fmc_grad_update(xf_table *tw, xf_table *tv, const xf_dev_batch *b, const uint32_t *d_rows_w,
+                    const uint32_t *d_rows_v, const float *d_wu, const float *d_vu,
+                    const float *d_S, const float *d_loss, float *d_gw, double *d_hpart,
+                    const float *d_coo_val, hipStream_t s) {
+  XF_REQUIRE(tw && tv && b && d_rows_w && d_rows_v && d_wu && d_vu && d_S && d_loss && d_gw,
+             "fm canonical gradient: null argument");
+  if (b->U == 0) return XF_OK;
+  const xf::TableDev &TW = xf::table_dev(tw), &TV = xf::table_dev(tv);
+  const bool ftrl = TV.nz != nullptr;
+  XF_REQUIRE((TW.nz != nullptr) == ftrl, "fm canonical gradient: w and v use different optimizers");
+  return fmc_grad_launch(ftrl ? XF_OPT_FTRL : XF_OPT_SGD, TW, TV, TV.dim, b, d_rows_w, d_rows_v,
+                         d_wu, d_vu, d_S, d_loss, d_gw, nullptr, d_hpart, d_coo_val, s);
+}
+
+// The gradient alone, for a worker whose keys live on other ranks: gw[U] and gv[U x k] from the
+// pulled d_vu[U x k], the forward's d_S and d_loss; every entry of both is written.  No table,
+// no state row and no pulled w is read: the keys' owners step what the Push brings them
+// (table_update_heads).  d_hpart, d_coo_val: as fmc_grad_update's.
+int fmc_grad_emit(const xf_dev_batch *b, int k, const float *d_vu, const float *d_S,
+                  const float *d_loss, float *d_gw, float *d_gv, double *d_hpart,
+                  const float *d_coo_val, hipStream_t s) {
+  XF_REQUIRE(b && k >= 1, "fm canonical gradient (emit): bad argument");
+  if (b->U == 0) return XF_OK;  // (no key: nothing to write, and the arrays may be empty)
+  XF_REQUIRE(d_vu && d_S && d_loss && d_gw && d_gv, "fm canonical gradient (emit): bad argument");
+  const TableDev none{};
+  return fmc_grad_launch(kOptEmit, none, none, k, b, nullptr, nullptr, nullptr, d_vu, d_S, d_loss,
+                         d_gw, d_gv, d_hpart, d_coo_val, s);
 }
 
 }  // namespace xf

@@ -23,6 +23,12 @@
 //               the table and before Pull(t+2) — overlaps the next weights exchange, forward
 //               and gradient.  Weights are exactly one step stale (inside ps-lite's
 //               asynchronous semantics), still deterministic.
+// Both exchange whole rows — w and the v rows one way, their gradients the other — so they run
+// every form of the model whose forward takes the pulled rows: the reference FM, canonical FM
+// (xf_fm_canonical.hip), field-aware FM (xf_ffm.hip: the Push also carries each key's 8-byte mask
+// of touched fields, and the owner steps a coordinate of v only for the sources that touched it)
+// and minibatches with feature values.  The worker's gradient kernels are the fused step's in
+// their emitting instantiation (xf::kOptEmit): they hand the gradient out instead of stepping.
 // With world == 1 there is nothing to exchange: the step IS the fused single-shard step
 // (xf_lr_step / xf_fm_step) on a locally compiled minibatch.
 #include <hip/hip_runtime.h>
@@ -42,6 +48,8 @@
 #include "xf_cells.h"
 #include "xf_common.h"
 #include "xf_device.h"
+#include "xf_ffm.h"
+#include "xf_fm_canonical.h"
 #include "xf_scratch.h"
 
 namespace xf {
@@ -70,6 +78,9 @@ int table_head_rows(const uint64_t *d_keys_sorted, const uint32_t *d_order,
                     const uint32_t *d_rows, size_t n, uint32_t *d_hrow, hipStream_t s);
 int table_update_heads(xf_table *t, const uint32_t *d_hrow, const uint32_t *d_order, size_t n,
                        const float *d_grads, hipStream_t s);
+int table_update_heads_masked(xf_table *t, const uint32_t *d_hrow, const uint32_t *d_order,
+                              size_t n, const float *d_grads, const uint64_t *d_mask, int k,
+                              hipStream_t s);
 void table_set_init(xf_table *t, int kind, float init_const, uint64_t seed);
 }  // namespace xf
 
@@ -141,6 +152,9 @@ struct StepBuf {
   Dev<float> w_send, wu, g, g_recv, loss, vsum;
   Dev<char> ks;  // FM: the per-key records of the forward
   Dev<float> v_send, vu, gv, gv_recv;
+  Dev<float> S;           // canonical FM: the forward's per-factor row sums [R x k]
+  Dev<double> hpart;      // canonical / field-aware FM, valued LR: the heavy keys' chunk sums
+  Dev<uint64_t> mask, mask_recv;  // field-aware FM: the keys' touched fields, sent with gv
 };
 
 struct xf_sbatch {
@@ -388,7 +402,43 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     XF_TRY(a2a(st, B.v_send.p, b->recv_counts, B.vu.p, b->send_counts, 4 * (size_t)k, s));
   }
   XF_MARK(kEvA2aW + 1);
-  if (!fm) {
+  const xf_batch *hb = b->b;
+  const xf_dev_batch &v = hb->view;
+  if (!fm && hb->valued) {
+    // valued LR: the w half of the canonical step (xf_valued.hip), no cells
+    XF_TRY(xf::val_lr_forward(&v, hb->d_xval, B.wu.p, B.loss.p, d_pctr, s));
+    XF_MARK(kEvForward + 1);
+    if (want_grad) {
+      XF_TRY(B.g.reserve(b->U));
+      XF_TRY(B.hpart.reserve(xf::fmc_heavy_doubles(&v, 0)));
+      XF_TRY(xf::val_lr_grad_emit(&v, hb->d_coo_val, B.loss.p, B.g.p, B.hpart.p, s));
+    }
+  } else if (fm && st->fm_mode == XF_FM_CANONICAL) {
+    XF_TRY(B.S.reserve((size_t)b->R * k));
+    XF_TRY(xf::fmc_forward(&v, k, B.wu.p, B.vu.p, B.S.p, B.loss.p, d_pctr,
+                           hb->valued ? hb->d_xval : nullptr, s));
+    XF_MARK(kEvForward + 1);
+    if (want_grad) {
+      XF_TRY(B.g.reserve(b->U));
+      XF_TRY(B.gv.reserve((size_t)b->U * k));
+      XF_TRY(B.hpart.reserve(xf::fmc_heavy_doubles(&v, k)));
+      XF_TRY(xf::fmc_grad_emit(&v, k, B.vu.p, B.S.p, B.loss.p, B.g.p, B.gv.p, B.hpart.p,
+                               hb->valued ? hb->d_coo_val : nullptr, s));
+    }
+  } else if (fm && st->fm_mode == XF_FM_FIELD_AWARE) {
+    const int F = st->fm_fields, kf = k / F;  // (k: the v rows' width, fields x kf)
+    XF_TRY(xf::ffm_forward(&v, kf, F, B.wu.p, B.vu.p, hb->d_xfg, B.loss.p, d_pctr,
+                           hb->valued ? hb->d_xval : nullptr, s));
+    XF_MARK(kEvForward + 1);
+    if (want_grad) {
+      XF_TRY(B.g.reserve(b->U));
+      XF_TRY(B.gv.reserve((size_t)b->U * k));
+      XF_TRY(B.mask.reserve(b->U));
+      XF_TRY(B.hpart.reserve(xf::ffm_heavy_doubles(&v, k)));
+      XF_TRY(xf::ffm_grad_emit(&v, kf, F, B.vu.p, hb->d_xfg, hb->d_coo_pos, B.loss.p, B.g.p,
+                               B.gv.p, B.mask.p, B.hpart.p, hb->valued ? hb->d_xval : nullptr, s));
+    }
+  } else if (!fm) {
     XF_TRY(st->partial.reserve(xf::cells_partial_doubles(b->cells)));
     XF_TRY(xf::cells_lr_forward(b->cells, B.wu.p, b->b->view.labels, st->partial.p, B.loss.p,
                                 d_pctr, s));
@@ -423,6 +473,10 @@ int back_exchange(xf_sharded *st, xf_sbatch *b, StepBuf &B, hipStream_t s) {
   if (st->cfg.model == 1) {
     XF_TRY(B.gv_recv.reserve(b->n_recv * st->cfg.k));
     XF_TRY(a2a(st, B.gv.p, b->send_counts, B.gv_recv.p, b->recv_counts, 4 * (size_t)st->cfg.k, s));
+    if (st->fm_mode == XF_FM_FIELD_AWARE) {  // which fields of a key each source touched
+      XF_TRY(B.mask_recv.reserve(b->n_recv));
+      XF_TRY(a2a(st, B.mask.p, b->send_counts, B.mask_recv.p, b->recv_counts, 8, s));
+    }
   }
   return XF_OK;
 }
@@ -432,8 +486,39 @@ int back_exchange(xf_sharded *st, xf_sbatch *b, StepBuf &B, hipStream_t s) {
 int back_apply(xf_sharded *st, xf_sbatch *b, StepBuf &B, hipStream_t s) {
   if (!b->n_recv) return XF_OK;
   XF_TRY(xf::table_update_heads(st->tw, b->hrow_w.p, b->rorder.p, b->n_recv, B.g_recv.p, s));
-  if (st->cfg.model == 1)
+  if (st->cfg.model == 1 && st->fm_mode == XF_FM_FIELD_AWARE)
+    XF_TRY(xf::table_update_heads_masked(st->tv, b->hrow_v.p, b->rorder.p, b->n_recv,
+                                         B.gv_recv.p, B.mask_recv.p,
+                                         st->cfg.k / st->fm_fields, s));
+  else if (st->cfg.model == 1)
     XF_TRY(xf::table_update_heads(st->tv, b->hrow_v.p, b->rorder.p, b->n_recv, B.gv_recv.p, s));
+  return XF_OK;
+}
+
+// does the minibatch carry what the trainer's form reads?  (before any exchange: every rank
+// holds a minibatch of the same kind, so every rank answers alike)
+int form_check(const xf_sharded *st, const xf_sbatch *b, const char *who) {
+  const xf_batch *hb = b->b;
+  XF_REQUIRE(hb, "%s: the minibatch holds no key list", who);
+  const bool fm = st->cfg.model == 1;
+  XF_REQUIRE(!hb->valued || !fm || st->fm_mode != XF_FM_REFERENCE,
+             "%s: a minibatch with feature values (feature_values) needs fm_mode = canonical or "
+             "field_aware", who);
+  XF_REQUIRE(!hb->valued || hb->NNZ == 0 || (hb->d_xval && hb->d_coo_val),
+             "%s: a minibatch with feature values (feature_values) without its value arrays", who);
+  if (fm && st->fm_mode == XF_FM_FIELD_AWARE) {
+    XF_REQUIRE(hb->fields > 0, "%s: field-aware FM needs a minibatch compiled with its fields "
+               "(xf_sharded_compile_fielded*): this one was compiled without fields", who);
+    XF_REQUIRE(hb->fields == st->fm_fields, "%s: the minibatch was compiled with fields = %d, "
+               "the trainer runs fields = %d", who, hb->fields, st->fm_fields);
+    XF_REQUIRE(hb->NNZ == 0 || (hb->d_xfg && hb->d_coo_pos),
+               "%s: a minibatch with fields without its field arrays", who);
+  }
+  if ((fm && st->fm_mode != XF_FM_REFERENCE) || hb->valued)
+    XF_REQUIRE(hb->U == 0 || (hb->view.uidx && hb->view.tile_ptr),
+               "%s: the minibatch has no index of its key list or no gradient tiles", who);
+  else if (!fm)
+    XF_REQUIRE(b->cells, "%s: an LR minibatch without its cells", who);
   return XF_OK;
 }
 
@@ -1386,7 +1471,9 @@ static int compile_exchange_tail(xf_sharded *st, xf_sbatch *b, int keep) {
   hipStream_t s = st->main;
   XF_TRY(xf_batch_dims(b->b, &b->R, &b->NNZ, &b->U, nullptr));
   const xf_dev_batch &v = b->b->view;
-  if (st->cfg.model == 0 && !b->cells)  // the LR kernels stream cells over the batch's unique-key index
+  // the LR kernels stream cells over the batch's unique-key index (a valued minibatch has its own
+  // kernels, xf_valued.hip: no cells)
+  if (st->cfg.model == 0 && !b->cells && !b->b->valued)
     XF_TRY(xf::cells_build(&b->cells, v.uidx, nullptr, v.rowptr, b->R, b->NNZ, b->U,
                            xf::kCellsUidx, keep != 0, s));
   const int W = st->world;
@@ -1533,11 +1620,53 @@ extern "C" int xf_sharded_compile(xf_sharded *st, xf_sbatch **out, const uint64_
   return XF_OK;
 }
 
-// Feature values: a valued minibatch always takes the generic build, and steps on one rank only
+static const char *schedule_name(int schedule) {
+  switch (schedule) {
+    case XF_SCHEDULE_SEQUENTIAL: return "sequential";
+    case XF_SCHEDULE_STALE1: return "stale1";
+    case XF_SCHEDULE_OWNER: return "owner";
+    case XF_SCHEDULE_OWNER_STALE1: return "owner_stale1";
+  }
+  return "?";
+}
+
+// The forms beyond the reference's — canonical and field-aware FM, feature values — run where
+// whole rows are at hand: the fused one-rank step, and the weight / gradient exchange of the
+// schedules sequential and stale1.  The owner-compute dataflow moves the reference form's pooled
+// row sums (and sum_then_step exists only there).
+static int rows_at_hand(const xf_sharded *st, const char *who, const char *what) {
+  XF_REQUIRE(st->fused || !owner_dataflow(st->cfg.schedule),
+             "%s: %s on several ranks (world %d) run on the schedules sequential and stale1, "
+             "which exchange whole rows; schedule %s (the owner-compute dataflow) exchanges the "
+             "reference form's pooled row sums", who, what, st->world,
+             schedule_name(st->cfg.schedule));
+  return XF_OK;
+}
+
+// A fielded minibatch was built (or not: rc, the fgid range check above all) on this rank; the
+// ranks are about to exchange its keys.  A rank that entered the exchange while a peer had
+// returned with an error would wait there until the collective's timeout, so the ranks first tell
+// one another how the build went and all leave together when it failed anywhere.  This is one more
+// small host all-gather per fielded compile, ahead of the one compile_exchange_tail opens with
+// (the status could ride in that one).  Only the fielded compiles agree this way: a valued or
+// plain build that fails on one rank alone (out of memory, say) still leaves its peers in the
+// tail until the timeout, as before.
+static int build_agreed(xf_sharded *st, int rc, const char *who) {
+  if (st->fused) return rc;
+  std::vector<int64_t> all((size_t)st->world);
+  const int64_t mine = rc;
+  XF_TRY(xf_group_allgather_host(st->g, &mine, 8, all.data()));
+  if (rc != XF_OK) return rc;  // (this rank's own message stands)
+  for (int p = 0; p < st->world; ++p)
+    XF_REQUIRE(all[(size_t)p] == XF_OK,
+               "%s: rank %d could not build its minibatch (error %d there): no rank steps it", who,
+               p, (int)all[(size_t)p]);
+  return XF_OK;
+}
+
+// Feature values: a valued minibatch always takes the generic build
 static int valued_trainer_check(const xf_sharded *st, const char *who) {
-  XF_REQUIRE(st->world == 1 && st->fused && st->ws,
-             "%s: feature values (feature_values) run on one worker only (world %d)", who,
-             st->world);
+  XF_TRY(rows_at_hand(st, who, "feature values (feature_values)"));
   XF_REQUIRE(st->cfg.model == 0 || st->fm_mode != XF_FM_REFERENCE,
              "%s: feature values (feature_values) with FM need fm_mode = canonical or field_aware "
              "(xf_sharded_set_fm_mode)", who);
@@ -1550,7 +1679,6 @@ extern "C" int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const 
                                          const uint64_t *keys, const float *vals,
                                          const int32_t *labels, size_t row_begin, size_t row_end,
                                          int keep) {
-  (void)keep;  // (the generic minibatch is replayable as it is)
   XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
              "xf_sharded_compile_valued: bad argument");
   XF_ALIVE(st);
@@ -1568,7 +1696,11 @@ extern "C" int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const 
   else
     XF_TRY(xf_batch_compile_valued_gpu(&b->b, rowptr, keys, vals, labels, row_begin, row_end,
                                        st->main));
-  XF_TRY(fused_room(st, b));
+  if (st->fused) XF_TRY(fused_room(st, b));
+  else {
+    if (st->cfg.host_key_build) XF_TRY(xf_batch_upload(b->b, st->main));
+    XF_TRY(compile_exchange_tail(st, b, keep));
+  }
   guard.b = nullptr;
   *out = b;
   return XF_OK;
@@ -1578,7 +1710,6 @@ extern "C" int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out,
                                              const uint64_t *d_keys, const float *d_vals,
                                              const uint32_t *d_rowptr, const int32_t *d_labels,
                                              uint32_t R, uint32_t NNZ, int keep) {
-  (void)keep;
   XF_REQUIRE(st && out && d_rowptr && d_vals && (R == 0 || d_labels) && (NNZ == 0 || d_keys),
              "xf_sharded_compile_valued_dev: null argument");
   XF_ALIVE(st);
@@ -1594,17 +1725,18 @@ extern "C" int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out,
   } guard{b};
   b->owner = st;
   XF_TRY(xf_batch_compile_valued_dev(&b->b, d_keys, d_vals, d_rowptr, d_labels, R, NNZ, st->main));
-  XF_TRY(fused_room(st, b));
+  if (st->fused) XF_TRY(fused_room(st, b));
+  else
+    XF_TRY(compile_exchange_tail(st, b, keep));
   guard.b = nullptr;
   *out = b;
   return XF_OK;
 }
 
-// Fields: a fielded minibatch always takes the generic build and steps on a one-rank trainer in
-// the field-aware form
+// Fields: a fielded minibatch always takes the generic build and steps on a trainer in the
+// field-aware form
 static int fielded_trainer_check(const xf_sharded *st, bool valued, const char *who) {
-  XF_REQUIRE(st->world == 1 && st->fused && st->ws,
-             "%s: field-aware FM runs on one worker only (world %d)", who, st->world);
+  XF_TRY(rows_at_hand(st, who, "field-aware FM (fm_mode = field_aware)"));
   XF_REQUIRE(st->cfg.model == 1 && st->fm_mode == XF_FM_FIELD_AWARE,
              "%s: a minibatch with fields is for fm_mode = field_aware (xf_sharded_set_fm_fields, "
              "xf_sharded_set_fm_mode)", who);
@@ -1616,7 +1748,6 @@ extern "C" int xf_sharded_compile_fielded(xf_sharded *st, xf_sbatch **out, const
                                           const uint64_t *keys, const int32_t *fgid,
                                           const float *vals, const int32_t *labels,
                                           size_t row_begin, size_t row_end, int keep) {
-  (void)keep;  // (the generic minibatch is replayable as it is)
   XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
              "xf_sharded_compile_fielded: bad argument");
   XF_ALIVE(st);
@@ -1629,13 +1760,20 @@ extern "C" int xf_sharded_compile_fielded(xf_sharded *st, xf_sbatch **out, const
     }
   } guard{b};
   b->owner = st;
+  // (the fgid range check is the build's first act: a failure is agreed on before any exchange)
+  int rc;
   if (st->cfg.host_key_build)
-    XF_TRY(xf_batch_compile_fielded(&b->b, rowptr, keys, fgid, vals, labels, row_begin, row_end,
-                                    st->fm_fields));
+    rc = xf_batch_compile_fielded(&b->b, rowptr, keys, fgid, vals, labels, row_begin, row_end,
+                                  st->fm_fields);
   else
-    XF_TRY(xf_batch_compile_fielded_gpu(&b->b, rowptr, keys, fgid, vals, labels, row_begin,
-                                        row_end, st->fm_fields, st->main));
-  XF_TRY(fused_room(st, b));
+    rc = xf_batch_compile_fielded_gpu(&b->b, rowptr, keys, fgid, vals, labels, row_begin, row_end,
+                                      st->fm_fields, st->main);
+  XF_TRY(build_agreed(st, rc, "xf_sharded_compile_fielded"));
+  if (st->fused) XF_TRY(fused_room(st, b));
+  else {
+    if (st->cfg.host_key_build) XF_TRY(xf_batch_upload(b->b, st->main));
+    XF_TRY(compile_exchange_tail(st, b, keep));
+  }
   guard.b = nullptr;
   *out = b;
   return XF_OK;
@@ -1646,7 +1784,6 @@ extern "C" int xf_sharded_compile_fielded_dev(xf_sharded *st, xf_sbatch **out,
                                               const float *d_vals, const uint32_t *d_rowptr,
                                               const int32_t *d_labels, uint32_t R, uint32_t NNZ,
                                               int keep) {
-  (void)keep;
   XF_REQUIRE(st && out && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || (d_keys && d_fgid)),
              "xf_sharded_compile_fielded_dev: null argument");
   XF_ALIVE(st);
@@ -1661,9 +1798,12 @@ extern "C" int xf_sharded_compile_fielded_dev(xf_sharded *st, xf_sbatch **out,
     }
   } guard{b};
   b->owner = st;
-  XF_TRY(xf_batch_compile_fielded_dev(&b->b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ,
-                                      st->fm_fields, st->main));
-  XF_TRY(fused_room(st, b));
+  const int rc = xf_batch_compile_fielded_dev(&b->b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R,
+                                              NNZ, st->fm_fields, st->main);
+  XF_TRY(build_agreed(st, rc, "xf_sharded_compile_fielded_dev"));
+  if (st->fused) XF_TRY(fused_room(st, b));
+  else
+    XF_TRY(compile_exchange_tail(st, b, keep));
   guard.b = nullptr;
   *out = b;
   return XF_OK;
@@ -1727,6 +1867,7 @@ extern "C" int xf_sharded_step(xf_sharded *st, xf_sbatch *b) {
   }
   if (owner_dataflow(st->cfg.schedule)) return step_owner(st, b);
   XF_REQUIRE(!b->oc, "xf_sharded_step: the minibatch was compiled for the owner-compute dataflow");
+  XF_TRY(form_check(st, b, "xf_sharded_step"));
   XF_TRY(begin_profiled_step(st));
   const int flip = b->flip;
   b->flip ^= 1;
@@ -1805,6 +1946,7 @@ extern "C" int xf_sharded_predict(xf_sharded *st, xf_sbatch *b, float *pctr_out)
   }
   XF_REQUIRE(!b->oc, "xf_sharded_predict: the minibatch was compiled for the owner-compute "
              "dataflow");
+  XF_TRY(form_check(st, b, "xf_sharded_predict"));
   StepBuf &B = b->buf[b->flip];
   Dev<float> pctr;
   XF_TRY(pctr.reserve(b->R));
@@ -1918,9 +2060,8 @@ extern "C" int xf_sharded_set_fm_mode(xf_sharded *st, int mode) {
              "xf_sharded_set_fm_mode: mode must be XF_FM_REFERENCE (0), XF_FM_CANONICAL (1) or "
              "XF_FM_FIELD_AWARE (2)");
   XF_REQUIRE(st->cfg.model == 1 && st->tv, "xf_sharded_set_fm_mode: not an FM trainer");
-  XF_REQUIRE(st->world == 1 && st->fused && st->ws,
-             "xf_sharded_set_fm_mode: canonical and field-aware FM run on one rank only (world "
-             "%d): the exchanges of several ranks carry the reference form's row sums", st->world);
+  if (mode != XF_FM_REFERENCE)
+    XF_TRY(rows_at_hand(st, "xf_sharded_set_fm_mode", "canonical and field-aware FM"));
   if (mode == XF_FM_FIELD_AWARE) {
     XF_REQUIRE(st->fm_fields, "xf_sharded_set_fm_mode: field-aware FM needs its number of fields "
                "first (xf_sharded_set_fm_fields)");
@@ -1936,7 +2077,9 @@ extern "C" int xf_sharded_set_fm_mode(xf_sharded *st, int mode) {
   XF_REQUIRE(nw == 0 && nv == 0,
              "xf_sharded_set_fm_mode: the tables hold keys already (%llu, %llu): set the FM form "
              "before the first step", (unsigned long long)nw, (unsigned long long)nv);
-  XF_TRY(xf_workspace_fm_mode(st->ws, mode));
+  // (the fused step reads the form from its workspace; the exchange path has none: front_compute
+  // and back_apply read it from the trainer)
+  if (st->fused) XF_TRY(xf_workspace_fm_mode(st->ws, mode));
   // canonical: hash-normal factors for both optimizers (SGD's constant init would give every
   // factor of a key the same gradient forever); the reference form keeps sgd.h:67-72
   if (st->cfg.optimizer == XF_OPT_SGD) {
@@ -1950,11 +2093,15 @@ extern "C" int xf_sharded_set_fm_mode(xf_sharded *st, int mode) {
 
 extern "C" int xf_sharded_set_fm_fields(xf_sharded *st, int fields) {
   XF_REQUIRE(st, "xf_sharded_set_fm_fields: null trainer");
-  XF_REQUIRE(st->cfg.model == 1 && st->tv && st->ws, "xf_sharded_set_fm_fields: not a one-rank FM trainer");
+  XF_REQUIRE(st->cfg.model == 1 && st->tv, "xf_sharded_set_fm_fields: not an FM trainer");
   XF_REQUIRE(st->fm_mode != XF_FM_FIELD_AWARE,
              "xf_sharded_set_fm_fields: the trainer runs field-aware FM already: set the fields "
              "before the form");
-  XF_TRY(xf_workspace_fm_fields(st->ws, fields));
+  if (st->fused) XF_TRY(xf_workspace_fm_fields(st->ws, fields));
+  else
+    XF_REQUIRE(fields >= 1 && fields <= 64,
+               "xf_sharded_set_fm_fields: fields must be in 1 .. 64 (a key's touched fields are "
+               "one 64-bit mask), not %d", fields);
   st->fm_fields = fields;
   return XF_OK;
 }

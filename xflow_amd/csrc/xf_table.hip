@@ -594,6 +594,49 @@ k_update_heads(xf::TableDev T, const uint32_t *__restrict__ hrow,
   }
 }
 
+// k_update_heads for the field-aware v table (dim = fields x k, coordinate (h, f) at h k + f):
+// mask[p] holds the fields that the minibatch behind push p touched, and push p steps
+// coordinate j only when bit j / k is set — an FTRL step with g = 0 would erase the hash-normal
+// init of a field that source has not met (xf_ffm.hip).  A coordinate's (n, z) are still loaded
+// once and stored once; a coordinate that no source touched is not stored at all, so its
+// (w, n, z) keep their bits.
+template <int OPT>
+__global__ void __launch_bounds__(kBlock)
+k_update_heads_masked(xf::TableDev T, const uint32_t *__restrict__ hrow,
+                      const uint32_t *__restrict__ order, size_t n,
+                      const float *__restrict__ grads,
+                      const unsigned long long *__restrict__ mask, uint32_t k) {
+  const size_t total = n * (size_t)T.dim;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    const size_t i = e / (size_t)T.dim;
+    const size_t j = e - i * (size_t)T.dim;
+    const uint32_t row = hrow[i];
+    if (row == kNotHead) continue;  // a later push of a key whose first entry does the walk
+    const size_t o = (size_t)row * T.dim + j;
+    const uint32_t h = (uint32_t)j / k;
+    bool any = false;
+    float w = T.w[o], nn = 0.0f, z = 0.0f;
+    if (OPT == XF_OPT_FTRL) xf::load_nz(T, o, nn, z);
+    size_t s = i;
+    do {
+      const uint32_t p = order[s];
+      if ((mask[p] >> h) & 1ull) {
+        const float g = grads[(size_t)p * T.dim + j];
+        if (OPT == XF_OPT_FTRL)
+          xf::ftrl_step(T.alpha, T.inv_alpha, T.beta, T.lambda1, T.lambda2, g, w, nn, z);
+        else
+          w = xf::sgd_step(T.lr, g, w);
+        any = true;
+      }
+      ++s;
+    } while (s < n && hrow[s] == kNotHead);
+    if (!any) continue;
+    T.w[o] = w;
+    if (OPT == XF_OPT_FTRL) xf::store_nz(T, o, nn, z);
+  }
+}
+
 // export / import of one FTRL accumulator (comp 0 = n, 1 = z)
 __global__ void __launch_bounds__(kBlock)
 k_gather_nz(const float2 *__restrict__ nz, int comp, int dim, const uint32_t *__restrict__ rows,
@@ -2296,6 +2339,26 @@ int table_update_heads(xf_table *t, const uint32_t *d_hrow, const uint32_t *d_or
     hipLaunchKernelGGL(k_update_heads<XF_OPT_FTRL>, g, b, 0, s, t->T, d_hrow, d_order, n, d_grads);
   else
     hipLaunchKernelGGL(k_update_heads<XF_OPT_SGD>, g, b, 0, s, t->T, d_hrow, d_order, n, d_grads);
+  XF_HIP(hipGetLastError());
+  return XF_OK;
+}
+// ... of the field-aware v table: d_mask[p] = the fields push p touched (its 64 bits), k = the
+// width of one field's vector (t's dim = fields x k); untouched coordinates are not written
+int table_update_heads_masked(xf_table *t, const uint32_t *d_hrow, const uint32_t *d_order,
+                              size_t n, const float *d_grads, const uint64_t *d_mask, int k,
+                              hipStream_t s) {
+  if (n == 0) return XF_OK;
+  XF_REQUIRE(d_mask && k >= 1 && t->T.dim % k == 0 && t->T.dim / k <= 64,
+             "table_update_heads_masked: dim %d is not (at most 64 fields) x k = %d", t->T.dim, k);
+  ++t->writes;
+  const dim3 g(grid_for(n * t->T.dim)), b(kBlock);
+  const unsigned long long *m = (const unsigned long long *)d_mask;
+  if (t->cfg.opt_kind == XF_OPT_FTRL)
+    hipLaunchKernelGGL(k_update_heads_masked<XF_OPT_FTRL>, g, b, 0, s, t->T, d_hrow, d_order, n,
+                       d_grads, m, (uint32_t)k);
+  else
+    hipLaunchKernelGGL(k_update_heads_masked<XF_OPT_SGD>, g, b, 0, s, t->T, d_hrow, d_order, n,
+                       d_grads, m, (uint32_t)k);
   XF_HIP(hipGetLastError());
   return XF_OK;
 }

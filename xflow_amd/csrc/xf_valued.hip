@@ -67,6 +67,7 @@ k_val_lr_forward(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict
 
 // ------------------------------------------------------------- gradient + Push, LR
 // the w half of k_fmc_grad_tiled<OPT, K, true>: a tile's loss x in LDS, a lane per key
+// (OPT = xf::kOptEmit: gw[u] written and nothing stepped — TW, wu and rows_w are not read)
 template <int OPT>
 __global__ void __launch_bounds__(kBlock)
 k_val_lr_grad_tiled(xf::TableDev TW, const uint32_t *__restrict__ tile_ptr, uint32_t ntiles,
@@ -90,7 +91,7 @@ k_val_lr_grad_tiled(xf::TableDev TW, const uint32_t *__restrict__ tile_ptr, uint
       for (uint32_t j = sp[q]; j < sp[q + 1]; ++j) aw += (double)lx[j];
       const float g1 = xf::div_by_rows((float)aw, R);
       gw[ua + q] = g1;
-      xf::step_coord<OPT>(TW, rows_w[ua + q], wu[ua + q], g1);
+      if constexpr (OPT != xf::kOptEmit) xf::step_coord<OPT>(TW, rows_w[ua + q], wu[ua + q], g1);
     }
     __syncthreads();
   }
@@ -111,6 +112,32 @@ int val_lr_forward(const xf_dev_batch *b, const float *d_xval, const float *d_wu
   return XF_OK;
 }
 
+// the tile kernel and the heavy keys' two for one OPT (an optimizer, or kOptEmit)
+static int val_lr_grad_launch(int opt, const TableDev &TW, const xf_dev_batch *b,
+                              const float *d_coo_val, const uint32_t *d_rows_w, const float *d_wu,
+                              const float *d_loss, float *d_gw, double *d_hpart, hipStream_t s) {
+  XF_REQUIRE(b->ntiles && b->tile_ptr, "valued lr gradient: the minibatch has no gradient tiles");
+  XF_REQUIRE(!b->H || (b->heavy_chunk_ptr && d_hpart),
+             "valued lr gradient: heavy keys without their chunks or scratch");
+  const dim3 gt((unsigned)std::min<uint32_t>(b->ntiles, 1u << 16)), blk(kBlock);
+  if (opt == kOptEmit)
+    hipLaunchKernelGGL(k_val_lr_grad_tiled<kOptEmit>, gt, blk, 0, s, TW, b->tile_ptr, b->ntiles,
+                       b->segptr, b->coo_row, d_coo_val, d_loss, d_wu, d_rows_w, b->R, d_gw);
+  else if (opt == XF_OPT_FTRL)
+    hipLaunchKernelGGL(k_val_lr_grad_tiled<XF_OPT_FTRL>, gt, blk, 0, s, TW, b->tile_ptr, b->ntiles,
+                       b->segptr, b->coo_row, d_coo_val, d_loss, d_wu, d_rows_w, b->R, d_gw);
+  else
+    hipLaunchKernelGGL(k_val_lr_grad_tiled<XF_OPT_SGD>, gt, blk, 0, s, TW, b->tile_ptr, b->ntiles,
+                       b->segptr, b->coo_row, d_coo_val, d_loss, d_wu, d_rows_w, b->R, d_gw);
+  XF_HIP(hipGetLastError());
+  if (b->H) {
+    fmc_heavy_update(opt, TW, TW, 0, b, d_rows_w, d_rows_w, d_wu, d_wu, nullptr, d_loss, d_gw,
+                     nullptr, d_hpart, d_coo_val, s);
+    XF_HIP(hipGetLastError());
+  }
+  return XF_OK;
+}
+
 // gradient + Push of w with the values in key-grouped order.  d_hpart: n_heavy_chunks doubles
 // (fmc_heavy_doubles(b, 0)).
 int val_lr_grad_update(xf_table *tw, const xf_dev_batch *b, const float *d_coo_val,
@@ -120,23 +147,20 @@ int val_lr_grad_update(xf_table *tw, const xf_dev_batch *b, const float *d_coo_v
              "valued lr gradient: null argument");
   if (b->U == 0) return XF_OK;
   const xf::TableDev &TW = xf::table_dev(tw);
-  XF_REQUIRE(b->ntiles && b->tile_ptr, "valued lr gradient: the minibatch has no gradient tiles");
-  XF_REQUIRE(!b->H || (b->heavy_chunk_ptr && d_hpart),
-             "valued lr gradient: heavy keys without their chunks or scratch");
-  const dim3 gt((unsigned)std::min<uint32_t>(b->ntiles, 1u << 16)), blk(kBlock);
-  if (TW.nz != nullptr)
-    hipLaunchKernelGGL(k_val_lr_grad_tiled<XF_OPT_FTRL>, gt, blk, 0, s, TW, b->tile_ptr, b->ntiles,
-                       b->segptr, b->coo_row, d_coo_val, d_loss, d_wu, d_rows_w, b->R, d_gw);
-  else
-    hipLaunchKernelGGL(k_val_lr_grad_tiled<XF_OPT_SGD>, gt, blk, 0, s, TW, b->tile_ptr, b->ntiles,
-                       b->segptr, b->coo_row, d_coo_val, d_loss, d_wu, d_rows_w, b->R, d_gw);
-  XF_HIP(hipGetLastError());
-  if (b->H) {
-    fmc_heavy_update(TW, TW, 0, b, d_rows_w, d_rows_w, d_wu, d_wu, nullptr, d_loss, d_gw, d_hpart,
-                     d_coo_val, s);
-    XF_HIP(hipGetLastError());
-  }
-  return XF_OK;
+  return val_lr_grad_launch(TW.nz != nullptr ? XF_OPT_FTRL : XF_OPT_SGD, TW, b, d_coo_val, d_rows_w,
+                            d_wu, d_loss, d_gw, d_hpart, s);
+}
+
+// The gradient alone, for a worker whose keys live on other ranks (as fmc_grad_emit): gw[U],
+// every entry written; no table, state row or pulled w is read.
+int val_lr_grad_emit(const xf_dev_batch *b, const float *d_coo_val, const float *d_loss,
+                     float *d_gw, double *d_hpart, hipStream_t s) {
+  XF_REQUIRE(b, "valued lr gradient (emit): null argument");
+  if (b->U == 0) return XF_OK;  // (no key: nothing to write, and the arrays may be empty)
+  XF_REQUIRE(d_coo_val && d_loss && d_gw, "valued lr gradient (emit): null argument");
+  const TableDev none{};
+  return val_lr_grad_launch(kOptEmit, none, b, d_coo_val, nullptr, nullptr, d_loss, d_gw, d_hpart,
+                            s);
 }
 
 }  // namespace xf
