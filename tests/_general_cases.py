@@ -45,8 +45,10 @@ def values(rng, n, scale=1.0):
     return (x * np.float32(scale)).astype(np.float32)
 
 
-def _structure(case, Fd, i):
-    """minibatch i of a case: (rowptr, keys, fgid or None, labels) of the exact tests' streams"""
+def _structure(case, Fd, i, base=0):
+    """minibatch i of a case: (rowptr, keys, fgid or None, labels) of the exact tests' streams;
+    every generator's seed is moved by `base` (a rank's streams: tests/_sharded_general_checker.py)"""
+    i = base + i
     if case == "long_rows":
         rowptr, keys, fg, _, labels = F.stream(case, Fd, seed=i)[0]
         return rowptr, keys, fg, labels
@@ -62,17 +64,17 @@ def _structure(case, Fd, i):
     return rowptr, keys, fg, labels
 
 
-def stream(case, fields=0, steps=STEPS):
+def stream(case, fields=0, steps=STEPS, base=0):
     out = []
     for i in range(steps):
-        rowptr, keys, fg, labels = _structure(case, fields, i)
-        rng = np.random.RandomState(5000 + i)
+        rowptr, keys, fg, labels = _structure(case, fields, i, base)
+        rng = np.random.RandomState(5000 + base + i)
         out.append((rowptr, keys, fg,
                     values(rng, len(keys), 0.125 if case == "long_rows" else 1.0), labels))
     return out
 
 
-def underflow_stream(fields=0):
+def underflow_stream(fields=0, base=0):
     """two ragged minibatches; the second is the underflow one: one row in ten carries values
     2^-63 of the others' (v x near 2^-70: the squares fp32((v x)^2), fp32(S^2) and the pair
     products land in fp32's denormal range and below it, an exact 0) or 2^-120 of them (w x,
@@ -80,9 +82,9 @@ def underflow_stream(fields=0):
     that sits half way between two fp32 values decides the rounding of S[r,f] in exact arithmetic
     and is absorbed in fp64 — with single tiny values 5 to 17 of 3600 S were open, and no S may
     be.  The tiny rows' keys occur in other rows too, so gw and gv mix both magnitudes."""
-    mbs = stream("ragged", fields, steps=2)
+    mbs = stream("ragged", fields, steps=2, base=base)
     rowptr, keys, fg, vals, labels = mbs[1]
-    rng = np.random.RandomState(77)
+    rng = np.random.RandomState(77 + base)
     u = rng.rand(len(labels))
     scale = np.where(u < 0.05, 2.0 ** -63, np.where(u < 0.1, 2.0 ** -120, 1.0)).astype(np.float32)
     vals = vals * np.repeat(scale, np.diff(rowptr.astype(np.int64)))
