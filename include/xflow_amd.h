@@ -383,6 +383,22 @@ int xf_table_reserve(xf_table *t, uint64_t new_capacity);
  * second state buffer of the same size from its first call on (the two swap roles: no
  * allocation, no clearing per call). */
 int xf_table_defrag(xf_table *t);
+/* which way the table's last xf_table_defrag call put the arrival index's keys in order
+ * (read-only, for tests and profiles): XF_DEFRAG_NONE when it found nothing to move (or before
+ * the first call); XF_DEFRAG_SORTFREE the index read front to back, block by block; the radix
+ * sort of every key because xf_tune("key_build", 1) asked for it or the table is beyond 2^38
+ * positions (_ASKED), because a block's last cluster ran on for more than 32768 positions
+ * (_EXTENT), because the blocks' counts did not add up to the keys the index holds (_COUNT), or
+ * because a cluster held more than 1024 keys (_CLUSTER) */
+enum {
+  XF_DEFRAG_NONE = 0,
+  XF_DEFRAG_SORTFREE = 1,
+  XF_DEFRAG_RADIX_ASKED = 2,
+  XF_DEFRAG_RADIX_EXTENT = 3,
+  XF_DEFRAG_RADIX_COUNT = 4,
+  XF_DEFRAG_RADIX_CLUSTER = 5
+};
+int xf_table_defrag_path(xf_table *t, int *path);
 int xf_table_set_hyper(xf_table *t, float alpha, float beta, float l1, float l2, float lr);
 
 /* ps-lite-shaped host API: keys sorted & unique (the KVWorker contract), host pointers,

@@ -14,6 +14,9 @@ LIB_PATH = os.environ.get("XF_LIB") or os.path.join(_HERE, "lib", "libxflow_amd.
 XF_OK = 0
 OPT_FTRL, OPT_SGD = 0, 1
 INIT_ZERO, INIT_CONST, INIT_HASHNORM = 0, 1, 2
+# xf_table_defrag_path
+(DEFRAG_NONE, DEFRAG_SORTFREE, DEFRAG_RADIX_ASKED, DEFRAG_RADIX_EXTENT, DEFRAG_RADIX_COUNT,
+ DEFRAG_RADIX_CLUSTER) = range(6)
 HEAVY_SEG = 64
 FM_REFERENCE, FM_CANONICAL, FM_FIELD_AWARE = 0, 1, 2
 FM_MODES = {"reference": FM_REFERENCE, "canonical": FM_CANONICAL, "field_aware": FM_FIELD_AWARE}
@@ -161,6 +164,7 @@ SIGNATURES = {
     "xf_table_destroy": (C.c_int, [vp]),
     "xf_table_size": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "xf_table_settled": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
+    "xf_table_defrag_path": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "xf_table_prepare_defrag": (C.c_int, [vp]),
     "xf_table_capacity": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "xf_table_reserve": (C.c_int, [vp, C.c_uint64]),
@@ -786,6 +790,13 @@ class Table:
         n = C.c_uint64(0)
         check(lib().xf_table_settled(self.h, C.byref(n)))
         return n.value
+
+    @property
+    def defrag_path(self):
+        """how the last defrag() ordered the keys: one of the DEFRAG_* values"""
+        p = C.c_int(0)
+        check(lib().xf_table_defrag_path(self.h, C.byref(p)))
+        return p.value
 
     @property
     def capacity(self):

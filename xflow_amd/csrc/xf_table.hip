@@ -823,10 +823,28 @@ k_build_dirs(xf::TableDev T, const uint64_t *__restrict__ skeys, size_t n,
 //   k_df_merge  the sorted new keys merged with the settled tier's (merge path: one diagonal
 //               search per workgroup, the rest in LDS)
 // instead of a 64-bit radix sort of every key the table holds (8 passes over 12 bytes per key).
+// Who owns an entry: the block its cluster starts in.  A block skips its `lead` (the run at its
+// start that began before it) and follows its last cluster past its own end for `ext` positions
+// (through whole blocks, if need be: an inner block that is all lead owns nothing and does not
+// extend).
 // The one cluster that may wrap around the end of the index holds keys of both ends: an entry
-// whose home lies AFTER its position has wrapped (it belongs to the end), the others to block 0.
-// A cluster of more than kDfCluster keys (keys that are not hashes: one home for all) sets a
-// flag and the radix sort runs instead.
+// whose home lies AFTER its position has wrapped (it belongs to the end: to the block that
+// follows the cluster past the end of the index), the others are block 0's — in its own range
+// and, when the wrapped cluster covers ALL of block 0 (lead == len) and runs on into block 1, in
+// the extension that block 0 then follows like any other (df_owned).  Such a cluster holds more
+// than kDfBlock keys, so k_df_fix hands it to the radix sort all the same: completing the rule
+// only makes the blocks' counts add up there too (RADIX_CLUSTER, not RADIX_COUNT, below).
+// The radix sort of every key the table holds runs instead when
+//   - a cluster holds more than kDfCluster = 1024 keys (keys that are not hashes: one home for
+//     all, or a run of homes without a gap): k_df_fix sets the flag;
+//   - a block's last cluster runs on for more than 4 * kDfMax = 32768 positions: k_df_count
+//     sets the flag;
+//   - the blocks' counts do not add up to the keys the index holds: no layout is known to do
+//     that, the radix sort is right whatever the index looks like, and it holds its own count
+//     against the table's — the check that reports a corrupt index.  Such a fallback hides a
+//     wrong ownership decision as well as it covers for one: xf_table_defrag_path says which
+//     way a call went, and tests/test_gpu_defrag_layouts.py asserts it for every layout;
+//   - key_build = 1 (xf_tune) asks for it.
 constexpr uint32_t kDfBlock = 16384;  // index positions per block (a workgroup: 16 per thread)
 constexpr uint32_t kDfMax = 8192;    // (4 x this: how far a block follows its last cluster)
 constexpr int kDfThreads = 1024;
@@ -858,8 +876,10 @@ __device__ __forceinline__ DfBlock df_extent(const xf::TableDev &T, uint32_t b, 
   r.lead = pred_occ ? first_empty : 0u;
   r.ext = 0;
   // the block's last position is occupied and belongs to a cluster the block owns (or, block 0:
-  // to the wrapped cluster, whose far end then is the last block's): how far does it run on?
-  if (r.lead < len && T.keys[p1 - 1] != xf::kEmptyKey) {
+  // to the wrapped cluster, whose far end then is the last block's — also when that cluster
+  // covers ALL of block 0: what has not wrapped of it is block 0's wherever it sits): how far
+  // does it run on?
+  if ((r.lead < len || b == 0) && T.keys[p1 - 1] != xf::kEmptyKey) {
     if (tid < 64) {  // one wavefront, 64 positions at a time
       uint32_t ext = 0;
       for (;;) {  // wave-uniform
@@ -883,7 +903,10 @@ __device__ __forceinline__ DfBlock df_extent(const xf::TableDev &T, uint32_t b, 
 
 // is the entry at position p (key k) one of the block's?  In the block's own range: everything
 // past `lead` — and, block 0 only, the entries of the leading run that have NOT wrapped; in the
-// extension: everything, except that past the end of the index only the wrapped entries count
+// extension: everything, except that past the end of the index only the wrapped entries count.
+// Block 0 whose every position is lead (the wrapped cluster covers it and runs on into block 1)
+// extends all the same, and owns what has not wrapped there too: small keys displaced past the
+// wrapped run, which block 1 skips as its lead and the end, taking wrapped entries only, leaves.
 __device__ __forceinline__ bool df_owned(const xf::TableDev &T, uint32_t b, const DfBlock &e,
                                          uint32_t rel /* position - p0 */, uint64_t key,
                                          uint64_t *pos_out) {
@@ -894,7 +917,9 @@ __device__ __forceinline__ bool df_owned(const xf::TableDev &T, uint32_t b, cons
   *pos_out = p;
   if (key == xf::kEmptyKey) return false;
   if (past_end) return xf::home_of(T, key) > p;                      // wrapped: the end's
-  if (b == 0 && rel < e.lead) return xf::home_of(T, key) <= p;       // not wrapped: block 0's
+  // (block 0 is min(kDfBlock, cap) positions long: lead == that length, every position is lead)
+  if (b == 0 && (rel < e.lead || e.lead >= min((uint64_t)kDfBlock, T.cap)))
+    return xf::home_of(T, key) <= p;                                 // not wrapped: block 0's
   return rel >= e.lead;
 }
 
@@ -1199,6 +1224,7 @@ struct xf_table {
   float *w_alt = nullptr;
   float2 *nz_alt = nullptr;
   size_t alt_elems = 0;
+  int defrag_path = XF_DEFRAG_NONE;  // how the last xf_table_defrag ordered the keys
   // The keys the HOST API (xf_table_pull / xf_table_push) has put into a table without a settled
   // tier, while they are few (lr_worker.cc:180-182 pushes key 0 before the first minibatch).
   // When they are ALL the table holds — the key count says so — and no row number has left the
@@ -1544,6 +1570,12 @@ static int read_stat(xf_table *t, xf::TableStat *st) {
   return XF_OK;
 }
 
+extern "C" int xf_table_defrag_path(xf_table *t, int *path) {
+  XF_REQUIRE(t && path, "xf_table_defrag_path: null argument");
+  *path = t->defrag_path;
+  return XF_OK;
+}
+
 extern "C" int xf_table_settled(xf_table *t, uint64_t *nkeys) {
   XF_REQUIRE(t && nkeys, "xf_table_settled: null argument");
   *nkeys = t->T.nbase;
@@ -1648,6 +1680,7 @@ extern "C" int xf_table_reserve(xf_table *t, uint64_t new_capacity) {
 extern "C" int xf_table_defrag(xf_table *t) {
   XF_REQUIRE(t, "xf_table_defrag: null table");
   XF_HIP(hipDeviceSynchronize());
+  t->defrag_path = XF_DEFRAG_NONE;
   xf::TableStat st;
   XF_TRY(read_stat(t, &st));
   if (st.err) return xf_table_check(t, nullptr);
@@ -1676,6 +1709,7 @@ extern "C" int xf_table_defrag(xf_table *t) {
   // the index's keys in key order without a sort (kernels: "defrag without a library sort"):
   // into k_all / r_all, then merged with the settled tier's into k_sorted / r_sorted
   bool sorted_ok = false;
+  int path = XF_DEFRAG_RADIX_ASKED;  // (key_build = 1, or a table beyond the limits below)
   const uint64_t nblk64 = (T.cap + kDfBlock - 1) / kDfBlock;
   if (nblk64 < (1u << 24) && n_idx < 0xFFFFFFFFull && xf::key_build_mode() != 1) {
     const uint32_t nblk = (uint32_t)nblk64;
@@ -1690,10 +1724,13 @@ extern "C" int xf_table_defrag(xf_table *t) {
     uint32_t listed32 = 0;
     XF_HIP(hipMemcpy(&hflag, dflag, 4, hipMemcpyDeviceToHost));
     XF_HIP(hipMemcpy(&listed32, bcnt + nblk, 4, hipMemcpyDeviceToHost));
-    if (!hflag) {
-      if (listed32 != n_idx)
-        return xf::set_error(XF_EINVAL, "xf_table_defrag: index holds %u keys, %zu expected",
-                             listed32, n_idx);
+    // The blocks' counts add up to the keys of the index when every block decided rightly what is
+    // its own.  When they do not, the table need not be at fault — the ownership rule may be —
+    // and the radix path below sorts any index, so it runs; but it hides the cause, whatever it
+    // is: only xf_table_defrag_path tells (the tests hold it against every layout they craft),
+    // and only the radix path's own count, held against the table's, reports a corrupt index.
+    path = hflag ? XF_DEFRAG_RADIX_EXTENT : listed32 != n_idx ? XF_DEFRAG_RADIX_COUNT : path;
+    if (!hflag && listed32 == n_idx) {
       uint64_t *bk = T.nbase ? k_all : k_sorted;  // (no settled tier: nothing to merge with)
       uint32_t *br = T.nbase ? r_all : r_sorted;
       hipLaunchKernelGGL(k_df_list, dim3(nblk), dim3(kDfThreads), 0, 0, T, bcnt, bk, br, cstart);
@@ -1709,6 +1746,7 @@ extern "C" int xf_table_defrag(xf_table *t) {
         XF_HIP(hipGetLastError());
         sorted_ok = true;
       }
+      path = sorted_ok ? XF_DEFRAG_SORTFREE : XF_DEFRAG_RADIX_CLUSTER;
     }
   }
   if (!sorted_ok) {  // keys that are not hashes (one home for thousands of them): a radix sort
@@ -1765,6 +1803,7 @@ extern "C" int xf_table_defrag(xf_table *t) {
   N.nz = nz2;
   T = N;
   ++t->epoch;  // every row number handed out before this call is stale
+  t->defrag_path = path;
   return XF_OK;
 }
 
