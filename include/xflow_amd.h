@@ -779,6 +779,54 @@ int xf_sharded_profile_read(xf_sharded *st, double *ms_sum, long *steps);
 int xf_sharded_save(xf_sharded *st, const char *prefix);
 int xf_sharded_load(xf_sharded *st, const char *prefix);
 
+/* ---------------------------------------------------------------- feature admission    */
+/* A counting Bloom filter ahead of the key build (not in the reference; the FTRL paper's "Bloom
+ * filter inclusion"): a key enters the model only once the filter has seen it `count` times.  It
+ * filters a minibatch's CSR arrays: a nonzero whose key is not admitted is taken out of its row,
+ * the row keeps its label and its other nonzeros, and the result goes to any *_dev compile.
+ * State: 2^log2_slots saturating 8-bit counters in HBM, zero at creation; log2_slots in 2 .. 32,
+ * hashes in 1 .. 8, count in 1 .. 255.  slot_j(key) = mix64(key ^ mix64(seed + j)) >>
+ * (64 - log2_slots), j = 0 .. hashes - 1, mix64 = x += 0x9e3779b97f4a7c15, then the splitmix64
+ * finaliser (xf_admit_slot: 0 for a log2_slots or j outside the ranges).
+ * One apply = one minibatch, two phases.  Count (update != 0 only): every nonzero adds 1 to each
+ * of its `hashes` counters, saturating at `count`: c[s] = min(count, c_old[s] + #{(nonzero, j):
+ * slot_j(key) = s}) — two j of one key on one slot count twice per occurrence; independent of
+ * order.  Test and compact (after the whole count): a nonzero is kept iff all its counters equal
+ * `count`; kept nonzeros keep their order, rowptr is rebuilt, fgid / vals (may be NULL) are
+ * compacted with the keys.  update == 0 (predict) only reads the counters.  count = 1 with update
+ * keeps everything: the outputs equal the inputs byte for byte.
+ * xf_admit_apply_dev: device arrays (d_rowptr row-relative u32, R + 1).  The outputs are device
+ * arrays owned by the filter, valid until its next apply (NULL for fgid / vals that were not
+ * given); *NNZ_out = kept nonzeros.  Waits for the stream.  R = 0 and NNZ = 0 are valid.
+ * xf_admit_apply: the reader's host arrays and a row slice (as xf_batch_compile_gpu): uploads the
+ * slice (rowptr rebased to u32; labels, when given, to *d_labels_out unchanged) and runs the same
+ * kernels — there is one implementation, the device one.
+ * xf_admit_export / _import: the 2^log2_slots counters as bytes.  xf_admit_save / _load: a file
+ * whose header carries the four parameters; a load into a filter with other parameters is
+ * XF_EINVAL naming both sets, a missing or damaged file XF_EIO naming the path.
+ * xf_admit_stats: nonzeros seen / kept, summed over the update != 0 applies. */
+typedef struct xf_admit xf_admit;
+uint64_t xf_admit_slot(uint64_t key, uint64_t seed, int log2_slots, int j);
+int xf_admit_create(xf_admit **out, int log2_slots, int hashes, int count, uint64_t seed);
+int xf_admit_destroy(xf_admit *a);
+int xf_admit_params(const xf_admit *a, int *log2_slots, int *hashes, int *count, uint64_t *seed);
+int xf_admit_apply_dev(xf_admit *a, int update, const uint64_t *d_keys, const int32_t *d_fgid,
+                       const float *d_vals, const uint32_t *d_rowptr, uint32_t R, uint32_t NNZ,
+                       void *stream, const uint64_t **d_keys_out, const int32_t **d_fgid_out,
+                       const float **d_vals_out, const uint32_t **d_rowptr_out,
+                       uint32_t *NNZ_out);
+int xf_admit_apply(xf_admit *a, int update, const uint64_t *rowptr, const uint64_t *keys,
+                   const int32_t *fgid, const float *vals, const int32_t *labels,
+                   size_t row_begin, size_t row_end, void *stream, const uint64_t **d_keys_out,
+                   const int32_t **d_fgid_out, const float **d_vals_out,
+                   const uint32_t **d_rowptr_out, const int32_t **d_labels_out, uint32_t *R_out,
+                   uint32_t *NNZ_out);
+int xf_admit_export(xf_admit *a, uint8_t *counters);
+int xf_admit_import(xf_admit *a, const uint8_t *counters);
+int xf_admit_save(xf_admit *a, const char *path);
+int xf_admit_load(xf_admit *a, const char *path);
+int xf_admit_stats(const xf_admit *a, uint64_t *nonzeros_seen, uint64_t *nonzeros_kept);
+
 /* ---------------------------------------------------------------- metrics             */
 /* Base::calculate_auc (base.h:84-110): reference-format logloss (mean of y*log2 p +
  * (1-y)*log2(1-p), negative), AUC by descending-pctr rank sum, plus the conventional
@@ -813,7 +861,13 @@ int XFDestroy(void **h);
  *        ingest(host|gpu: the text of a block tokenised and hashed on the GPU, xf_ingest_*;
  *        blocks that are not of the common shape go to the host parser; core_num 1, no block
  *        cache.  gpu_fields: the same, and the tokeniser also reads fgid and the feature value
- *        when fm_mode=field_aware / feature_values=on need them, xf_ingest_set_fields).  XFGetMetric: ... blocks_gpu blocks_host (how the blocks were parsed) */
+ *        when fm_mode=field_aware / feature_values=on need them, xf_ingest_set_fields).  XFGetMetric: ... blocks_gpu blocks_host (how the blocks were parsed)
+ *        admit_count(0 off | 1 .. 255: feature admission, xf_admit_* — every block compiled from
+ *        text is counted and filtered before its key build, every test block filtered; a key
+ *        enters the tables once the filter has seen it that many times; one worker, core_num 1,
+ *        key_build=gpu, parity=exact) admit_log2_slots(2 .. 32, default 26) admit_hashes(1 .. 8,
+ *        default 3); the filter's seed is `seed`; XFSaveModel writes <path>.admit beside the
+ *        model, XFLoadModel needs it.  XFGetMetric: admit_seen admit_kept (nonzeros) */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

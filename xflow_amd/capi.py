@@ -3,6 +3,7 @@
 The library is the product; this module only marshals pointers.  It never falls back to
 a CPU implementation: a missing library or a missing GPU raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -243,6 +244,23 @@ SIGNATURES = {
     "xf_sharded_load": (C.c_int, [vp, C.c_char_p]),
     "xf_auc_logloss": (C.c_int, [i32p, f32p, C.c_size_t, f32p, f32p, C.POINTER(C.c_int),
                                  C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "xf_admit_slot": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int, C.c_int]),
+    "xf_admit_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_uint64]),
+    "xf_admit_destroy": (C.c_int, [vp]),
+    "xf_admit_params": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                  C.POINTER(C.c_uint64)]),
+    "xf_admit_apply_dev": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp,
+                                     C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                     C.POINTER(C.c_uint32)]),
+    "xf_admit_apply": (C.c_int, [vp, C.c_int, u64p, u64p, i32p, f32p, i32p, C.c_size_t,
+                                 C.c_size_t, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_uint32)]),
+    "xf_admit_export": (C.c_int, [vp, C.POINTER(C.c_uint8)]),
+    "xf_admit_import": (C.c_int, [vp, C.POINTER(C.c_uint8)]),
+    "xf_admit_save": (C.c_int, [vp, C.c_char_p]),
+    "xf_admit_load": (C.c_int, [vp, C.c_char_p]),
+    "xf_admit_stats": (C.c_int, [vp, u64p, u64p]),
     "XFCreate": (C.c_int, [C.POINTER(vp), C.c_char_p, C.c_char_p]),
     "XFStartTrain": (C.c_int, [C.POINTER(vp)]),
     "XFDestroy": (C.c_int, [C.POINTER(vp)]),
@@ -520,6 +538,117 @@ class Ingest:
             if a is not None and a.nbytes:
                 check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
         return True, rp, ks, lb, fg, vs
+
+
+def admit_slot(key, seed, log2_slots, j):
+    """slot_j(key) of a filter with this seed and 2^log2_slots counters (xf_admit_slot; host code)"""
+    return int(lib().xf_admit_slot(int(key), int(seed), int(log2_slots), int(j)))
+
+
+class AdmitDev(collections.namedtuple(
+        "AdmitDev", "d_keys d_rowptr d_labels R NNZ d_fgid d_vals")):
+    """A filtered minibatch on the device: pointers (ints; None for an array that was not given)
+    owned by the Admit object, valid until its next apply.  The first five fields are
+    Sharded.compile_dev's arguments, compile_valued_dev takes d_vals in second place."""
+
+
+class Admit:
+    """Feature admission (xf_admit_*): a counting Bloom filter over 2^log2_slots saturating 8-bit
+    counters.  apply() counts a minibatch's nonzeros (update=True) and returns the minibatch
+    without the nonzeros whose key the filter has not seen `count` times."""
+
+    def __init__(self, log2_slots, count, hashes=3, seed=0):
+        self.h = vp()
+        self.log2_slots, self.count, self.hashes, self.seed = log2_slots, count, hashes, seed
+        check(lib().xf_admit_create(C.byref(self.h), log2_slots, hashes, count, seed))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().xf_admit_destroy(self.h)
+            self.h = None
+
+    def slot(self, key, j):
+        return admit_slot(key, self.seed, self.log2_slots, j)
+
+    def apply_dev(self, rowptr, keys, labels=None, fgid=None, values=None, update=True,
+                  stream=None):
+        """host arrays in (uploaded as they are), the filtered minibatch as an AdmitDev out"""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert len(rowptr) >= 1 and int(rowptr[-1]) - int(rowptr[0]) <= len(keys)
+        R = len(rowptr) - 1
+        args = []
+        for a, dt, pt in ((fgid, np.int32, i32p), (values, np.float32, f32p)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=dt)
+                assert len(a) == len(keys), "one entry per key"
+                a = a if len(a) else np.zeros(1, dt)
+            args.append((a, pt))
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            assert len(labels) == R, "one label per row"
+            labels = labels if R else np.zeros(1, np.int32)
+        args.append((labels, i32p))
+        if len(keys) == 0:
+            keys = np.zeros(1, np.uint64)
+        ptr = [(_p(a, pt) if a is not None else None) for a, pt in args]
+        dk, dfg, dv, dr, dl = vp(), vp(), vp(), vp(), vp()
+        Ro, No = C.c_uint32(), C.c_uint32()
+        check(lib().xf_admit_apply(self.h, 1 if update else 0, _p(rowptr, u64p), _p(keys, u64p),
+                                   ptr[0], ptr[1], ptr[2], 0, R, stream, C.byref(dk),
+                                   C.byref(dfg), C.byref(dv), C.byref(dr), C.byref(dl),
+                                   C.byref(Ro), C.byref(No)))
+        return AdmitDev(dk.value, dr.value, dl.value, Ro.value, No.value, dfg.value, dv.value)
+
+    def filter_dev(self, d_keys, d_rowptr, R, NNZ, d_fgid=None, d_vals=None, update=True,
+                   stream=None):
+        """xf_admit_apply_dev: device pointers in (ints), (d_keys, d_rowptr, NNZ, d_fgid, d_vals)
+        of the filtered minibatch out; labels and R are the caller's, untouched"""
+        dk, dfg, dv, dr = vp(), vp(), vp(), vp()
+        No = C.c_uint32()
+        check(lib().xf_admit_apply_dev(self.h, 1 if update else 0, d_keys, d_fgid, d_vals,
+                                       d_rowptr, R, NNZ, stream, C.byref(dk), C.byref(dfg),
+                                       C.byref(dv), C.byref(dr), C.byref(No)))
+        return dk.value, dr.value, No.value, dfg.value, dv.value
+
+    def apply(self, rowptr, keys, labels=None, fgid=None, values=None, update=True):
+        """the filtered host arrays (downloaded): (rowptr uint32, keys) and then, for each of
+        labels / fgid / values that was given, its filtered array in that order"""
+        d = self.apply_dev(rowptr, keys, labels, fgid, values, update)
+        rp, ks = np.zeros(d.R + 1, np.uint32), np.zeros(d.NNZ, np.uint64)
+        out = [(rp, d.d_rowptr), (ks, d.d_keys)]
+        if labels is not None:
+            out.append((np.zeros(d.R, np.int32), d.d_labels))
+        if fgid is not None:
+            out.append((np.zeros(d.NNZ, np.int32), d.d_fgid))
+        if values is not None:
+            out.append((np.zeros(d.NNZ, np.float32), d.d_vals))
+        for a, ptr in out:
+            if a.nbytes:
+                check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
+        return tuple(a for a, _ in out)
+
+    def export(self):
+        out = np.empty(1 << self.log2_slots, np.uint8)
+        check(lib().xf_admit_export(self.h, _p(out, C.POINTER(C.c_uint8))))
+        return out
+
+    def import_(self, counters):
+        counters = np.ascontiguousarray(counters, dtype=np.uint8)
+        assert len(counters) == 1 << self.log2_slots
+        check(lib().xf_admit_import(self.h, _p(counters, C.POINTER(C.c_uint8))))
+
+    def save(self, path):
+        check(lib().xf_admit_save(self.h, str(path).encode()))
+
+    def load(self, path):
+        check(lib().xf_admit_load(self.h, str(path).encode()))
+
+    def stats(self):
+        """(nonzeros seen, nonzeros kept), summed over the update=True applies"""
+        seen, kept = C.c_uint64(), C.c_uint64()
+        check(lib().xf_admit_stats(self.h, C.byref(seen), C.byref(kept)))
+        return seen.value, kept.value
 
 
 class Batch:

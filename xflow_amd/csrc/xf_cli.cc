@@ -25,7 +25,10 @@ int main(int argc, char *argv[]) {
               << "feature values (x = val of fgid:fid:val instead of 1; LR, or FM with "
                  "fm_mode=canonical or field_aware; one worker): append feature_values=on\n"
               << "text tokenised on the GPU: append ingest=gpu (keys only) or ingest=gpu_fields "
-                 "(also fgid and val, for field_aware and feature_values)\n";
+                 "(also fgid and val, for field_aware and feature_values)\n"
+              << "feature admission (a key enters the model once a counting Bloom filter has seen "
+                 "it N times; one worker): append admit_count=N [admit_log2_slots=26 "
+                 "admit_hashes=3]\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler

@@ -51,6 +51,7 @@ Worker::~Worker() {
   for (xf_ingest *g : ingest_)
     if (g) xf_ingest_destroy(g);
   for (xf_sbatch *b : cache_) xf_sbatch_free(b);
+  if (admit_) xf_admit_destroy(admit_);
   if (sharded_) xf_sharded_destroy(sharded_);  // owns the tables
   if (group_) xf_group_destroy(group_);
 }
@@ -69,7 +70,7 @@ static const char *env_first(std::initializer_list<const char *> names) {
 // environment, as scripts/local.sh sets it) this process joins the group — one process per
 // GPU — and its tables are one key-range shard of the parameter table.
 int Worker::create_tables() {
-  if (sharded_) return XF_OK;
+  if (sharded_) return create_admit();
   int w = world;
   if (w <= 0) {
     const char *v = env_first({"WORLD_SIZE", "XF_WORLD", "DMLC_NUM_WORKER"});
@@ -133,7 +134,93 @@ int Worker::create_tables() {
     xf_sharded_destroy(warm);
     XF_TRY(rc);
   }
+  return create_admit();
+}
+
+static int world_from_env(int world) {
+  if (world > 0) return world;
+  const char *v = env_first({"WORLD_SIZE", "XF_WORLD", "DMLC_NUM_WORKER"});
+  return v ? atoi(v) : 1;
+}
+
+// Feature admission is a filter in front of ONE worker's key build on the GPU: each rank of a
+// group would count only its own shard of the data (and rank 0's predict would test keys other
+// ranks admitted), core_num > 1 slices a block after it was read, the host key build and the
+// reference-order forward take host arrays.  All refused by name, before any rendezvous.
+int Worker::check_admit() const {
+  if (admit_count == 0) return XF_OK;
+  XF_REQUIRE(admit_count >= 1 && admit_count <= 255,
+             "XFStartTrain: admit_count must be 0 (off) or in 1 .. 255 (8-bit counters), not %d",
+             admit_count);
+  XF_REQUIRE(admit_log2_slots >= 2 && admit_log2_slots <= 32,
+             "XFStartTrain: admit_log2_slots must be in 2 .. 32, not %d", admit_log2_slots);
+  XF_REQUIRE(admit_hashes >= 1 && admit_hashes <= 8,
+             "XFStartTrain: admit_hashes must be in 1 .. 8, not %d", admit_hashes);
+  const int w = sharded_ ? world : world_from_env(world);
+  XF_REQUIRE(w <= 1, "XFStartTrain: admit_count=%d runs on one worker only (world %d): every rank "
+             "would count its own shard of the data", admit_count, w);
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: admit_count=%d needs core_num=1, not core_num=%d",
+             admit_count, core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: admit_count=%d together with key_build=host: the "
+             "filtered minibatch is born on the GPU (use key_build=gpu)", admit_count);
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: admit_count=%d together with "
+             "parity=reference_order: that mode builds its keys on the host", admit_count);
   return XF_OK;
+}
+
+int Worker::create_admit() {
+  if (admit_count == 0 || admit_) return XF_OK;
+  XF_TRY(check_admit());
+  return xf_admit_create(&admit_, admit_log2_slots, admit_hashes, admit_count, seed);
+}
+
+// the _dev compile of the worker's mode on device arrays
+int Worker::compile_dev_arrays(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
+                               const float *d_vals, const uint32_t *d_rowptr,
+                               const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
+  if (fm_mode == XF_FM_FIELD_AWARE)
+    return xf_sharded_compile_fielded_dev(sharded_, b, d_keys, d_fgid,
+                                          feature_values ? d_vals : nullptr, d_rowptr, d_labels, R,
+                                          NNZ, keep);
+  if (feature_values)
+    return xf_sharded_compile_valued_dev(sharded_, b, d_keys, d_vals, d_rowptr, d_labels, R, NNZ,
+                                         keep);
+  return xf_sharded_compile_dev(sharded_, b, d_keys, d_rowptr, d_labels, R, NNZ, keep);
+}
+
+int Worker::compile_admitted_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
+                                 const int32_t *d_fgid, const float *d_vals,
+                                 const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
+                                 uint32_t NNZ, int keep) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const uint64_t *fk = nullptr;
+  const int32_t *ff = nullptr;
+  const float *fv = nullptr;
+  const uint32_t *fr = nullptr;
+  uint32_t kept = 0;
+  XF_TRY(xf_admit_apply_dev(admit_, update, d_keys,
+                            fm_mode == XF_FM_FIELD_AWARE ? d_fgid : nullptr,
+                            feature_values ? d_vals : nullptr, d_rowptr, R, NNZ, stream, &fk, &ff,
+                            &fv, &fr, &kept));
+  return compile_dev_arrays(b, fk, ff, fv, fr, d_labels, R, kept, keep);
+}
+
+int Worker::compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr,
+                             const uint64_t *keys, const int32_t *fgid, const float *vals,
+                             const int32_t *labels, size_t row_begin, size_t row_end, int keep) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const uint64_t *fk = nullptr;
+  const int32_t *ff = nullptr, *fl = nullptr;
+  const float *fv = nullptr;
+  const uint32_t *fr = nullptr;
+  uint32_t R = 0, kept = 0;
+  XF_TRY(xf_admit_apply(admit_, update, rowptr, keys,
+                        fm_mode == XF_FM_FIELD_AWARE ? fgid : nullptr,
+                        feature_values ? vals : nullptr, labels, row_begin, row_end, stream, &fk,
+                        &ff, &fv, &fr, &fl, &R, &kept));
+  return compile_dev_arrays(b, fk, ff, fv, fr, fl, R, kept, keep);
 }
 
 // ingest = gpu_fields: what the tokeniser reads beside the fid is what the model needs — fgid for
@@ -364,7 +451,10 @@ int Worker::batch_training() {
           xf_sbatch *b = nullptr;
           const double tc0 = now_s();
           // a rank without rows of its own still takes part in the (collective) step
-          if (fm_mode == XF_FM_FIELD_AWARE)  // (one worker, as with feature values)
+          if (admit_)  // (one worker, core_num 1: counted, filtered, compiled from device arrays)
+            rc = compile_admitted(&b, 1, p->rowptr, p->keys, p->fgid, p->vals, p->labels, start,
+                                  end, keep);
+          else if (fm_mode == XF_FM_FIELD_AWARE)  // (one worker, as with feature values)
             rc = xf_sharded_compile_fielded(sharded_, &b, p->rowptr, p->keys, p->fgid,
                                             feature_values ? p->vals : nullptr, p->labels, start,
                                             end, keep);
@@ -571,7 +661,9 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
         const int32_t *dfg = nullptr;
         const float *dv = nullptr;
         rc = xf_ingest_fields(ingest_[k], &dfg, &dv);
-        if (rc == XF_OK && ffm)
+        if (rc == XF_OK && admit_)
+          rc = compile_admitted_dev(&b, 1, dk, dfg, dv, drp, dl, R, NNZ, keep);
+        else if (rc == XF_OK && ffm)
           rc = xf_sharded_compile_fielded_dev(sharded_, &b, dk, dfg, feature_values ? dv : nullptr,
                                               drp, dl, R, NNZ, keep);
         else if (rc == XF_OK && feature_values)
@@ -593,7 +685,9 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
                                     &fgid, &labels);
         if (rc == XF_OK && feature_values) rc = xf_block_values(blocks_[0], &vals);
         // (with fields or values — one worker — a block without rows is no minibatch: b stays null)
-        if (rc == XF_OK && ffm && rows)
+        if (rc == XF_OK && admit_) {
+          if (rows) rc = compile_admitted(&b, 1, rowptr, keys, fgid, vals, labels, 0, rows, keep);
+        } else if (rc == XF_OK && ffm && rows)
           rc = xf_sharded_compile_fielded(sharded_, &b, rowptr, keys, fgid, vals, labels, 0, rows,
                                           keep);
         else if (rc == XF_OK && feature_values && rows)
@@ -694,7 +788,9 @@ int Worker::predict(int rank, int block, bool reader) {
       const size_t start = i * thread_size, end = (i + 1) * thread_size;
       if (end == start && world <= 1) continue;
       xf_sbatch *b = nullptr;
-      if (fm_mode == XF_FM_FIELD_AWARE)
+      if (admit_)  // a key the filter has not admitted is neither scored nor inserted
+        XF_TRY(compile_admitted(&b, 0, rowptr, keys, fgid, vals, labels, start, end, 0));
+      else if (fm_mode == XF_FM_FIELD_AWARE)
         XF_TRY(xf_sharded_compile_fielded(sharded_, &b, rowptr, keys, fgid,
                                           feature_values ? vals : nullptr, labels, start, end, 0));
       else if (feature_values)
@@ -781,6 +877,7 @@ int Worker::train() {
     XF_REQUIRE(!ingest_gpu, "XFStartTrain: feature_values=on together with ingest=gpu: the GPU "
                "tokeniser carries no values (use ingest=gpu_fields)");
   }
+  XF_TRY(check_admit());  // before any rendezvous of a group
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
   std::cout << "my rank is = " << rank << std::endl;
@@ -802,6 +899,12 @@ int Worker::train() {
 
 // one worker: one file at `path`; several: one file per shard + a manifest (xf_sharded_save)
 int Worker::save_model(const char *path) {
+  // the filter's counters beside the model; with admission off a file saved under the same name
+  // earlier is stale, like the manifest below
+  const std::string apath = std::string(path) + ".admit";
+  if (admit_) XF_TRY(xf_admit_save(admit_, apath.c_str()));
+  else
+    (void)unlink(apath.c_str());
   if (world > 1) return xf_sharded_save(sharded_, path);
   XF_TRY(xf_sharded_flush(sharded_));
   XF_TRY(xf::model_write(path, table_w_, table_v_, v_width()));
@@ -812,7 +915,12 @@ int Worker::save_model(const char *path) {
 }
 
 // a single file or a sharded checkpoint of ANY world size: every rank keeps the keys it owns
-int Worker::load_model(const char *path) { return xf_sharded_load(sharded_, path); }
+int Worker::load_model(const char *path) {
+  XF_TRY(xf_sharded_load(sharded_, path));
+  // with admission on the model comes with its filter (a missing file: XF_EIO naming it)
+  if (admit_) XF_TRY(xf_admit_load(admit_, (std::string(path) + ".admit").c_str()));
+  return XF_OK;
+}
 
 int Worker::set_param(const char *name, const char *value) {
   XF_REQUIRE(name && value, "XFSetParam: null argument");
@@ -898,6 +1006,15 @@ int Worker::set_param(const char *name, const char *value) {
     else
       return xf::set_error(XF_EINVAL, "XFSetParam: feature_values must be on or off, not '%s'",
                            value);
+  } else if (n == "admit_count") {
+    XF_REQUIRE(!admit_, "XFSetParam: admit_count cannot change once the filter exists");
+    admit_count = atoi(value);
+  } else if (n == "admit_log2_slots") {
+    XF_REQUIRE(!admit_, "XFSetParam: admit_log2_slots cannot change once the filter exists");
+    admit_log2_slots = atoi(value);
+  } else if (n == "admit_hashes") {
+    XF_REQUIRE(!admit_, "XFSetParam: admit_hashes cannot change once the filter exists");
+    admit_hashes = atoi(value);
   } else if (n == "key_build") {
     if (!strcmp(value, "gpu")) key_build_gpu = true;
     else if (!strcmp(value, "host")) key_build_gpu = false;
@@ -920,7 +1037,11 @@ int Worker::get_metric(const char *name, double *value) {
   else if (n == "rows_trained") *value = (double)rows_trained_;
   else if (n == "blocks_gpu") *value = (double)blocks_gpu;
   else if (n == "blocks_host") *value = (double)blocks_host;
-  else if (n == "train_seconds") *value = train_seconds_;
+  else if (n == "admit_seen" || n == "admit_kept") {
+    uint64_t seen = 0, kept = 0;
+    if (admit_) XF_TRY(xf_admit_stats(admit_, &seen, &kept));
+    *value = (double)(n == "admit_seen" ? seen : kept);
+  } else if (n == "train_seconds") *value = train_seconds_;
   else if (n == "examples_per_sec") *value = train_seconds_ > 0 ? rows_trained_ / train_seconds_ : 0;
   else if (n == "keys") {
     uint64_t k = 0;

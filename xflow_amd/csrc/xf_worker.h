@@ -71,11 +71,32 @@ class Worker {
   // is ingest = gpu
   bool ingest_fields = false;
   long blocks_gpu = 0, blocks_host = 0;  // how the blocks of the last training run were parsed
+  // Feature admission (xf_admit.hip): admit_count = N >= 1: every block compiled from text goes
+  // through a counting Bloom filter first (training: counted and filtered, predict: filtered) and a
+  // key enters the tables only once the filter has seen it N times; 0 = off, nothing is created.
+  // One worker, core_num 1, key_build=gpu, parity=exact (checked where training starts).  The
+  // filter's seed is the worker's `seed`; its counters travel with the model as <model>.admit.
+  int admit_count = 0;
+  int admit_log2_slots = 26;  // 2^26 8-bit counters: 64 MiB
+  int admit_hashes = 3;
 
  private:
   int create_tables();
   int defrag_if_grown(int percent);
   int any_rank(bool mine, bool *any);
+  xf_admit *admit_ = nullptr;  // admit_count >= 1: the filter, created with the tables
+  int check_admit() const;     // the refusals of admit_count >= 1, before any rendezvous
+  int create_admit();
+  // filter a block (host arrays and a row slice / device arrays), then the matching _dev compile
+  int compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr, const uint64_t *keys,
+                       const int32_t *fgid, const float *vals, const int32_t *labels,
+                       size_t row_begin, size_t row_end, int keep);
+  int compile_admitted_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
+                           const int32_t *d_fgid, const float *d_vals, const uint32_t *d_rowptr,
+                           const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep);
+  int compile_dev_arrays(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
+                         const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
+                         uint32_t R, uint32_t NNZ, int keep);
   uint64_t keys_seen_ = 0;  // the table's keys at the last look (defrag_if_grown: the inflow per minibatch)
   bool rank_given_ = false;
 
