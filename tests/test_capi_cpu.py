@@ -669,6 +669,60 @@ def test_the_update_entry_points_fail_loudly_without_a_gpu():
     assert L.xf_sbatch_fm_keyed(None) < 0
 
 
+def test_the_host_front_ends_check_their_row_slice_before_any_device_call():
+    """xf_batch_compile_gpu / _valued_gpu / _fielded_gpu (and _fm / _local as far as null tables
+    reach): a slice that runs backwards, nonzeros without their arrays and a slice beyond 32 bits
+    are XF_EINVAL under the name of the function called, before anything touches the device"""
+    n = capi.C.c_int(0)
+    capi.check(capi.lib().xf_device_count(capi.C.byref(n)))
+    if n.value > 0:
+        pytest.skip("a GPU is present")
+    C, L = capi.C, capi.lib()
+    one = np.array([0, 1], np.uint64)
+    huge = np.array([0, 1 << 32], np.uint64)      # (nothing is dereferenced before the check)
+    k = np.zeros(1, np.uint64)
+    f = np.zeros(1, np.int32)
+    v = np.ones(1, np.float32)
+    lb = np.zeros(1, np.int32)
+    P = capi._p
+    K, F, V, LB = P(k, capi.u64p), P(f, capi.i32p), P(v, capi.f32p), P(lb, capi.i32p)
+
+    def plain(rp, keys, b, e):
+        return L.xf_batch_compile_gpu(C.byref(h), P(rp, capi.u64p), keys, LB, b, e, None)
+
+    def valued(rp, keys, vals, b, e):
+        return L.xf_batch_compile_valued_gpu(C.byref(h), P(rp, capi.u64p), keys, vals, LB, b, e, None)
+
+    def fielded(rp, keys, fg, vals, b, e):
+        return L.xf_batch_compile_fielded_gpu(C.byref(h), P(rp, capi.u64p), keys, fg, vals, LB, b, e,
+                                              3, None)
+
+    def failed(rc, who, why):
+        msg = L.xf_last_error().decode()
+        assert rc != 0 and msg.startswith(who + ":") and why in msg, (rc, who, why, msg)
+
+    h = capi.vp()
+    failed(plain(one, K, 1, 0), "xf_batch_compile_gpu", "bad argument")
+    failed(plain(one, None, 0, 1), "xf_batch_compile_gpu", "null keys")
+    failed(plain(huge, K, 0, 1), "xf_batch_compile_gpu", "too large")
+    failed(valued(one, K, V, 1, 0), "xf_batch_compile_valued_gpu", "bad argument")
+    failed(valued(one, None, V, 0, 1), "xf_batch_compile_valued_gpu", "null keys")
+    failed(valued(one, K, None, 0, 1), "xf_batch_compile_valued_gpu", "null keys")
+    failed(valued(huge, K, V, 0, 1), "xf_batch_compile_valued_gpu", "too large")
+    for vals in (None, V):
+        failed(fielded(one, K, F, vals, 1, 0), "xf_batch_compile_fielded_gpu", "bad argument")
+        failed(fielded(one, None, F, vals, 0, 1), "xf_batch_compile_fielded_gpu", "null keys")
+        failed(fielded(one, K, None, vals, 0, 1), "xf_batch_compile_fielded_gpu", "null keys")
+        failed(fielded(huge, K, F, vals, 0, 1), "xf_batch_compile_fielded_gpu", "too large")
+    for b, e in ((1, 0), (0, 1)):                 # (null tables: the first check is as far as it goes)
+        failed(L.xf_batch_compile_fm(C.byref(h), None, None, one.ctypes.data, k.ctypes.data,
+                                     lb.ctypes.data, b, e, None, None),
+               "xf_batch_compile_fm", "bad argument")
+        failed(L.xf_batch_compile_local(C.byref(h), None, P(one, capi.u64p), K, LB, b, e, 1, None),
+               "xf_batch_compile_local", "bad argument")
+    assert not h.value
+
+
 def test_tune_takes_the_named_switches_and_no_experiment_knob():
     """xf_tune: the code paths a test may pin have names (xf_common.h); the experiments' numeric
     knob exists only in a library built with -DXF_EXPERIMENTS, and values out of range are refused."""

@@ -101,6 +101,30 @@ void blob_pool_limit(int blobs);  // 0 = no pooling (every free goes back to the
 enum { kSortSiteAny = 0, kSortSiteBatch = 1, kSortSiteMerged = 2, kSortSiteLr = 3, kSortSites = 4 };
 int sort_key_pos(const uint64_t *d_keys, uint32_t n, uint64_t lo, uint64_t span, uint64_t *sk,
                  uint32_t *spos, hipStream_t s, bool *done, uint32_t site = kSortSiteAny);
+// The host-array front end of every device build (xf_batch_dev.hip): the row slice
+// [row_begin, row_end) of the reader's block arrays goes to the device — the 64-bit row offsets
+// rebased to 32-bit ones relative to the slice — into scratch the caller owns (declared before
+// the call: the build that follows nests its own scratch above it).  fgid / vals travel when
+// with_fgid / with_vals say so and must then be there for every nonzero; an array that does not
+// travel stays null, one that does is never null (Scratch::get hands out at least one element:
+// xf_batch_compile_valued_dev wants its d_vals even for a slice without nonzeros).  The caller has
+// checked rowptr, labels and row_end >= row_begin; the rest is checked here, under the name `who`,
+// before anything touches the device.  wait = false: the caller's build waits for the stream
+// itself before it returns — until then this struct (the uploads' source) must live.
+struct Scratch;
+struct SliceDev {
+  std::vector<uint32_t> rowptr;  // the rebased offsets on the host
+  uint64_t *d_keys = nullptr;
+  int32_t *d_fgid = nullptr;
+  float *d_vals = nullptr;
+  uint32_t *d_rowptr = nullptr;
+  int32_t *d_labels = nullptr;
+  uint32_t R = 0, NNZ = 0;
+};
+int upload_slice(SliceDev *out, Scratch &sc, const uint64_t *rowptr, const uint64_t *keys,
+                 const int32_t *fgid, bool with_fgid, const float *vals, bool with_vals,
+                 const int32_t *labels, size_t row_begin, size_t row_end, hipStream_t s,
+                 const char *who, bool wait = true);
 // xf_batch_compile_dev, with or without the panel-major forward view (xf_batch_dev.hip)
 int batch_compile_dev_ex(xf_batch **out, const uint64_t *d_keys, const uint32_t *d_rowptr,
                          const int32_t *d_labels, uint32_t R, uint32_t NNZ, hipStream_t stream,

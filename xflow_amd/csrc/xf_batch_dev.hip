@@ -966,32 +966,53 @@ extern "C" int xf_batch_compile_fm_dev(xf_batch **out, xf_table *w, xf_table *v,
   return XF_OK;
 }
 
+// The host-array front end of every device build (xf_batch.h): the checks, the rebase of the row
+// offsets, the scratch arrays and the uploads of one row slice.
+namespace xf {
+int upload_slice(SliceDev *out, Scratch &sc, const uint64_t *rowptr, const uint64_t *keys,
+                 const int32_t *fgid, bool with_fgid, const float *vals, bool with_vals,
+                 const int32_t *labels, size_t row_begin, size_t row_end, hipStream_t s,
+                 const char *who, bool wait) {
+  const size_t R = row_end - row_begin;
+  const uint64_t base = rowptr[row_begin];
+  const size_t NNZ = (size_t)(rowptr[row_end] - base);
+  XF_REQUIRE(NNZ == 0 || (keys && (fgid || !with_fgid) && (vals || !with_vals)),
+             "%s: null keys, fgid or values", who);
+  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "%s: batch too large", who);
+  out->R = (uint32_t)R;
+  out->NNZ = (uint32_t)NNZ;
+  out->rowptr.resize(R + 1);
+  for (size_t r = 0; r <= R; ++r) out->rowptr[r] = (uint32_t)(rowptr[row_begin + r] - base);
+  XF_TRY(sc.get(&out->d_keys, NNZ));
+  if (with_fgid) XF_TRY(sc.get(&out->d_fgid, NNZ));
+  if (with_vals) XF_TRY(sc.get(&out->d_vals, NNZ));  // (never null: get() rounds 0 up to 1)
+  XF_TRY(sc.get(&out->d_rowptr, R + 1));
+  XF_TRY(sc.get(&out->d_labels, R));
+  if (NNZ) {
+    XF_HIP(hipMemcpyAsync(out->d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
+    if (with_fgid)
+      XF_HIP(hipMemcpyAsync(out->d_fgid, fgid + base, NNZ * 4, hipMemcpyHostToDevice, s));
+    if (with_vals)
+      XF_HIP(hipMemcpyAsync(out->d_vals, vals + base, NNZ * 4, hipMemcpyHostToDevice, s));
+  }
+  XF_HIP(hipMemcpyAsync(out->d_rowptr, out->rowptr.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
+  if (R) XF_HIP(hipMemcpyAsync(out->d_labels, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
+  if (wait) XF_HIP(hipStreamSynchronize(s));
+  return XF_OK;
+}
+}  // namespace xf
+
 // Host-array front end of the device key build: same arguments as xf_batch_compile (the
 // reader's block arrays and a row slice); uploads the raw slice and builds on the GPU.
 extern "C" int xf_batch_compile_gpu(xf_batch **out, const uint64_t *rowptr, const uint64_t *keys,
                                     const int32_t *labels, size_t row_begin, size_t row_end,
                                     void *stream) {
   XF_REQUIRE(out && rowptr && labels && row_end >= row_begin, "xf_batch_compile_gpu: bad argument");
-  const size_t R = row_end - row_begin;
-  const uint64_t base = rowptr[row_begin];
-  const size_t NNZ = (size_t)(rowptr[row_end] - base);
-  XF_REQUIRE(NNZ == 0 || keys, "xf_batch_compile_gpu: null keys");
-  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile_gpu: batch too large");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<uint32_t> rp(R + 1);
-  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
   Scratch sc;
-  uint64_t *d_keys = nullptr;
-  uint32_t *d_rp = nullptr;
-  int32_t *d_lab = nullptr;
-  XF_TRY(sc.get(&d_keys, NNZ));
-  XF_TRY(sc.get(&d_rp, R + 1));
-  XF_TRY(sc.get(&d_lab, R));
-  if (NNZ) XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
-  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
-  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
-  XF_HIP(hipStreamSynchronize(s));
-  return xf_batch_compile_dev(out, d_keys, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ, stream);
+  xf::SliceDev d;
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, nullptr, false, nullptr, false, labels, row_begin,
+                          row_end, (hipStream_t)stream, "xf_batch_compile_gpu"));
+  return xf_batch_compile_dev(out, d.d_keys, d.d_rowptr, d.d_labels, d.R, d.NNZ, stream);
 }
 
 // host-array front end of xf_batch_compile_valued_dev
@@ -1001,31 +1022,11 @@ extern "C" int xf_batch_compile_valued_gpu(xf_batch **out, const uint64_t *rowpt
                                            void *stream) {
   XF_REQUIRE(out && rowptr && labels && row_end >= row_begin,
              "xf_batch_compile_valued_gpu: bad argument");
-  const size_t R = row_end - row_begin;
-  const uint64_t base = rowptr[row_begin];
-  const size_t NNZ = (size_t)(rowptr[row_end] - base);
-  XF_REQUIRE(NNZ == 0 || (keys && vals), "xf_batch_compile_valued_gpu: null keys or values");
-  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile_valued_gpu: batch too large");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<uint32_t> rp(R + 1);
-  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
   Scratch sc;
-  uint64_t *d_keys = nullptr;
-  float *d_vals = nullptr;
-  uint32_t *d_rp = nullptr;
-  int32_t *d_lab = nullptr;
-  XF_TRY(sc.get(&d_keys, NNZ));
-  XF_TRY(sc.get(&d_vals, NNZ + 1));
-  XF_TRY(sc.get(&d_rp, R + 1));
-  XF_TRY(sc.get(&d_lab, R));
-  if (NNZ) {
-    XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
-    XF_HIP(hipMemcpyAsync(d_vals, vals + base, NNZ * 4, hipMemcpyHostToDevice, s));
-  }
-  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
-  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
-  XF_HIP(hipStreamSynchronize(s));
-  return xf_batch_compile_valued_dev(out, d_keys, d_vals, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ,
+  xf::SliceDev d;
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, nullptr, false, vals, true, labels, row_begin,
+                          row_end, (hipStream_t)stream, "xf_batch_compile_valued_gpu"));
+  return xf_batch_compile_valued_dev(out, d.d_keys, d.d_vals, d.d_rowptr, d.d_labels, d.R, d.NNZ,
                                      stream);
 }
 
@@ -1043,7 +1044,7 @@ extern "C" int xf_batch_compile_fielded_dev(xf_batch **out, const uint64_t *d_ke
                                   false, d_vals, d_fgid, fields);
 }
 
-// host-array front end of xf_batch_compile_fielded_dev
+// host-array front end of xf_batch_compile_fielded_dev (vals null: the binary minibatch)
 extern "C" int xf_batch_compile_fielded_gpu(xf_batch **out, const uint64_t *rowptr,
                                             const uint64_t *keys, const int32_t *fgid,
                                             const float *vals, const int32_t *labels,
@@ -1051,35 +1052,13 @@ extern "C" int xf_batch_compile_fielded_gpu(xf_batch **out, const uint64_t *rowp
                                             void *stream) {
   XF_REQUIRE(out && rowptr && labels && row_end >= row_begin,
              "xf_batch_compile_fielded_gpu: bad argument");
-  const size_t R = row_end - row_begin;
-  const uint64_t base = rowptr[row_begin];
-  const size_t NNZ = (size_t)(rowptr[row_end] - base);
-  XF_REQUIRE(NNZ == 0 || (keys && fgid), "xf_batch_compile_fielded_gpu: null keys or fgid");
-  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile_fielded_gpu: batch too large");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<uint32_t> rp(R + 1);
-  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
   Scratch sc;
-  uint64_t *d_keys = nullptr;
-  int32_t *d_fg = nullptr;
-  float *d_vals = nullptr;
-  uint32_t *d_rp = nullptr;
-  int32_t *d_lab = nullptr;
-  XF_TRY(sc.get(&d_keys, NNZ));
-  XF_TRY(sc.get(&d_fg, NNZ + 1));
-  if (vals) XF_TRY(sc.get(&d_vals, NNZ + 1));
-  XF_TRY(sc.get(&d_rp, R + 1));
-  XF_TRY(sc.get(&d_lab, R));
-  if (NNZ) {
-    XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
-    XF_HIP(hipMemcpyAsync(d_fg, fgid + base, NNZ * 4, hipMemcpyHostToDevice, s));
-    if (vals) XF_HIP(hipMemcpyAsync(d_vals, vals + base, NNZ * 4, hipMemcpyHostToDevice, s));
-  }
-  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
-  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
-  XF_HIP(hipStreamSynchronize(s));
-  return xf_batch_compile_fielded_dev(out, d_keys, d_fg, d_vals, d_rp, d_lab, (uint32_t)R,
-                                      (uint32_t)NNZ, fields, stream);
+  xf::SliceDev d;
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, fgid, true, vals, vals != nullptr, labels,
+                          row_begin, row_end, (hipStream_t)stream,
+                          "xf_batch_compile_fielded_gpu"));
+  return xf_batch_compile_fielded_dev(out, d.d_keys, d.d_fgid, d.d_vals, d.d_rowptr, d.d_labels,
+                                      d.R, d.NNZ, fields, stream);
 }
 
 // host-array front end of xf_batch_compile_fm_dev (the reader's block arrays and a row slice)
@@ -1089,27 +1068,12 @@ extern "C" int xf_batch_compile_fm(xf_batch **out, xf_table *w, xf_table *v,
                                    void *stream, int *keyed) {
   XF_REQUIRE(out && w && v && rowptr && labels && row_end >= row_begin,
              "xf_batch_compile_fm: bad argument");
-  const size_t R = row_end - row_begin;
-  const uint64_t base = rowptr[row_begin];
-  const size_t NNZ = (size_t)(rowptr[row_end] - base);
-  XF_REQUIRE(NNZ == 0 || keys, "xf_batch_compile_fm: null keys");
-  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile_fm: batch too large");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<uint32_t> rp(R + 1);
-  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
   Scratch sc;
-  uint64_t *d_keys = nullptr;
-  uint32_t *d_rp = nullptr;
-  int32_t *d_lab = nullptr;
-  XF_TRY(sc.get(&d_keys, NNZ));
-  XF_TRY(sc.get(&d_rp, R + 1));
-  XF_TRY(sc.get(&d_lab, R));
-  if (NNZ) XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
-  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
-  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
-  XF_HIP(hipStreamSynchronize(s));
-  return xf_batch_compile_fm_dev(out, w, v, d_keys, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ,
-                                 stream, keyed);
+  xf::SliceDev d;
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, nullptr, false, nullptr, false, labels, row_begin,
+                          row_end, (hipStream_t)stream, "xf_batch_compile_fm"));
+  return xf_batch_compile_fm_dev(out, w, v, d.d_keys, d.d_rowptr, d.d_labels, d.R, d.NNZ, stream,
+                                 keyed);
 }
 
 // every row's unique-key indices in ascending order (parity mode "reference order": ascending

@@ -640,26 +640,11 @@ extern "C" int xf_batch_compile_local(xf_batch **out, xf_table *t, const uint64_
                                       void *stream) {
   XF_REQUIRE(out && t && rowptr && labels && row_end >= row_begin,
              "xf_batch_compile_local: bad argument");
-  const size_t R = row_end - row_begin;
-  const uint64_t base = rowptr[row_begin];
-  const size_t NNZ = (size_t)(rowptr[row_end] - base);
-  XF_REQUIRE(NNZ == 0 || keys, "xf_batch_compile_local: null keys");
-  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_batch_compile_local: batch too large");
-  hipStream_t s = (hipStream_t)stream;
-  std::vector<uint32_t> rp(R + 1);
-  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
   xf::Scratch sc;
-  uint64_t *d_keys = nullptr;
-  uint32_t *d_rp = nullptr;
-  int32_t *d_lab = nullptr;
-  XF_TRY(sc.get(&d_keys, NNZ));
-  XF_TRY(sc.get(&d_rp, R + 1));
-  XF_TRY(sc.get(&d_lab, R));
-  if (NNZ) XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
-  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
-  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
-  XF_HIP(hipStreamSynchronize(s));
-  return xf_batch_compile_local_dev(out, t, d_keys, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ,
+  xf::SliceDev d;
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, nullptr, false, nullptr, false, labels, row_begin,
+                          row_end, (hipStream_t)stream, "xf_batch_compile_local"));
+  return xf_batch_compile_local_dev(out, t, d.d_keys, d.d_rowptr, d.d_labels, d.R, d.NNZ,
                                     retain_keys, stream);
 }
 

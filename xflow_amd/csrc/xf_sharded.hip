@@ -40,6 +40,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -1030,25 +1031,13 @@ static int compile_owner_dev(xf_sharded *st, xf_sbatch *b, const uint64_t *d_key
 static int compile_owner(xf_sharded *st, xf_sbatch *b, const uint64_t *rowptr,
                          const uint64_t *keys, const int32_t *labels, size_t row_begin,
                          size_t row_end) {
-  hipStream_t s = st->main;
-  const size_t R = row_end - row_begin;
-  const uint64_t base = rowptr[row_begin];
-  const size_t NNZ = (size_t)(rowptr[row_end] - base);
-  XF_REQUIRE(R < 0xFFFFFFFFull && NNZ < 0xFFFFFFFFull, "xf_sharded_compile: minibatch too large");
-  std::vector<uint32_t> rp(R + 1);
-  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
   xf::Scratch sc;
-  uint64_t *d_k = nullptr;
-  uint32_t *d_rp = nullptr;
-  int32_t *d_lab = nullptr;
-  XF_TRY(sc.get(&d_k, NNZ));
-  XF_TRY(sc.get(&d_rp, R + 1));
-  XF_TRY(sc.get(&d_lab, R));
-  if (NNZ) XF_HIP(hipMemcpyAsync(d_k, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
-  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
-  if (R) XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
-  // (its wait is also the wait for these uploads: `rp` and the scratch may go when it returns)
-  return compile_owner_dev(st, b, d_k, d_rp, d_lab, (uint32_t)R, NNZ);
+  xf::SliceDev d;
+  // (no wait here: compile_owner_dev's wait is also the wait for these uploads — `d` and the
+  // scratch may go when it returns)
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, nullptr, false, nullptr, false, labels, row_begin,
+                          row_end, st->main, "xf_sharded_compile", false));
+  return compile_owner_dev(st, b, d.d_keys, d.d_rowptr, d.d_labels, d.R, d.NNZ);
 }
 
 // the cells of the received nonzeros against the shard's current row numbering (keys resolved —
@@ -1545,79 +1534,14 @@ static int compile_lr_from_host(xf_sbatch *b, const uint64_t *rowptr, const uint
   const size_t R = row_end - row_begin;
   const uint64_t base = rowptr[row_begin];
   const size_t NNZ = (size_t)(rowptr[row_end] - base);
+  // (not for this build: the caller's xf_batch_compile_gpu takes the slice, or refuses it by name)
   if (!R || !NNZ || !keys || R >= 0xFFFFFFFFull || NNZ >= 0xFFFFFFFFull) return XF_OK;
-  std::vector<uint32_t> rp(R + 1);
-  for (size_t r = 0; r <= R; ++r) rp[r] = (uint32_t)(rowptr[row_begin + r] - base);
   xf::Scratch sc;
-  uint64_t *d_keys = nullptr;
-  uint32_t *d_rp = nullptr;
-  int32_t *d_lab = nullptr;
-  XF_TRY(sc.get(&d_keys, NNZ));
-  XF_TRY(sc.get(&d_rp, R + 1));
-  XF_TRY(sc.get(&d_lab, R));
-  XF_HIP(hipMemcpyAsync(d_keys, keys + base, NNZ * 8, hipMemcpyHostToDevice, s));
-  XF_HIP(hipMemcpyAsync(d_rp, rp.data(), (R + 1) * 4, hipMemcpyHostToDevice, s));
-  XF_HIP(hipMemcpyAsync(d_lab, labels + row_begin, R * 4, hipMemcpyHostToDevice, s));
-  XF_HIP(hipStreamSynchronize(s));
-  return xf::batch_compile_lr_dev(&b->b, &b->cells, d_keys, d_rp, d_lab, (uint32_t)R, (uint32_t)NNZ,
+  xf::SliceDev d;
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, nullptr, false, nullptr, false, labels, row_begin,
+                          row_end, s, "xf_sharded_compile"));
+  return xf::batch_compile_lr_dev(&b->b, &b->cells, d.d_keys, d.d_rowptr, d.d_labels, d.R, d.NNZ,
                                   keep != 0, s, lean);
-}
-
-// Compile a minibatch: the key build (lr_worker.cc:146-166) and the static part of the
-// exchange.  COLLECTIVE: every rank of the group calls it, in the same order.  Host arrays
-// (the reader's block arrays and a row slice).  keep != 0: the batch will be replayed.
-extern "C" int xf_sharded_compile(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
-                                  const uint64_t *keys, const int32_t *labels, size_t row_begin,
-                                  size_t row_end, int keep) {
-  XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
-             "xf_sharded_compile: bad argument");
-  XF_ALIVE(st);
-  xf_sbatch *b = new xf_sbatch;
-  struct Guard {
-    xf_sbatch *b;
-    ~Guard() {
-      if (b) xf_sbatch_free(b);
-    }
-  } guard{b};
-  hipStream_t s = st->main;
-  b->owner = st;
-  if (st->fused) {  // one shard: the table is local
-    if (st->cfg.host_key_build)
-      XF_TRY(xf_batch_compile(&b->b, rowptr, keys, labels, row_begin, row_end));
-    else if (st->cfg.model == 0)
-      XF_TRY(xf_batch_compile_local(&b->b, st->tw, rowptr, keys, labels, row_begin, row_end,
-                                    keep, s));
-    else if (st->tv && st->parity_mode == XF_PARITY_EXACT_SUMS && st->fm_mode == XF_FM_REFERENCE)
-      // FM: against the tables' settled tiers when every key sits there (no sort; otherwise
-      // this is xf_batch_compile_gpu)
-      XF_TRY(xf_batch_compile_fm(&b->b, st->tw, st->tv, rowptr, keys, labels, row_begin, row_end,
-                                 s, nullptr));
-    else
-      XF_TRY(xf_batch_compile_gpu(&b->b, rowptr, keys, labels, row_begin, row_end, s));
-    XF_TRY(fused_room(st, b));
-    guard.b = nullptr;
-    *out = b;
-    return XF_OK;
-  }
-  if (owner_dataflow(st->cfg.schedule)) {
-    b->oc_keep = keep != 0;
-    XF_TRY(compile_owner(st, b, rowptr, keys, labels, row_begin, row_end));
-    guard.b = nullptr;
-    *out = b;
-    return XF_OK;
-  }
-  if (st->cfg.host_key_build) {
-    XF_TRY(xf_batch_compile(&b->b, rowptr, keys, labels, row_begin, row_end));
-    XF_TRY(xf_batch_upload(b->b, s));
-  } else {
-    bool lean = false;
-    if (st->cfg.model == 0) XF_TRY(compile_lr_from_host(b, rowptr, keys, labels, row_begin, row_end, keep, s, &lean));
-    if (!lean) XF_TRY(xf_batch_compile_gpu(&b->b, rowptr, keys, labels, row_begin, row_end, s));
-  }
-  XF_TRY(compile_exchange_tail(st, b, keep));
-  guard.b = nullptr;
-  *out = b;
-  return XF_OK;
 }
 
 static const char *schedule_name(int schedule) {
@@ -1675,64 +1599,6 @@ static int valued_trainer_check(const xf_sharded *st, const char *who) {
   return XF_OK;
 }
 
-extern "C" int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
-                                         const uint64_t *keys, const float *vals,
-                                         const int32_t *labels, size_t row_begin, size_t row_end,
-                                         int keep) {
-  XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
-             "xf_sharded_compile_valued: bad argument");
-  XF_ALIVE(st);
-  XF_TRY(valued_trainer_check(st, "xf_sharded_compile_valued"));
-  xf_sbatch *b = new xf_sbatch;
-  struct Guard {
-    xf_sbatch *b;
-    ~Guard() {
-      if (b) xf_sbatch_free(b);
-    }
-  } guard{b};
-  b->owner = st;
-  if (st->cfg.host_key_build)
-    XF_TRY(xf_batch_compile_valued(&b->b, rowptr, keys, vals, labels, row_begin, row_end));
-  else
-    XF_TRY(xf_batch_compile_valued_gpu(&b->b, rowptr, keys, vals, labels, row_begin, row_end,
-                                       st->main));
-  if (st->fused) XF_TRY(fused_room(st, b));
-  else {
-    if (st->cfg.host_key_build) XF_TRY(xf_batch_upload(b->b, st->main));
-    XF_TRY(compile_exchange_tail(st, b, keep));
-  }
-  guard.b = nullptr;
-  *out = b;
-  return XF_OK;
-}
-
-extern "C" int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out,
-                                             const uint64_t *d_keys, const float *d_vals,
-                                             const uint32_t *d_rowptr, const int32_t *d_labels,
-                                             uint32_t R, uint32_t NNZ, int keep) {
-  XF_REQUIRE(st && out && d_rowptr && d_vals && (R == 0 || d_labels) && (NNZ == 0 || d_keys),
-             "xf_sharded_compile_valued_dev: null argument");
-  XF_ALIVE(st);
-  XF_TRY(valued_trainer_check(st, "xf_sharded_compile_valued_dev"));
-  XF_REQUIRE(!st->cfg.host_key_build, "xf_sharded_compile_valued_dev: the trainer builds its keys "
-             "on the host (host_key_build): hand it host arrays");
-  xf_sbatch *b = new xf_sbatch;
-  struct Guard {
-    xf_sbatch *b;
-    ~Guard() {
-      if (b) xf_sbatch_free(b);
-    }
-  } guard{b};
-  b->owner = st;
-  XF_TRY(xf_batch_compile_valued_dev(&b->b, d_keys, d_vals, d_rowptr, d_labels, R, NNZ, st->main));
-  if (st->fused) XF_TRY(fused_room(st, b));
-  else
-    XF_TRY(compile_exchange_tail(st, b, keep));
-  guard.b = nullptr;
-  *out = b;
-  return XF_OK;
-}
-
 // Fields: a fielded minibatch always takes the generic build and steps on a trainer in the
 // field-aware form
 static int fielded_trainer_check(const xf_sharded *st, bool valued, const char *who) {
@@ -1744,69 +1610,173 @@ static int fielded_trainer_check(const xf_sharded *st, bool valued, const char *
   return XF_OK;
 }
 
+// ---- xf_sharded_compile*: six entry points (plain, valued or fielded rows; host or device
+// arrays), one body
+enum RowKind { kPlainRows, kValuedRows, kFieldedRows };
+
+// The raw rows a compile is handed.  Host arrays: the reader's block arrays and the row slice
+// [row_begin, row_end) (rowptr, 64-bit).  Device arrays (dev): the rows themselves (d_rowptr,
+// 32-bit, R, NNZ).  keys, fgid, vals and labels are host or device pointers accordingly; fgid
+// and vals are null where the kind has none (fielded rows with null vals: the binary minibatch).
+struct RawRows {
+  bool dev = false;
+  const uint64_t *keys = nullptr;
+  const int32_t *fgid = nullptr;
+  const float *vals = nullptr;
+  const int32_t *labels = nullptr;
+  const uint64_t *rowptr = nullptr;
+  size_t row_begin = 0, row_end = 0;
+  const uint32_t *d_rowptr = nullptr;
+  uint32_t R = 0, NNZ = 0;
+};
+
+static RawRows host_rows(const uint64_t *rowptr, const uint64_t *keys, const int32_t *fgid,
+                         const float *vals, const int32_t *labels, size_t row_begin,
+                         size_t row_end) {
+  RawRows a;
+  a.keys = keys, a.fgid = fgid, a.vals = vals, a.labels = labels;
+  a.rowptr = rowptr, a.row_begin = row_begin, a.row_end = row_end;
+  return a;
+}
+
+static RawRows dev_rows(const uint64_t *d_keys, const int32_t *d_fgid, const float *d_vals,
+                        const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
+                        uint32_t NNZ) {
+  RawRows a;
+  a.dev = true;
+  a.keys = d_keys, a.fgid = d_fgid, a.vals = d_vals, a.labels = d_labels;
+  a.d_rowptr = d_rowptr, a.R = R, a.NNZ = NNZ;
+  return a;
+}
+
+// the build of plain rows: what the trainer's shape and model allow beyond the generic build
+static int build_plain(xf_sharded *st, xf_sbatch *b, const RawRows &a, int keep) {
+  hipStream_t s = st->main;
+  if (st->fused) {  // one shard: the table is local
+    if (st->cfg.host_key_build)  // (host arrays: device arrays were refused)
+      return xf_batch_compile(&b->b, a.rowptr, a.keys, a.labels, a.row_begin, a.row_end);
+    if (st->cfg.model == 0)
+      return a.dev ? xf_batch_compile_local_dev(&b->b, st->tw, a.keys, a.d_rowptr, a.labels, a.R,
+                                                a.NNZ, keep, s)
+                   : xf_batch_compile_local(&b->b, st->tw, a.rowptr, a.keys, a.labels,
+                                            a.row_begin, a.row_end, keep, s);
+    if (st->tv && st->parity_mode == XF_PARITY_EXACT_SUMS && st->fm_mode == XF_FM_REFERENCE)
+      // FM: against the tables' settled tiers when every key sits there (no sort; otherwise
+      // this is the generic build)
+      return a.dev ? xf_batch_compile_fm_dev(&b->b, st->tw, st->tv, a.keys, a.d_rowptr, a.labels,
+                                             a.R, a.NNZ, s, nullptr)
+                   : xf_batch_compile_fm(&b->b, st->tw, st->tv, a.rowptr, a.keys, a.labels,
+                                         a.row_begin, a.row_end, s, nullptr);
+    return a.dev ? xf_batch_compile_dev(&b->b, a.keys, a.d_rowptr, a.labels, a.R, a.NNZ, s)
+                 : xf_batch_compile_gpu(&b->b, a.rowptr, a.keys, a.labels, a.row_begin, a.row_end,
+                                        s);
+  }
+  if (owner_dataflow(st->cfg.schedule)) {
+    b->oc_keep = keep != 0;
+    return a.dev ? compile_owner_dev(st, b, a.keys, a.d_rowptr, a.labels, a.R, a.NNZ)
+                 : compile_owner(st, b, a.rowptr, a.keys, a.labels, a.row_begin, a.row_end);
+  }
+  if (st->cfg.host_key_build)  // (the caller uploads it)
+    return xf_batch_compile(&b->b, a.rowptr, a.keys, a.labels, a.row_begin, a.row_end);
+  // LR: the keys and the cells, nothing else (xf::batch_compile_lr_dev); FM, or beyond that
+  // build's limits: the minibatch with all its views
+  bool lean = false;
+  if (st->cfg.model == 0)
+    XF_TRY(a.dev ? xf::batch_compile_lr_dev(&b->b, &b->cells, a.keys, a.d_rowptr, a.labels, a.R,
+                                            a.NNZ, keep != 0, s, &lean)
+                 : compile_lr_from_host(b, a.rowptr, a.keys, a.labels, a.row_begin, a.row_end,
+                                        keep, s, &lean));
+  if (lean) return XF_OK;
+  return a.dev ? xf::batch_compile_dev_ex(&b->b, a.keys, a.d_rowptr, a.labels, a.R, a.NNZ, s, false)
+               : xf_batch_compile_gpu(&b->b, a.rowptr, a.keys, a.labels, a.row_begin, a.row_end,
+                                      s);
+}
+
+// a valued minibatch always takes the generic build
+static int build_valued(xf_sharded *st, xf_sbatch *b, const RawRows &a) {
+  if (a.dev)
+    return xf_batch_compile_valued_dev(&b->b, a.keys, a.vals, a.d_rowptr, a.labels, a.R, a.NNZ,
+                                       st->main);
+  if (st->cfg.host_key_build)
+    return xf_batch_compile_valued(&b->b, a.rowptr, a.keys, a.vals, a.labels, a.row_begin,
+                                   a.row_end);
+  return xf_batch_compile_valued_gpu(&b->b, a.rowptr, a.keys, a.vals, a.labels, a.row_begin,
+                                     a.row_end, st->main);
+}
+
+// ... and so does a fielded one (the fgid range check is the build's first act)
+static int build_fielded(xf_sharded *st, xf_sbatch *b, const RawRows &a) {
+  if (a.dev)
+    return xf_batch_compile_fielded_dev(&b->b, a.keys, a.fgid, a.vals, a.d_rowptr, a.labels, a.R,
+                                        a.NNZ, st->fm_fields, st->main);
+  if (st->cfg.host_key_build)
+    return xf_batch_compile_fielded(&b->b, a.rowptr, a.keys, a.fgid, a.vals, a.labels,
+                                    a.row_begin, a.row_end, st->fm_fields);
+  return xf_batch_compile_fielded_gpu(&b->b, a.rowptr, a.keys, a.fgid, a.vals, a.labels,
+                                      a.row_begin, a.row_end, st->fm_fields, st->main);
+}
+
+struct SbatchFree {
+  void operator()(xf_sbatch *b) const { xf_sbatch_free(b); }
+};
+
+// Compile a minibatch: the key build (lr_worker.cc:146-166) and the static part of the
+// exchange.  COLLECTIVE: every rank of the group calls it, in the same order.  keep != 0: the
+// batch will be replayed.  `who` (the entry point) has checked its arguments.
+static int compile_rows(xf_sharded *st, xf_sbatch **out, RowKind kind, const RawRows &a, int keep,
+                        const char *who) {
+  XF_ALIVE(st);
+  if (kind == kFieldedRows) XF_TRY(fielded_trainer_check(st, a.vals != nullptr, who));
+  if (kind == kValuedRows) XF_TRY(valued_trainer_check(st, who));
+  XF_REQUIRE(!a.dev || !st->cfg.host_key_build, "%s: the trainer builds its keys on the host "
+             "(host_key_build): hand it host arrays", who);
+  std::unique_ptr<xf_sbatch, SbatchFree> b(new xf_sbatch);
+  b->owner = st;
+  if (kind == kPlainRows) XF_TRY(build_plain(st, b.get(), a, keep));
+  if (kind == kValuedRows) XF_TRY(build_valued(st, b.get(), a));
+  // (a failure of the fielded build is agreed on before any exchange)
+  if (kind == kFieldedRows) XF_TRY(build_agreed(st, build_fielded(st, b.get(), a), who));
+  if (st->fused) {
+    XF_TRY(fused_room(st, b.get()));
+  } else if (!owner_dataflow(st->cfg.schedule)) {  // (owner-compute: compile_owner* did it all)
+    if (st->cfg.host_key_build) XF_TRY(xf_batch_upload(b->b, st->main));
+    XF_TRY(compile_exchange_tail(st, b.get(), keep));
+  }
+  *out = b.release();
+  return XF_OK;
+}
+
+// Host arrays (the reader's block arrays and a row slice).
+extern "C" int xf_sharded_compile(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
+                                  const uint64_t *keys, const int32_t *labels, size_t row_begin,
+                                  size_t row_end, int keep) {
+  XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
+             "xf_sharded_compile: bad argument");
+  return compile_rows(st, out, kPlainRows,
+                      host_rows(rowptr, keys, nullptr, nullptr, labels, row_begin, row_end), keep,
+                      "xf_sharded_compile");
+}
+
+extern "C" int xf_sharded_compile_valued(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
+                                         const uint64_t *keys, const float *vals,
+                                         const int32_t *labels, size_t row_begin, size_t row_end,
+                                         int keep) {
+  XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
+             "xf_sharded_compile_valued: bad argument");
+  return compile_rows(st, out, kValuedRows,
+                      host_rows(rowptr, keys, nullptr, vals, labels, row_begin, row_end), keep,
+                      "xf_sharded_compile_valued");
+}
+
 extern "C" int xf_sharded_compile_fielded(xf_sharded *st, xf_sbatch **out, const uint64_t *rowptr,
                                           const uint64_t *keys, const int32_t *fgid,
                                           const float *vals, const int32_t *labels,
                                           size_t row_begin, size_t row_end, int keep) {
   XF_REQUIRE(st && out && rowptr && labels && row_end >= row_begin,
              "xf_sharded_compile_fielded: bad argument");
-  XF_ALIVE(st);
-  XF_TRY(fielded_trainer_check(st, vals != nullptr, "xf_sharded_compile_fielded"));
-  xf_sbatch *b = new xf_sbatch;
-  struct Guard {
-    xf_sbatch *b;
-    ~Guard() {
-      if (b) xf_sbatch_free(b);
-    }
-  } guard{b};
-  b->owner = st;
-  // (the fgid range check is the build's first act: a failure is agreed on before any exchange)
-  int rc;
-  if (st->cfg.host_key_build)
-    rc = xf_batch_compile_fielded(&b->b, rowptr, keys, fgid, vals, labels, row_begin, row_end,
-                                  st->fm_fields);
-  else
-    rc = xf_batch_compile_fielded_gpu(&b->b, rowptr, keys, fgid, vals, labels, row_begin, row_end,
-                                      st->fm_fields, st->main);
-  XF_TRY(build_agreed(st, rc, "xf_sharded_compile_fielded"));
-  if (st->fused) XF_TRY(fused_room(st, b));
-  else {
-    if (st->cfg.host_key_build) XF_TRY(xf_batch_upload(b->b, st->main));
-    XF_TRY(compile_exchange_tail(st, b, keep));
-  }
-  guard.b = nullptr;
-  *out = b;
-  return XF_OK;
-}
-
-extern "C" int xf_sharded_compile_fielded_dev(xf_sharded *st, xf_sbatch **out,
-                                              const uint64_t *d_keys, const int32_t *d_fgid,
-                                              const float *d_vals, const uint32_t *d_rowptr,
-                                              const int32_t *d_labels, uint32_t R, uint32_t NNZ,
-                                              int keep) {
-  XF_REQUIRE(st && out && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || (d_keys && d_fgid)),
-             "xf_sharded_compile_fielded_dev: null argument");
-  XF_ALIVE(st);
-  XF_TRY(fielded_trainer_check(st, d_vals != nullptr, "xf_sharded_compile_fielded_dev"));
-  XF_REQUIRE(!st->cfg.host_key_build, "xf_sharded_compile_fielded_dev: the trainer builds its "
-             "keys on the host (host_key_build): hand it host arrays");
-  xf_sbatch *b = new xf_sbatch;
-  struct Guard {
-    xf_sbatch *b;
-    ~Guard() {
-      if (b) xf_sbatch_free(b);
-    }
-  } guard{b};
-  b->owner = st;
-  const int rc = xf_batch_compile_fielded_dev(&b->b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R,
-                                              NNZ, st->fm_fields, st->main);
-  XF_TRY(build_agreed(st, rc, "xf_sharded_compile_fielded_dev"));
-  if (st->fused) XF_TRY(fused_room(st, b));
-  else
-    XF_TRY(compile_exchange_tail(st, b, keep));
-  guard.b = nullptr;
-  *out = b;
-  return XF_OK;
+  return compile_rows(st, out, kFieldedRows,
+                      host_rows(rowptr, keys, fgid, vals, labels, row_begin, row_end), keep,
+                      "xf_sharded_compile_fielded");
 }
 
 // The same from device-resident arrays (raw keys in CSR order, 32-bit row offsets, labels): what
@@ -1817,44 +1787,32 @@ extern "C" int xf_sharded_compile_dev(xf_sharded *st, xf_sbatch **out, const uin
                                       uint32_t R, uint32_t NNZ, int keep) {
   XF_REQUIRE(st && out && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || d_keys),
              "xf_sharded_compile_dev: null argument");
-  XF_ALIVE(st);
-  XF_REQUIRE(!st->cfg.host_key_build, "xf_sharded_compile_dev: the trainer builds its keys on "
-             "the host (host_key_build): hand it host arrays");
-  xf_sbatch *b = new xf_sbatch;
-  struct Guard {
-    xf_sbatch *b;
-    ~Guard() {
-      if (b) xf_sbatch_free(b);
-    }
-  } guard{b};
-  hipStream_t s = st->main;
-  b->owner = st;
-  if (st->fused) {
-    if (st->cfg.model == 0)
-      XF_TRY(xf_batch_compile_local_dev(&b->b, st->tw, d_keys, d_rowptr, d_labels, R, NNZ, keep,
-                                        s));
-    else if (st->tv && st->parity_mode == XF_PARITY_EXACT_SUMS && st->fm_mode == XF_FM_REFERENCE)
-      XF_TRY(xf_batch_compile_fm_dev(&b->b, st->tw, st->tv, d_keys, d_rowptr, d_labels, R, NNZ, s,
-                                     nullptr));
-    else
-      XF_TRY(xf_batch_compile_dev(&b->b, d_keys, d_rowptr, d_labels, R, NNZ, s));
-    XF_TRY(fused_room(st, b));
-  } else if (owner_dataflow(st->cfg.schedule)) {
-    b->oc_keep = keep != 0;
-    XF_TRY(compile_owner_dev(st, b, d_keys, d_rowptr, d_labels, R, NNZ));
-  } else {
-    // LR: the keys and the cells, nothing else (xf::batch_compile_lr_dev); FM, or beyond that
-    // build's limits: the minibatch with all its views
-    bool lean = false;
-    if (st->cfg.model == 0)
-      XF_TRY(xf::batch_compile_lr_dev(&b->b, &b->cells, d_keys, d_rowptr, d_labels, R, NNZ, keep != 0,
-                                      s, &lean));
-    if (!lean) XF_TRY(xf::batch_compile_dev_ex(&b->b, d_keys, d_rowptr, d_labels, R, NNZ, s, false));
-    XF_TRY(compile_exchange_tail(st, b, keep));
-  }
-  guard.b = nullptr;
-  *out = b;
-  return XF_OK;
+  return compile_rows(st, out, kPlainRows,
+                      dev_rows(d_keys, nullptr, nullptr, d_rowptr, d_labels, R, NNZ), keep,
+                      "xf_sharded_compile_dev");
+}
+
+extern "C" int xf_sharded_compile_valued_dev(xf_sharded *st, xf_sbatch **out,
+                                             const uint64_t *d_keys, const float *d_vals,
+                                             const uint32_t *d_rowptr, const int32_t *d_labels,
+                                             uint32_t R, uint32_t NNZ, int keep) {
+  XF_REQUIRE(st && out && d_rowptr && d_vals && (R == 0 || d_labels) && (NNZ == 0 || d_keys),
+             "xf_sharded_compile_valued_dev: null argument");
+  return compile_rows(st, out, kValuedRows,
+                      dev_rows(d_keys, nullptr, d_vals, d_rowptr, d_labels, R, NNZ), keep,
+                      "xf_sharded_compile_valued_dev");
+}
+
+extern "C" int xf_sharded_compile_fielded_dev(xf_sharded *st, xf_sbatch **out,
+                                              const uint64_t *d_keys, const int32_t *d_fgid,
+                                              const float *d_vals, const uint32_t *d_rowptr,
+                                              const int32_t *d_labels, uint32_t R, uint32_t NNZ,
+                                              int keep) {
+  XF_REQUIRE(st && out && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || (d_keys && d_fgid)),
+             "xf_sharded_compile_fielded_dev: null argument");
+  return compile_rows(st, out, kFieldedRows,
+                      dev_rows(d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ), keep,
+                      "xf_sharded_compile_fielded_dev");
 }
 
 // One LRWorker::update / FMWorker::update of every rank (COLLECTIVE), asynchronous.

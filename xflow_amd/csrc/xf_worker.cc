@@ -122,12 +122,7 @@ int Worker::create_tables() {
     const bool ffm = fm_mode == XF_FM_FIELD_AWARE;
     int rc = ffm ? xf_sharded_set_fm_fields(warm, fields) : XF_OK;
     if (rc == XF_OK && fm_mode != XF_FM_REFERENCE) rc = xf_sharded_set_fm_mode(warm, fm_mode);
-    if (rc == XF_OK && ffm)
-      rc = xf_sharded_compile_fielded(warm, &b, rp, keys, fg, feature_values ? vals : nullptr, lab,
-                                      0, 2, 1);
-    else if (rc == XF_OK)
-      rc = feature_values ? xf_sharded_compile_valued(warm, &b, rp, keys, vals, lab, 0, 2, 1)
-                          : xf_sharded_compile(warm, &b, rp, keys, lab, 0, 2, 1);
+    if (rc == XF_OK) rc = compile_rows(warm, &b, 0, rp, keys, fg, vals, lab, 0, 2, 1);
     if (rc == XF_OK) rc = xf_sharded_step(warm, b);
     if (rc == XF_OK) rc = xf_sharded_predict(warm, b, p);
     if (b) xf_sbatch_free(b);
@@ -172,6 +167,29 @@ int Worker::create_admit() {
   if (admit_count == 0 || admit_) return XF_OK;
   XF_TRY(check_admit());
   return xf_admit_create(&admit_, admit_log2_slots, admit_hashes, admit_count, seed);
+}
+
+// a rank without rows of its own still takes part in the (collective) step: the empty minibatch
+int Worker::compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep) {
+  static const uint64_t kNoRows[1] = {0};
+  return xf_sharded_compile(trainer, b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0, keep);
+}
+
+// the compile of the worker's mode on rows [start, end) of a block's host arrays (fgid and vals
+// are looked at only in the modes that read them); update: the admission filter counts the keys
+int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
+                         const uint64_t *keys, const int32_t *fgid, const float *vals,
+                         const int32_t *labels, size_t start, size_t end, int keep) {
+  if (admit_ && trainer == sharded_)  // (one worker, core_num 1: filtered, compiled from device arrays)
+    return compile_admitted(b, update, rowptr, keys, fgid, vals, labels, start, end, keep);
+  if (fm_mode == XF_FM_FIELD_AWARE)
+    return xf_sharded_compile_fielded(trainer, b, rowptr, keys, fgid,
+                                      feature_values ? vals : nullptr, labels, start, end, keep);
+  if (feature_values)
+    return xf_sharded_compile_valued(trainer, b, rowptr, keys, vals, labels, start, end, keep);
+  if (end > start)
+    return xf_sharded_compile(trainer, b, rowptr, keys, labels, start, end, keep);
+  return compile_no_rows(trainer, b, keep);
 }
 
 // the _dev compile of the worker's mode on device arrays
@@ -335,7 +353,6 @@ int Worker::batch_training() {
   // compiled minibatches are kept in HBM for the epochs that replay them — with one epoch
   // there is none: the batches are one-shot (no key-sorted copy, their blobs go back to the pool)
   const int keep = cache_batches != 0 && epochs > 1;
-  static const uint64_t kNoRows[1] = {0};
   for (int epoch = 0; epoch < epochs; ++epoch) {
     if (cached) {
       // The compiled batches depend only on the file, so later epochs replay them from
@@ -382,6 +399,7 @@ int Worker::batch_training() {
         std::string err;
       };
       Parsed slot[2];
+      const Parsed none;  // (a rank whose file has ended: no arrays)
       for (int i = 0; i < 2; ++i) {
         int rc = blocks_[i] ? XF_OK : xf_block_create(&blocks_[i]);
         if (rc != XF_OK) {
@@ -451,21 +469,9 @@ int Worker::batch_training() {
           xf_sbatch *b = nullptr;
           const double tc0 = now_s();
           // a rank without rows of its own still takes part in the (collective) step
-          if (admit_)  // (one worker, core_num 1: counted, filtered, compiled from device arrays)
-            rc = compile_admitted(&b, 1, p->rowptr, p->keys, p->fgid, p->vals, p->labels, start,
-                                  end, keep);
-          else if (fm_mode == XF_FM_FIELD_AWARE)  // (one worker, as with feature values)
-            rc = xf_sharded_compile_fielded(sharded_, &b, p->rowptr, p->keys, p->fgid,
-                                            feature_values ? p->vals : nullptr, p->labels, start,
-                                            end, keep);
-          else if (feature_values)  // (one worker: a block without rows ended the loop above)
-            rc = xf_sharded_compile_valued(sharded_, &b, p->rowptr, p->keys, p->vals, p->labels,
-                                           start, end, keep);
-          else if (end > start)
-            rc = xf_sharded_compile(sharded_, &b, p->rowptr, p->keys, p->labels, start, end, keep);
-          else
-            rc = xf_sharded_compile(sharded_, &b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0,
-                                    keep);
+          const Parsed &m = p ? *p : none;
+          rc = compile_rows(sharded_, &b, 1, m.rowptr, m.keys, m.fgid, m.vals, m.labels, start, end,
+                            keep);
           if (rc != XF_OK) break;
           const double tc1 = now_s();
           rc = xf_sharded_step(sharded_, b);
@@ -625,7 +631,6 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
       if (last) return;
     }
   });
-  static const uint64_t kNoRows[1] = {0};
   int rc = XF_OK;
   bool mine_done = false;
   for (int k = 0; rc == XF_OK;) {
@@ -663,13 +668,8 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
         rc = xf_ingest_fields(ingest_[k], &dfg, &dv);
         if (rc == XF_OK && admit_)
           rc = compile_admitted_dev(&b, 1, dk, dfg, dv, drp, dl, R, NNZ, keep);
-        else if (rc == XF_OK && ffm)
-          rc = xf_sharded_compile_fielded_dev(sharded_, &b, dk, dfg, feature_values ? dv : nullptr,
-                                              drp, dl, R, NNZ, keep);
-        else if (rc == XF_OK && feature_values)
-          rc = xf_sharded_compile_valued_dev(sharded_, &b, dk, dv, drp, dl, R, NNZ, keep);
         else if (rc == XF_OK)
-          rc = xf_sharded_compile_dev(sharded_, &b, dk, drp, dl, R, NNZ, keep);
+          rc = compile_dev_arrays(&b, dk, dfg, dv, drp, dl, R, NNZ, keep);
         rows = R;
         on_gpu = true;
         ++blocks_gpu;
@@ -684,22 +684,14 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
           rc = xf_reader_parse_text(rd, buf, p->len, blocks_[0], &rows, &nnz, &rowptr, &keys,
                                     &fgid, &labels);
         if (rc == XF_OK && feature_values) rc = xf_block_values(blocks_[0], &vals);
-        // (with fields or values — one worker — a block without rows is no minibatch: b stays null)
-        if (rc == XF_OK && admit_) {
-          if (rows) rc = compile_admitted(&b, 1, rowptr, keys, fgid, vals, labels, 0, rows, keep);
-        } else if (rc == XF_OK && ffm && rows)
-          rc = xf_sharded_compile_fielded(sharded_, &b, rowptr, keys, fgid, vals, labels, 0, rows,
-                                          keep);
-        else if (rc == XF_OK && feature_values && rows)
-          rc = xf_sharded_compile_valued(sharded_, &b, rowptr, keys, vals, labels, 0, rows, keep);
-        else if (rc == XF_OK && !ffm && !feature_values)
-          rc = rows ? xf_sharded_compile(sharded_, &b, rowptr, keys, labels, 0, rows, keep)
-                    : xf_sharded_compile(sharded_, &b, kNoRows, nullptr,
-                                         (const int32_t *)kNoRows, 0, 0, keep);
+        // (under admission, with fields or with values — one worker — a block without rows is no
+        // minibatch: b stays null; a plain one is the empty minibatch)
+        if (rc == XF_OK && (rows || !(admit_ || ffm || feature_values)))
+          rc = compile_rows(sharded_, &b, 1, rowptr, keys, fgid, vals, labels, 0, rows, keep);
         ++blocks_host;
       }
     } else {  // a rank without rows of its own still takes part in the (collective) step
-      rc = xf_sharded_compile(sharded_, &b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0, keep);
+      rc = compile_no_rows(sharded_, &b, keep);
     }
     const double tc1 = now_s();
     if (rc == XF_OK && b) rc = xf_sharded_step(sharded_, b);
@@ -766,7 +758,6 @@ int Worker::predict(int rank, int block, bool reader) {
       if (r) xf_reader_close(r);
     }
   } rd_guard{rd};
-  static const uint64_t kNoRows[1] = {0};
   std::vector<int32_t> all_labels;
   std::vector<float> all_pctr, pctr;
   bool mine_done = !reader;
@@ -788,17 +779,8 @@ int Worker::predict(int rank, int block, bool reader) {
       const size_t start = i * thread_size, end = (i + 1) * thread_size;
       if (end == start && world <= 1) continue;
       xf_sbatch *b = nullptr;
-      if (admit_)  // a key the filter has not admitted is neither scored nor inserted
-        XF_TRY(compile_admitted(&b, 0, rowptr, keys, fgid, vals, labels, start, end, 0));
-      else if (fm_mode == XF_FM_FIELD_AWARE)
-        XF_TRY(xf_sharded_compile_fielded(sharded_, &b, rowptr, keys, fgid,
-                                          feature_values ? vals : nullptr, labels, start, end, 0));
-      else if (feature_values)
-        XF_TRY(xf_sharded_compile_valued(sharded_, &b, rowptr, keys, vals, labels, start, end, 0));
-      else if (end > start) XF_TRY(xf_sharded_compile(sharded_, &b, rowptr, keys, labels, start, end, 0));
-      else
-        XF_TRY(xf_sharded_compile(sharded_, &b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0,
-                                  0));
+      // (update 0: a key the admission filter has not admitted is neither scored nor inserted)
+      XF_TRY(compile_rows(sharded_, &b, 0, rowptr, keys, fgid, vals, labels, start, end, 0));
       struct BatchGuard {  // ... and frees the minibatch
         xf_sbatch *b;
         ~BatchGuard() { xf_sbatch_free(b); }

@@ -94,6 +94,12 @@ class Worker {
   int compile_admitted_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
                            const int32_t *d_fgid, const float *d_vals, const uint32_t *d_rowptr,
                            const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep);
+  // the compile of the worker's mode: rows [start, end) of host arrays on `trainer` (admitted,
+  // fielded, valued, plain, or — no rows — the empty minibatch), device arrays on sharded_
+  int compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
+                   const uint64_t *keys, const int32_t *fgid, const float *vals,
+                   const int32_t *labels, size_t start, size_t end, int keep);
+  int compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep);
   int compile_dev_arrays(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
                          const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
                          uint32_t R, uint32_t NNZ, int keep);
