@@ -256,6 +256,24 @@ int xf_batch_compile_local_dev(xf_batch **out, xf_table *t, const uint64_t *d_ke
 int xf_batch_compile_local(xf_batch **out, xf_table *t, const uint64_t *rowptr,
                            const uint64_t *keys, const int32_t *labels, size_t row_begin,
                            size_t row_end, int retain_keys, void *stream);
+/* The same for a minibatch with feature values (LR; d_vals / vals: one fp32 per nonzero, beside
+ * the keys): the sort-based local build — a probe of `t` per raw key (insert on first touch, the
+ * table grows when needed), then one stable radix pass that carries every nonzero's value along
+ * with its cell entry.  No key list, no uidx, no coo_val: xf_batch_host / xf_batch_values_* have
+ * nothing to show.  xf_lr_step / xf_lr_predict on `t` then run the valued cell kernels:
+ *   wx_r = sum_j w[row_j] x_j,   gw = (sum_occ loss_r x_occ) / R, stepped in place
+ * — the function of the generic valued minibatch (xf_batch_compile_valued*), bit for bit where
+ * its fp64 sums are exact; xf_workspace_fetch yields the loss only.  retain_keys != 0 also keeps
+ * the raw values (the rebuild after xf_table_defrag).  XF_PARITY_REFERENCE_ORDER,
+ * xf_workspace_capture and xf_fm_step / xf_fm_predict refuse it (XF_EINVAL). */
+int xf_batch_compile_local_valued_dev(xf_batch **out, xf_table *t, const uint64_t *d_keys,
+                                      const float *d_vals, const uint32_t *d_rowptr,
+                                      const int32_t *d_labels, uint32_t R, uint32_t NNZ,
+                                      int retain_keys, void *stream);
+int xf_batch_compile_local_valued(xf_batch **out, xf_table *t, const uint64_t *rowptr,
+                                  const uint64_t *keys, const float *vals, const int32_t *labels,
+                                  size_t row_begin, size_t row_end, int retain_keys,
+                                  void *stream);
 /* shape of a batch's cells once a step / predict has built them: out[0..8) = rows per window,
  * windows, chunks, forward workgroups per window, gradient work items, 0 (reserved), chunks
  * cut into several work items, size of the index space */
@@ -287,7 +305,9 @@ int xf_batch_tiles(const xf_batch *b, uint32_t *ntiles, const uint32_t **tile_pt
  * (tests pin one to run each against the oracle; 0 = by shape): "key_build" (1 the sort-based
  * build, 2 the two-level partition, 3 an empty table's keys through the arrival index too), "old_weight" (1 read, 2 derive from (n, z)), "lr_gradient"
  * (1 the general kernel, 2 / 3 the dense kernel with byte-masked / whole-line stores),
- * "owner_pass" (1 the general loop, 2 / 3 the merged phases, 4 a phase per worker) —
+ * "owner_pass" (1 the general loop, 2 / 3 the merged phases, 4 a phase per worker),
+ * "valued_lr" (a valued LR minibatch of a one-rank trainer: 1 the generic build + the tile
+ * kernels, 2 the local build + the valued cell kernels) —
  * xflow_amd/csrc/xf_common.h.  An unknown name, or a value a switch does not take, is XF_EINVAL
  * (a library built with -DXF_EXPERIMENTS also has the experiments' numeric "exp_knob"). */
 int xf_tune(const char *name, double value);
@@ -737,6 +757,10 @@ int xf_sharded_compile_fielded_dev(xf_sharded *st, xf_sbatch **out, const uint64
 int xf_sbatch_free(xf_sbatch *b);
 int xf_sbatch_dims(const xf_sbatch *b, uint32_t *R, uint32_t *NNZ, uint32_t *U,
                    uint64_t *n_owned /* keys of this minibatch (all ranks) this rank owns */);
+/* xf_batch_cells_info of a one-rank trainer's minibatch; XF_EINVAL when it has no cells over the
+ * table's rows (a minibatch with a key list that was not stepped yet, any FM minibatch) — which
+ * build a compile took, for tests and tools */
+int xf_sbatch_cells_info(const xf_sbatch *b, uint32_t *out);
 /* 1 when the minibatch came from the FM build against the tables' settled tiers
  * (xf_batch_compile_fm: one shard, every key settled), else 0; < 0: error */
 int xf_sbatch_fm_keyed(const xf_sbatch *b);

@@ -7,8 +7,10 @@ the same four minibatches of bench.py's generator, the two sides alternated with
     the margin of the ratio is the spread of the binary figure over its five repeats.
   * the generic build (xf_batch_compile_dev) with and without values, same shapes: host clock
     around a call that ends in a stream wait.
-  * valued LR at the configs[1] shape beside the binary cells step — for orientation only: a
-    different algorithm (sort-based build, Pull, gradient tiles).
+  * valued LR at the configs[1] shape: the binary cells step, the generic valued path (sort-based
+    generic build, Pull, gradient tiles: valued_lr = 1) and the local valued path (local build +
+    valued cell kernels: valued_lr = 2) — steps by device events; builds, and a build plus one
+    step of the fresh minibatch, by the host clock around calls that end in a stream wait.
 Compiled minibatches replayed from HBM, device events, every shape warmed up, five repeats.  One
 JSON line.  --leg k16_sgd | k64_ftrl | lr runs one configuration (a profiler run of its own).
   python tools/valued_leg.py [--leg L] [--rows R --nnz-per-row N --keys-per-gpu K]"""
@@ -146,7 +148,84 @@ def fm_leg(args, k, opt):
     return res
 
 
+class _Handle:
+    """a minibatch handle the step functions take"""
+
+    def __init__(self, h):
+        self.h = h
+
+
+def lr_build_and_once(batches, vals, tables, wss):
+    """LR from device arrays, the generic valued build (xf_batch_compile_valued_dev) beside the
+    local valued build (xf_batch_compile_local_valued_dev, retain_keys = 0) and the binary local
+    build: ms per build, and ms per build + ONE step of the fresh minibatch (what a minibatch that
+    is stepped once costs) — host clock, every timed call ends in a stream wait; the sides
+    alternated, five repeats after a warm-up round.  tables / wss: per side, in steady state."""
+    import ctypes as C
+    import torch
+    from xflow_amd import capi
+    L = capi.lib()
+    capi.tune("min_panel_nnz", 1e18)   # (as build_ms: the generic build without the panel view)
+    names = ("binary_local", "valued_generic", "valued_local")
+    dev = []
+    for (rowptr, keys, labels), x in zip(batches[:NB], vals):
+        dev.append((torch.from_numpy(keys.view(np.int64)).cuda(),
+                    torch.from_numpy(rowptr.astype(np.uint32).view(np.int32)).cuda(),
+                    torch.from_numpy(labels).cuda(), torch.from_numpy(x).cuda(),
+                    len(labels), len(keys)))
+    torch.cuda.synchronize()
+
+    def compile_(name, d):
+        dk, dr, dl, dv, R, NNZ = d
+        h = capi.vp()
+        if name == "valued_generic":
+            capi.check(L.xf_batch_compile_valued_dev(C.byref(h), dk.data_ptr(), dv.data_ptr(),
+                                                     dr.data_ptr(), dl.data_ptr(), R, NNZ, None))
+        elif name == "valued_local":
+            capi.check(L.xf_batch_compile_local_valued_dev(
+                C.byref(h), tables[name].h, dk.data_ptr(), dv.data_ptr(), dr.data_ptr(),
+                dl.data_ptr(), R, NNZ, 0, None))
+        else:
+            capi.check(L.xf_batch_compile_local_dev(C.byref(h), tables[name].h, dk.data_ptr(),
+                                                    dr.data_ptr(), dl.data_ptr(), R, NNZ, 0, None))
+        return h
+
+    build = {n: [] for n in names}
+    once = {n: [] for n in names}
+    for rep in range(REPEATS + 1):
+        for with_step, per in ((False, build), (True, once)):
+            for name in names:
+                t = 0.0
+                for d in dev:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    h = compile_(name, d)
+                    if with_step:
+                        capi.lr_step(tables[name], _Handle(h), wss[name])
+                    torch.cuda.synchronize()
+                    t += time.perf_counter() - t0
+                    L.xf_batch_free(h)
+                if rep:        # (the first round warms the builders' scratch up)
+                    per[name].append(t / NB * 1e3)
+    capi.tune("min_panel_nnz", 4e6)
+
+    def fig(p):
+        return {"ms": min(p), "ms_repeats": p, "spread": (max(p) - min(p)) / min(p)}
+    out = {"build": {n: fig(p) for n, p in build.items()},
+           "build_plus_one_step": {n: fig(p) for n, p in once.items()}}
+    g, l = out["build_plus_one_step"]["valued_generic"], out["build_plus_one_step"]["valued_local"]
+    # the rule of the by-shape default (DESIGN 3, "Feature values"): the local path for every
+    # minibatch if it is not slower than the generic one, the generic figure's spread the margin
+    out["stepped_once_local_over_generic"] = l["ms"] / g["ms"]
+    out["stepped_once_margin_generic_spread"] = g["spread"]
+    out["stepped_once_local_not_slower"] = l["ms"] <= g["ms"] * (1.0 + g["spread"])
+    return out
+
+
 def lr_leg(args, opt="ftrl"):
+    """configs[1]: the binary cells step, the generic valued path (valued_lr = 1: the parent's
+    code) and the local valued path (valued_lr = 2: valued cells), same minibatches, alternated"""
+    from xflow_amd import capi
     from xflow_amd.single import SingleGpuTrainer
     keytab = bench.make_key_table(args.keys_per_gpu)
     batches = bench.make_batches(args, 0, args.keys_per_gpu, keytab)[:NB]
@@ -154,24 +233,43 @@ def lr_leg(args, opt="ftrl"):
     cap = int(args.keys_per_gpu / args.load_factor) + 1024
     a = SingleGpuTrainer(model="lr", optimizer=opt, capacity=cap)
     b = SingleGpuTrainer(model="lr", optimizer=opt, capacity=cap, feature_values=True)
+    c = SingleGpuTrainer(model="lr", optimizer=opt, capacity=cap, feature_values=True)
     ca = [a.compile(*m) for m in batches]
-    cb = [b.compile(*m, values=x) for m, x in zip(batches, vals)]
+    try:
+        capi.tune("valued_lr", 1)
+        cb = [b.compile(*m, values=x) for m, x in zip(batches, vals)]
+        capi.tune("valued_lr", 2)
+        cc = [c.compile(*m, values=x) for m, x in zip(batches, vals)]
+    finally:
+        capi.tune("valued_lr", 0)
+    assert all(x.U > 0 for x in cb) and all(x.cells_info()["segments"] == 1 for x in cc)
     prepare(a, ca)
     prepare(b, cb)
-    pa, pb = timed((a, b), (ca, cb))
-    R, NNZ, U = (sum(getattr(c, n) for c in cb) / NB for n in ("R", "NNZ", "U"))
+    prepare(c, cc)
+    pa, pb, pc = timed((a, b, c), (ca, cb, cc))
+    R, NNZ, U = (sum(getattr(x, n) for x in cb) / NB for n in ("R", "NNZ", "U"))
 
-    class _Dims:   # (the cells minibatch has no key list: the valued one's dimensions)
+    class _Dims:   # (a cells minibatch has no key list: the generic one's dimensions)
         pass
     da = []
-    for c in cb:
+    for x in cb:
         d = _Dims()
-        d.R, d.NNZ, d.U = c.R, c.NNZ, c.U
+        d.R, d.NNZ, d.U = x.R, x.NNZ, x.U
         da.append(d)
-    return {"optimizer": opt, "zipf": args.zipf,
-            "binary_cells": side(pa, da, lr_bytes(NNZ, R, U, opt, False)),
-            "valued_generic": side(pb, cb, lr_bytes(NNZ, R, U, opt, True)),
-            "note": "orientation only: different algorithms"}
+    res = {"optimizer": opt, "zipf": args.zipf,
+           "binary_cells": side(pa, da, lr_bytes(NNZ, R, U, opt, False)),
+           "valued_generic": side(pb, cb, lr_bytes(NNZ, R, U, opt, True)),
+           "valued_cells": side(pc, da, lr_bytes(NNZ, R, U, opt, True)),
+           "cells_info": cc[0].cells_info()}
+    res["valued_cells_over_binary_cells"] = res["valued_cells"]["ms_per_step"] / \
+        res["binary_cells"]["ms_per_step"]
+    res["valued_generic_over_valued_cells"] = res["valued_generic"]["ms_per_step"] / \
+        res["valued_cells"]["ms_per_step"]
+    del ca, cb, cc
+    res.update(lr_build_and_once(
+        batches, vals, {"binary_local": a.w, "valued_generic": b.w, "valued_local": c.w},
+        {"binary_local": a.ws, "valued_generic": b.ws, "valued_local": c.ws}))
+    return res
 
 
 def main():

@@ -144,7 +144,12 @@ SIGNATURES = {
                                              C.c_uint32, C.c_int, vp]),
     "xf_batch_compile_local": (C.c_int, [C.POINTER(vp), vp, u64p, u64p, i32p, C.c_size_t,
                                          C.c_size_t, C.c_int, vp]),
+    "xf_batch_compile_local_valued": (C.c_int, [C.POINTER(vp), vp, u64p, u64p, f32p, i32p,
+                                                C.c_size_t, C.c_size_t, C.c_int, vp]),
+    "xf_batch_compile_local_valued_dev": (C.c_int, [C.POINTER(vp), vp, vp, vp, vp, vp,
+                                                    C.c_uint32, C.c_uint32, C.c_int, vp]),
     "xf_batch_cells_info": (C.c_int, [vp, u32p]),
+    "xf_sbatch_cells_info": (C.c_int, [vp, u32p]),
     "xf_source_hash": (C.c_char_p, []),
     "xf_workspace_capture": (C.c_int, [vp, C.c_int]),
     "xf_workspace_parity": (C.c_int, [vp, C.c_int]),
@@ -347,8 +352,17 @@ def hash_str(s):
     return int(lib().xf_hash_bytes(b, len(b)))
 
 
+_tuned = {}
+
+
 def tune(name, value):
     check(lib().xf_tune(name.encode(), float(value)))
+    _tuned[name] = float(value)
+
+
+def tuned(name, default=0.0):
+    """the value tune() last gave a knob in this process (the library's default: `default`)"""
+    return _tuned.get(name, default)
 
 
 def hash_decimal_range(start, n):
@@ -820,18 +834,28 @@ class FmBatch(Batch):
 
 class LocalBatch:
     """A minibatch compiled straight against one table on this GPU (xf_batch_compile_local):
-    raw keys -> state rows -> cells; no key list.  Feeds lr_step / lr_predict on that table."""
+    raw keys -> state rows -> cells; no key list.  Feeds lr_step / lr_predict on that table.
+    values (one fp32 per nonzero): feature values — xf_batch_compile_local_valued, the cells
+    carry them."""
 
-    def __init__(self, table, rowptr, keys, labels, row_begin=0, row_end=None, retain_keys=True):
+    def __init__(self, table, rowptr, keys, labels, row_begin=0, row_end=None, retain_keys=True,
+                 values=None):
         rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         labels = np.ascontiguousarray(labels, dtype=np.int32)
         if row_end is None:
             row_end = len(rowptr) - 1
         self.h = vp()
-        check(lib().xf_batch_compile_local(C.byref(self.h), table.h, _p(rowptr, u64p),
-                                           _p(keys, u64p), _p(labels, i32p), row_begin, row_end,
-                                           1 if retain_keys else 0, None))
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float32)
+            assert len(values) == len(keys), "one value per nonzero"
+            check(lib().xf_batch_compile_local_valued(
+                C.byref(self.h), table.h, _p(rowptr, u64p), _p(keys, u64p), _p(values, f32p),
+                _p(labels, i32p), row_begin, row_end, 1 if retain_keys else 0, None))
+        else:
+            check(lib().xf_batch_compile_local(C.byref(self.h), table.h, _p(rowptr, u64p),
+                                               _p(keys, u64p), _p(labels, i32p), row_begin,
+                                               row_end, 1 if retain_keys else 0, None))
         R, N = C.c_uint32(), C.c_uint32()
         check(lib().xf_batch_dims(self.h, C.byref(R), C.byref(N), None, None))
         self.R, self.NNZ, self.U, self.H = R.value, N.value, 0, 0
@@ -1165,6 +1189,14 @@ class ShardedBatch:
         check(lib().xf_sbatch_dims(h, C.byref(R), C.byref(N), C.byref(U), C.byref(own)))
         self.R, self.NNZ, self.U, self.n_owned = R.value, N.value, U.value, own.value
         self.keyed = lib().xf_sbatch_fm_keyed(h) == 1
+
+    def local_cells_info(self):
+        """cells_info() of the minibatch's cells over the table's rows (a one-rank LR minibatch
+        of the local builds: which build a compile took); XFError where it has none"""
+        out = (C.c_uint32 * 8)()
+        check(lib().xf_sbatch_cells_info(self.h, out))
+        names = ["W", "nwin", "nchunk", "G", "nitems", "segments", "nsplit_chunks", "M"]
+        return dict(zip(names, list(out)))
 
     def __del__(self):
         try:

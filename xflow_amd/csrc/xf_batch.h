@@ -84,6 +84,11 @@ struct xf_batch {
   const uint64_t *raw_keys = nullptr;
   const uint32_t *raw_rowptr = nullptr;
   const int32_t *raw_labels = nullptr;
+  // ... with feature values (xf_batch_compile_local_valued_*, LR): the values are in the cells
+  // (xf_cells::vals); `valued` stays false — there is no xval / coo_val.  The raw values are kept
+  // with the raw keys (d_raw: ... | vals f32[NNZ]).
+  bool local_valued = false;
+  const float *raw_vals = nullptr;
 };
 
 namespace xf {

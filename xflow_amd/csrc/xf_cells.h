@@ -79,6 +79,11 @@ struct xf_cells {
   uint32_t *entries_k = nullptr;    // [NNZ] the same cells sorted by key (the forward's stream;
                                     //       == entries when the copy was not built)
   bool entries_k_ready = false;     // (a forward before cells_key_sorted_copy reads `entries`)
+  // feature values (xf_cells_valued.hip): the value of every nonzero, in the order of `entries`
+  // — streamed beside them from the same offsets, never gathered.  Null for a binary minibatch
+  // (whose allocation is what it was).  Valued cells are one segment without holes and have no
+  // key-sorted copy (entries_k == entries): one value array serves both passes.
+  float *vals = nullptr;            // [NNZ]
   const uint32_t *fwd_entries() const { return entries_k_ready ? entries_k : entries; }
   uint32_t *cellptr = nullptr;      // [ncell + 1]
   uint32_t *blk_cell = nullptr;     // [nblk + 1] cell of entry kBlk*b; [nblk] = ncell - 1
@@ -104,10 +109,13 @@ namespace xf {
 // d_rowid != null: the nonzeros come in any order with their row number (d_rowptr unused, no
 // map); the rows are then numbered window by window by the caller: w_fixed rows per window.
 // chunk0 != 0: a segment over the chunks from chunk0 on (every position is >= chunk0 * kChunk).
+// d_xval != null: valued cells — d_xval[j] is the value of nonzero j, in the order of d_src (CSR
+// order, or the order of d_rowid); it goes through the same stable permutation as its entry (no
+// key-sorted copy is built: key_sorted_copy is ignored).
 int cells_build(xf_cells **out, const uint32_t *d_src, const uint32_t *d_map,
                 const uint32_t *d_rowptr, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
                 bool key_sorted_copy, hipStream_t stream, const uint32_t *d_rowid = nullptr,
-                uint32_t w_fixed = 0, uint32_t chunk0 = 0);
+                uint32_t w_fixed = 0, uint32_t chunk0 = 0, const float *d_xval = nullptr);
 void cells_free(xf_cells *c);  // the whole chain
 
 // The key build of LRWorker::update (lr_worker.cc:146-166) against table `t` on this GPU,
@@ -133,7 +141,7 @@ int cells_build_keyed_finish(KbDeferred *d, hipStream_t stream, bool *more);
 
 // pieces of cells_build shared with the keyed build
 int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
-                bool key_sorted_copy, uint32_t w_fixed, uint32_t chunk0);
+                bool key_sorted_copy, uint32_t w_fixed, uint32_t chunk0, bool valued = false);
 int cells_plan_items(xf_cells *c, hipStream_t stream);            // after cellptr is final
 int cells_fill_items(xf_cells *c, uint32_t nitems, uint32_t nsplit, hipStream_t stream);
 int cells_key_sorted_copy(xf_cells *c, hipStream_t stream);
@@ -148,6 +156,19 @@ size_t cells_partial_doubles(const xf_cells *c);
 int cells_lr_forward(const xf_cells *c, const float *d_w, const int32_t *d_labels,
                      double *d_partial, float *d_loss, float *d_pctr, hipStream_t stream,
                      const xf_cells *resume_from = nullptr);
+
+// feature values on cells (xf_cells_valued.hip; c->vals != null, one segment):
+//   wx_r = fp32(sum_j fp32(w[row_j] x_j))      gw = fp32(fp32(sum_occ fp32(loss_r x_occ)) / R)
+// the function of xf_valued.hip; the gradient steps the table in place as cells_lr_grad_update
+// (the build's sort for valued cells: entries / vals = ent / xval in the stable order of cid's low
+// `bits` bits, cid_s = cid sorted)
+int cells_sort_valued(const uint32_t *cid, uint32_t *cid_s, const uint32_t *ent,
+                      const float *xval, uint32_t n, int bits, uint32_t *entries, float *vals,
+                      hipStream_t stream);
+int cells_lr_forward_valued(const xf_cells *c, const float *d_w, const int32_t *d_labels,
+                            double *d_partial, float *d_loss, float *d_pctr, hipStream_t stream);
+int cells_lr_grad_update_valued(const xf_cells *c, const xf_table *t, const float *d_loss,
+                                hipStream_t stream);
 
 // owner-compute step (xf_sharded.hip): forward up to the fp64 row sums, and the gradient with
 // the Pushes of several workers applied in rank order (see xf_cells.hip)

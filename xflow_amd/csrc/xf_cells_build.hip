@@ -360,7 +360,7 @@ uint32_t cells_split_chunks(const xf_cells *c) {
 // geometry + the allocation whose size the shape decides: entries (two copies when the
 // key-sorted one is wanted), cellptr, blk_cell, the item plan
 int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
-                bool key_sorted_copy, uint32_t w_fixed, uint32_t chunk0) {
+                bool key_sorted_copy, uint32_t w_fixed, uint32_t chunk0, bool valued) {
   XF_REQUIRE(out, "cells_alloc: null argument");
   XF_REQUIRE(w_fixed <= kWinMax, "cells_alloc: %u rows per window", w_fixed);
   xf_cells *c = new xf_cells;
@@ -395,7 +395,9 @@ int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
   const size_t o_cellptr = o_entk + al(key_sorted_copy ? (size_t)NNZ * 4 : 0);
   const size_t o_blk = o_cellptr + al(((size_t)c->ncell + 1) * 4);
   const size_t o_plan = o_blk + al(((size_t)c->nblk + 1) * 4);
-  const size_t total = o_plan + al(4 * ((size_t)c->nchunk + 1) * 4) + 256;
+  // (the values behind everything a binary minibatch has: its offsets and size stay what they were)
+  const size_t o_vals = o_plan + al(4 * ((size_t)c->nchunk + 1) * 4);
+  const size_t total = o_vals + (valued ? al((size_t)NNZ * 4) : 0) + 256;
   int rc = blob_alloc((void **)&c->blob, total, &c->blob_bytes);
   if (rc != XF_OK) {
     delete c;
@@ -406,6 +408,7 @@ int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
   c->cellptr = (uint32_t *)(c->blob + o_cellptr);
   c->blk_cell = (uint32_t *)(c->blob + o_blk);
   c->plan = (uint32_t *)(c->blob + o_plan);
+  if (valued) c->vals = (float *)(c->blob + o_vals);
   *out = c;
   return XF_OK;
 }
@@ -470,13 +473,14 @@ int cells_fill_items(xf_cells *c, uint32_t nitems, uint32_t nsplit, hipStream_t 
 int cells_build(xf_cells **out, const uint32_t *d_src, const uint32_t *d_map,
                 const uint32_t *d_rowptr, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
                 bool key_sorted_copy, hipStream_t s, const uint32_t *d_rowid, uint32_t w_fixed,
-                uint32_t chunk0) {
+                uint32_t chunk0, const float *d_xval) {
   XF_REQUIRE(out && (d_rowptr || d_rowid || NNZ == 0) && (NNZ == 0 || d_src),
              "cells_build: null argument");
   XF_REQUIRE(!d_rowid || (w_fixed >= 1 && w_fixed <= kWinMax && !d_map),
              "cells_build: row ids need a window size");
+  const bool valued = d_xval != nullptr;
   xf_cells *c = nullptr;
-  XF_TRY(cells_alloc(&c, R, NNZ, M, mode, key_sorted_copy, w_fixed, chunk0));
+  XF_TRY(cells_alloc(&c, R, NNZ, M, mode, key_sorted_copy && !valued, w_fixed, chunk0, valued));
   struct Guard {
     xf_cells *c;
     ~Guard() {
@@ -499,12 +503,16 @@ int cells_build(xf_cells **out, const uint32_t *d_src, const uint32_t *d_map,
       int bits = 1;
       while (bits < 32 && (1ull << bits) < (uint64_t)c->ncell) ++bits;
       size_t tb = 0;
-      XF_HIP(rocprim::radix_sort_pairs(nullptr, tb, cid, cid_s, ent, c->entries, (size_t)NNZ, 0,
-                                       bits, s));
       void *tmp = nullptr;
-      XF_TRY(sc.get((char **)&tmp, tb));
-      XF_HIP(rocprim::radix_sort_pairs(tmp, tb, cid, cid_s, ent, c->entries, (size_t)NNZ, 0, bits,
-                                       s));
+      if (valued) {  // (entry, value) as one payload through the same stable sort
+        XF_TRY(cells_sort_valued(cid, cid_s, ent, d_xval, NNZ, bits, c->entries, c->vals, s));
+      } else {
+        XF_HIP(rocprim::radix_sort_pairs(nullptr, tb, cid, cid_s, ent, c->entries, (size_t)NNZ, 0,
+                                         bits, s));
+        XF_TRY(sc.get((char **)&tmp, tb));
+        XF_HIP(rocprim::radix_sort_pairs(tmp, tb, cid, cid_s, ent, c->entries, (size_t)NNZ, 0,
+                                         bits, s));
+      }
     }
     hipLaunchKernelGGL(k_cellptr, dim3(grid_for((size_t)c->ncell + 1)), dim3(kBlock), 0, s, cid_s,
                        NNZ, c->ncell, c->cellptr);
@@ -531,6 +539,23 @@ int cells_build(xf_cells **out, const uint32_t *d_src, const uint32_t *d_map,
 // ---------------------------------------------------------------- cells of a compiled batch
 namespace xf {
 
+// The cells of a valued local minibatch: the sort-based local build (general_build's second half,
+// xf_keybuild.hip) with the values — a probe of the table per nonzero (insert on first touch; the
+// table grows when needed; the same key many times in one launch is k_resolve's case: the lane
+// that wins the insert publishes the row, the others wait for it), then cells_build.  Always
+// one segment without holes.  Synchronises `stream`.
+static int cells_build_local_valued(xf_cells **out, xf_table *t, const uint64_t *d_keys,
+                                    const float *d_vals, const uint32_t *d_rowptr, uint32_t R,
+                                    uint32_t NNZ, hipStream_t s) {
+  Scratch sc;
+  uint32_t *idx = nullptr;
+  XF_TRY(sc.get(&idx, NNZ));
+  if (NNZ) XF_TRY(table_resolve_any(t, d_keys, NNZ, idx, s, true));
+  const uint64_t M = table_dev(t).max_rows + 1;
+  return cells_build(out, idx, nullptr, d_rowptr, R, NNZ, (uint32_t)M, kCellsTableRows, false, s,
+                     nullptr, 0, 0, NNZ ? d_vals : nullptr);
+}
+
 // Make b->cells the cells of `b` against table `t`'s current row numbering.  Batches with a
 // key list (xf_batch_compile*): Pull's key -> row resolve (insert on first touch, ftrl.h:56)
 // over the sorted unique keys, then uidx -> row.  Local batches: the retained raw keys are
@@ -552,8 +577,12 @@ int ensure_cells(xf_batch *b, xf_table *t, hipStream_t s) {
                "this minibatch was compiled against another table (or the table has renumbered "
                "its rows since) and did not keep its keys: compile it again, or with "
                "retain_keys = 1");
-    XF_TRY(cells_build_keyed(&c, t, b->raw_keys, b->raw_rowptr, nullptr, b->R, b->NNZ, true, 0,
-                             s));
+    if (b->local_valued)
+      XF_TRY(cells_build_local_valued(&c, t, b->raw_keys, b->raw_vals, b->raw_rowptr, b->R,
+                                      b->NNZ, s));
+    else
+      XF_TRY(cells_build_keyed(&c, t, b->raw_keys, b->raw_rowptr, nullptr, b->R, b->NNZ, true, 0,
+                               s));
   } else {
     XF_TRY(xf_batch_upload(b, s));
     if (!b->d_rows_u) XF_HIP(hipMalloc((void **)&b->d_rows_u, std::max<size_t>(b->U, 1) * 4));
@@ -646,6 +675,73 @@ extern "C" int xf_batch_compile_local(xf_batch **out, xf_table *t, const uint64_
                           row_end, (hipStream_t)stream, "xf_batch_compile_local"));
   return xf_batch_compile_local_dev(out, t, d.d_keys, d.d_rowptr, d.d_labels, d.R, d.NNZ,
                                     retain_keys, stream);
+}
+
+// The same with feature values (LR): the sort-based local build — no key list, no uidx, no
+// coo_val; the values ride with the entries into the cells (xf_cells.h: vals).  retain_keys also
+// keeps the raw values, for the rebuild after xf_table_defrag.
+extern "C" int xf_batch_compile_local_valued_dev(xf_batch **out, xf_table *t,
+                                                 const uint64_t *d_keys, const float *d_vals,
+                                                 const uint32_t *d_rowptr, const int32_t *d_labels,
+                                                 uint32_t R, uint32_t NNZ, int retain_keys,
+                                                 void *stream) {
+  XF_REQUIRE(out && t && d_rowptr && (R == 0 || d_labels) && (NNZ == 0 || (d_keys && d_vals)),
+             "xf_batch_compile_local_valued_dev: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  xf_batch *b = new xf_batch;
+  struct Guard {
+    xf_batch *b;
+    ~Guard() {
+      if (b) xf_batch_free(b);
+    }
+  } guard{b};
+  b->R = R;
+  b->NNZ = NNZ;
+  b->local = true;
+  b->local_valued = true;
+  b->on_device_only = true;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_lab = 0;
+  const size_t o_rp = o_lab + al((size_t)R * 4);
+  const size_t o_keys = o_rp + al(retain_keys ? ((size_t)R + 1) * 4 : 0);
+  const size_t o_vals = o_keys + al(retain_keys ? (size_t)NNZ * 8 : 0);
+  const size_t total = o_vals + al(retain_keys ? (size_t)NNZ * 4 : 0) + 256;
+  XF_TRY(xf::blob_alloc(&b->d_raw, total, &b->d_raw_bytes));
+  char *d = (char *)b->d_raw;
+  if (R) XF_HIP(hipMemcpyAsync(d + o_lab, d_labels, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
+  b->raw_labels = (const int32_t *)(d + o_lab);
+  if (retain_keys) {
+    XF_HIP(hipMemcpyAsync(d + o_rp, d_rowptr, ((size_t)R + 1) * 4, hipMemcpyDeviceToDevice, s));
+    if (NNZ) {
+      XF_HIP(hipMemcpyAsync(d + o_keys, d_keys, (size_t)NNZ * 8, hipMemcpyDeviceToDevice, s));
+      XF_HIP(hipMemcpyAsync(d + o_vals, d_vals, (size_t)NNZ * 4, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  XF_TRY(xf::cells_build_local_valued(&b->cells, t, d_keys, d_vals, d_rowptr, R, NNZ, s));
+  b->cells->table_uid = xf::table_uid(t);
+  b->cells->epoch = xf::table_epoch(t);
+  if (retain_keys) {
+    b->raw_rowptr = (const uint32_t *)(d + o_rp);
+    b->raw_keys = (const uint64_t *)(d + o_keys);
+    b->raw_vals = (const float *)(d + o_vals);
+  }
+  guard.b = nullptr;
+  *out = b;
+  return XF_OK;
+}
+
+extern "C" int xf_batch_compile_local_valued(xf_batch **out, xf_table *t, const uint64_t *rowptr,
+                                             const uint64_t *keys, const float *vals,
+                                             const int32_t *labels, size_t row_begin,
+                                             size_t row_end, int retain_keys, void *stream) {
+  XF_REQUIRE(out && t && rowptr && labels && row_end >= row_begin,
+             "xf_batch_compile_local_valued: bad argument");
+  xf::Scratch sc;
+  xf::SliceDev d;
+  XF_TRY(xf::upload_slice(&d, sc, rowptr, keys, nullptr, false, vals, true, labels, row_begin,
+                          row_end, (hipStream_t)stream, "xf_batch_compile_local_valued"));
+  return xf_batch_compile_local_valued_dev(out, t, d.d_keys, d.d_vals, d.d_rowptr, d.d_labels, d.R,
+                                           d.NNZ, retain_keys, stream);
 }
 
 // shape of a batch's cells (tests / bench): out[0..8) = W, nwin, nchunk, G, nitems,

@@ -6,22 +6,10 @@
 // Layout and rationale: xf_cells.h.  Numerics: a row's sum is accumulated in fp64 (LDS atomics)
 // and rounded to fp32 once, where the reference holds an fp32 value — exact, hence independent
 // of the order the atomics land in (xf_cells_grad.hip has the bound).  No MFMA.
-#include "xf_cells_impl.h"
+#include "xf_cells_fwd.h"
 
 namespace {
 // ------------------------------------------------------------------------------ forward
-// the cell of entry j, known to lie in [lo, hi]: the largest c with cellptr[c] <= j
-__device__ __forceinline__ uint32_t cell_of(const uint32_t *__restrict__ cellptr, uint32_t lo,
-                                            uint32_t hi, uint32_t j) {
-  while (lo < hi) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (cellptr[mid] <= j) lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
-}
-
 // Workgroup (v, g) takes the g-th of G slices of window v's entries, cut at multiples of kBlk
 // in the entry stream.  Its 16 wavefronts pull blocks of kBlk entries (kFwdE per lane) off a
 // counter in LDS and keep the NEXT block's index loads in flight while they work on the
@@ -34,25 +22,6 @@ __device__ __forceinline__ uint32_t cell_of(const uint32_t *__restrict__ cellptr
 // atomic.  An entry's cell follows from the block's first cell and the 5 chunk-number bits the entry carries; only
 // a block that spans 32 or more chunks (a sparse minibatch on a big table) searches cellptr.
 // The partial row sums of the G workgroups of a window are added by k_lr_finalize_cells.
-constexpr int kFwdE = (int)(kBlk / 64);
-
-struct FwdBlock {
-  uint32_t ent[kFwdE];
-  uint32_t lo, hi;
-};
-
-__device__ __forceinline__ void fwd_load(FwdBlock &B, const uint32_t *__restrict__ entries,
-                                         const uint32_t *__restrict__ blk_cell, uint32_t b,
-                                         uint32_t pb, uint32_t pe, uint32_t lane) {
-  B.lo = blk_cell[b];
-  B.hi = blk_cell[b + 1];
-#pragma unroll
-  for (int q = 0; q < kFwdE; ++q) {
-    const uint32_t j = b * kBlk + q * 64 + lane;
-    B.ent[q] = (j >= pb && j < pe) ? entries[j] : 0xFFFFFFFFu;
-  }
-}
-
 __device__ __forceinline__ void fwd_process(const FwdBlock &B, uint32_t b, uint32_t c0,
                                             uint32_t nchunk, uint32_t lane,
                                             const uint32_t *__restrict__ cellptr,
@@ -185,6 +154,16 @@ int cells_lr_forward(const xf_cells *c, const float *d_w, const int32_t *d_label
     hipLaunchKernelGGL(k_lr_fwd_cells, dim3(q->nwin * q->G), dim3(kFwdBlock), 0, s, q->fwd_entries(),
                        q->cellptr, q->blk_cell, q->nchunk, q->W, q->G,
                        d_w + (size_t)q->chunk0 * kChunk, d_partial, acc);
+  hipLaunchKernelGGL(k_lr_finalize_cells,
+                     dim3((unsigned)(((size_t)c->R * 4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                     d_partial, d_labels, c->R, c->W, c->G, d_loss, d_pctr);
+  XF_HIP(hipGetLastError());
+  return XF_OK;
+}
+
+// the rows' losses from the partial sums a forward kernel of another file left (xf_cells_valued.hip)
+int cells_lr_finalize(const xf_cells *c, const double *d_partial, const int32_t *d_labels,
+                      float *d_loss, float *d_pctr, hipStream_t s) {
   hipLaunchKernelGGL(k_lr_finalize_cells,
                      dim3((unsigned)(((size_t)c->R * 4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
                      d_partial, d_labels, c->R, c->W, c->G, d_loss, d_pctr);

@@ -1,5 +1,5 @@
 // xf_cells_grad.h — device helpers of the gradient (+ Push) kernels (internal; included by
-// xf_cells_grad.hip and xf_cells_grad_dense.hip).
+// xf_cells_grad.hip, xf_cells_grad_dense.hip and xf_cells_valued.hip).
 #ifndef XF_CELLS_GRAD_H_
 #define XF_CELLS_GRAD_H_
 
@@ -118,5 +118,9 @@ constexpr int kGradE = XF_GRAD_E;  // entries per lane and round
 constexpr uint32_t kGradWin = 32;  // windows whose slice bounds fit the LDS table
 constexpr uint32_t kSparseKeys = 2 * 256;  // touched keys of a chunk that are stepped from a list
 }  // namespace
+
+namespace xf {
+int cells_launch_split_finish(int opt, const xf_cells *c, const TableDev &T, hipStream_t s);
+}  // namespace xf
 
 #endif  // XF_CELLS_GRAD_H_

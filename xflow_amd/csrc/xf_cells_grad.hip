@@ -1124,4 +1124,21 @@ int cells_lr_grad_update_sources(const xf_cells *c, const xf_table *t, const flo
   return XF_OK;
 }
 
+// k_lr_grad_split_finish<opt, 0> for one source, behind a gradient kernel of another file whose
+// slices added into c->gsum / c->gtouched (xf_cells_valued.hip); leaves the accumulators zero
+int cells_launch_split_finish(int opt, const xf_cells *c, const TableDev &T, hipStream_t s) {
+  if (!c->nsplit_chunks) return XF_OK;
+  const dim3 grid(c->nsplit_chunks * (kChunk / kBlock)), blk(kBlock);
+  if (opt == XF_OPT_FTRL)
+    hipLaunchKernelGGL((k_lr_grad_split_finish<XF_OPT_FTRL, 0>), grid, blk, 0, s, T, c->split_chunk,
+                       c->gsum, c->gtouched, c->R, c->M, (float *)nullptr, 1u,
+                       (const uint32_t *)nullptr, c->nsplit_chunks, c->chunk0, 1);
+  else
+    hipLaunchKernelGGL((k_lr_grad_split_finish<XF_OPT_SGD, 0>), grid, blk, 0, s, T, c->split_chunk,
+                       c->gsum, c->gtouched, c->R, c->M, (float *)nullptr, 1u,
+                       (const uint32_t *)nullptr, c->nsplit_chunks, c->chunk0, 1);
+  XF_HIP(hipGetLastError());
+  return XF_OK;
+}
+
 }  // namespace xf

@@ -1,10 +1,12 @@
-// xf_cells_impl.h — what the four files of the cells path share (internal): launch constants,
+// xf_cells_impl.h — what the files of the cells path share (internal): launch constants,
 // the table module's hooks, and the gradient pass's hand-over between its two files.
 //   xf_cells_build.hip       cells of a minibatch (general build, item plan, the forward's copy)
 //   xf_cells_fwd.hip         forward: k_lr_fwd_cells, k_lr_finalize_cells
 //   xf_cells_grad.hip        gradient (+ Push): the general kernel, the several-workers passes,
 //                            the choice between them
 //   xf_cells_grad_dense.hip  the steady state's gradient + Push: k_lr_grad_dense
+//   xf_cells_valued.hip      feature values: the valued forward and gradient + Push, the
+//                            build's sort with a value per entry
 #ifndef XF_CELLS_IMPL_H_
 #define XF_CELLS_IMPL_H_
 

@@ -33,7 +33,12 @@ void scratch_poison();
 //   owner_pass   an owner's gradient + Pushes for several workers: 0 by shape; 1 the general
 //                loop (a sweep per worker); 2 the workers' phases merged (k_lr_grad_ranked);
 //                3 the same with 32-bit worker masks; 4 a phase per worker (k_lr_grad_multi)
-enum PathSwitch { kPathKeyBuild = 0, kPathOldWeight, kPathLrGradient, kPathOwnerPass, kPathCount };
+//   valued_lr    a valued LR minibatch of a one-rank trainer (xf_sharded.hip: build_valued): 0 by
+//                shape (today: the local build whatever the shape); 1 the generic build + the
+//                tile kernels (xf_valued.hip); 2 the local build + the valued cell kernels
+//                (xf_cells_valued.hip)
+enum PathSwitch { kPathKeyBuild = 0, kPathOldWeight, kPathLrGradient, kPathOwnerPass,
+                  kPathValuedLr, kPathCount };
 int path_switch(int which);
 void set_path_switch(int which, int v);
 inline int key_build_mode() { return path_switch(kPathKeyBuild); }

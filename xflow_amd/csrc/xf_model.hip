@@ -1916,11 +1916,15 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
 // feature values: the step / predict of a valued minibatch (below, with the canonical FM's)
 static int lr_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream);
 static int lr_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out);
+// ... and of a valued LOCAL minibatch: the valued cell kernels (xf_cells_valued.hip)
+static int lr_local_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream);
+static int lr_local_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out);
 
 extern "C" int xf_lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream) {
   XF_REQUIRE(w && b && ws, "xf_lr_step: null argument");
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_lr_step: the w table must have dim 1");
   if (b->valued) return lr_valued_step(w, b, ws, stream);
+  if (b->local_valued) return lr_local_valued_step(w, b, ws, stream);
   return lr_step(w, b, ws, stream, nullptr);
 }
 
@@ -2396,10 +2400,56 @@ static int lr_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *
   return xf_table_check(w, nullptr);
 }
 
+// ---- feature values, LR, on a local minibatch (xf_batch_compile_local_valued*): the step of a
+// binary local minibatch with the valued cell kernels — the cells (built with the table's rows,
+// the Pull's inserts included) carry the values; forward, then gradient + Push in place.  No key
+// list: xf_workspace_fetch yields the loss.  Refused before the cells are looked at: a refusal
+// leaves the table as it was.
+static int lr_local_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream) {
+  XF_TRY(valued_check(ws, "xf_lr_step"));
+  XF_TRY(xf::ensure_cells(b, w, S(stream)));  // Pull (:170): keys -> state rows, inserts
+  const xf_cells *c = b->cells;
+  XF_TRY(ws_reserve(ws, 0, 0, b->R));
+  XF_TRY(ws_reserve_cells(ws, c, false));
+  ws->rec = ws->profiling && ws->step_no++ % xf_workspace::kProfileEvery == 0;
+  if (ws->rec) XF_TRY(ws_next_set(ws));
+  ws->lastU = 0;
+  ws->lastR = b->R;
+  XF_BEGIN();
+  XF_TRY(xf::cells_lr_forward_valued(c, xf::table_dev(w).w, b->raw_labels, ws->partial, ws->loss,
+                                     nullptr, S(stream)));  // :172
+  XF_END(kEvForward);
+  XF_TRY(xf::cells_lr_grad_update_valued(c, w, ws->loss, S(stream)));  // :173, :175
+  XF_END(kEvGrad);
+  if (ws->rec) ws->sets[ws->cur].pending = true;
+  return XF_OK;
+}
+
+static int lr_local_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out) {
+  XF_TRY(valued_check(ws, "xf_lr_predict"));
+  XF_TRY(xf::ensure_cells(b, w, nullptr));
+  XF_TRY(ws_reserve(ws, 0, 0, b->R));
+  XF_TRY(ws_reserve_cells(ws, b->cells, false));
+  XF_TRY(xf::cells_lr_forward_valued(b->cells, xf::table_dev(w).w, b->raw_labels, ws->partial,
+                                     ws->loss, ws->pctr, nullptr));
+  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  return xf_table_check(w, nullptr);
+}
+
+// a local minibatch with feature values is LR's alone (its values live in the cells)
+static int no_local_valued(const xf_batch *b, const char *who) {
+  XF_REQUIRE(!b->local_valued,
+             "%s: a local minibatch with feature values (xf_batch_compile_local_valued*) is "
+             "stepped and scored by xf_lr_step / xf_lr_predict only: FM needs a minibatch with a "
+             "key list and its value arrays (xf_batch_compile_valued*)", who);
+  return XF_OK;
+}
+
 extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
                           void *stream) {
   XF_REQUIRE(w && vt && b && ws, "xf_fm_step: null argument");
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_fm_step: the w table must have dim 1");
+  XF_TRY(no_local_valued(b, "xf_fm_step"));
   XF_REQUIRE(!b->local, "xf_fm_step: needs a minibatch with a key list (xf_batch_compile*)");
   if (ws->fm_mode == XF_FM_FIELD_AWARE) return fm_field_aware_step(w, vt, b, ws, stream);
   if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_step(w, vt, b, ws, stream);
@@ -2663,6 +2713,7 @@ extern "C" int xf_lr_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *
   XF_REQUIRE(w && b && ws && pctr_out, "xf_lr_predict: null argument");
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_lr_predict: the w table must have dim 1");
   if (b->valued) return lr_valued_predict(w, b, ws, pctr_out);
+  if (b->local_valued) return lr_local_valued_predict(w, b, ws, pctr_out);
   XF_TRY(xf::ensure_cells(b, w, nullptr));
   XF_TRY(ws_reserve(ws, b->U, 0, b->R));
   XF_TRY(ws_reserve_cells(ws, b->cells, false));
@@ -2679,6 +2730,7 @@ extern "C" int xf_lr_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *
 extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
                              float *pctr_out) {
   XF_REQUIRE(w && vt && b && ws && pctr_out, "xf_fm_predict: null argument");
+  XF_TRY(no_local_valued(b, "xf_fm_predict"));
   XF_REQUIRE(!b->local, "xf_fm_predict: needs a minibatch with a key list (xf_batch_compile*)");
   if (ws->fm_mode == XF_FM_FIELD_AWARE) return fm_field_aware_predict(w, vt, b, ws, pctr_out);
   if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_predict(w, vt, b, ws, pctr_out);

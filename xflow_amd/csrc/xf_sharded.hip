@@ -1453,6 +1453,15 @@ extern "C" int xf_sbatch_dims(const xf_sbatch *b, uint32_t *R, uint32_t *NNZ, ui
   return XF_OK;
 }
 
+// shape of the minibatch's cells (xf_batch_cells_info) where it has cells over a table's rows — a
+// one-rank LR minibatch of the local builds; an error where it has none (a minibatch with a key
+// list before its first step, every FM minibatch): which build ran, for tests and tools
+extern "C" int xf_sbatch_cells_info(const xf_sbatch *b, uint32_t *out) {
+  XF_REQUIRE(b && out, "xf_sbatch_cells_info: null argument");
+  XF_REQUIRE(b->b, "xf_sbatch_cells_info: the minibatch has no cells over a table's rows");
+  return xf_batch_cells_info(b->b, out);
+}
+
 // the static part of the weight / gradient exchange of a minibatch with a key list (b->b):
 // contiguous owner ranges of the sorted unique keys (ps-lite's slicer), the keys to their
 // owners — once — and the owner's merged walking order
@@ -1588,7 +1597,7 @@ static int build_agreed(xf_sharded *st, int rc, const char *who) {
   return XF_OK;
 }
 
-// Feature values: a valued minibatch always takes the generic build
+// Feature values: a valued minibatch takes the generic build, or LR's local one (build_valued)
 static int valued_trainer_check(const xf_sharded *st, const char *who) {
   XF_TRY(rows_at_hand(st, who, "feature values (feature_values)"));
   XF_REQUIRE(st->cfg.model == 0 || st->fm_mode != XF_FM_REFERENCE,
@@ -1692,8 +1701,19 @@ static int build_plain(xf_sharded *st, xf_sbatch *b, const RawRows &a, int keep)
                                       s);
 }
 
-// a valued minibatch always takes the generic build
-static int build_valued(xf_sharded *st, xf_sbatch *b, const RawRows &a) {
+// A valued minibatch takes the generic build — but LR on one rank with the key build on the
+// device: there the table is local and the minibatch goes straight to state rows and valued
+// cells (xf_batch_compile_local_valued*).  xf_tune "valued_lr": 1 pins the generic build, 2 the
+// local one; 0, by shape, is the local one for every minibatch — measured at configs[1], a
+// minibatch that is stepped once costs 0.90 ms there against 1.60 ms (build + step), a replayed
+// one 0.148 ms a step against 0.333 (DESIGN 3 "Feature values", profiles/values_cells/)
+static int build_valued(xf_sharded *st, xf_sbatch *b, const RawRows &a, int keep) {
+  const int sw = xf::path_switch(xf::kPathValuedLr);
+  if (st->fused && st->cfg.model == 0 && !st->cfg.host_key_build && sw != 1)
+    return a.dev ? xf_batch_compile_local_valued_dev(&b->b, st->tw, a.keys, a.vals, a.d_rowptr,
+                                                     a.labels, a.R, a.NNZ, keep, st->main)
+                 : xf_batch_compile_local_valued(&b->b, st->tw, a.rowptr, a.keys, a.vals, a.labels,
+                                                 a.row_begin, a.row_end, keep, st->main);
   if (a.dev)
     return xf_batch_compile_valued_dev(&b->b, a.keys, a.vals, a.d_rowptr, a.labels, a.R, a.NNZ,
                                        st->main);
@@ -1733,7 +1753,7 @@ static int compile_rows(xf_sharded *st, xf_sbatch **out, RowKind kind, const Raw
   std::unique_ptr<xf_sbatch, SbatchFree> b(new xf_sbatch);
   b->owner = st;
   if (kind == kPlainRows) XF_TRY(build_plain(st, b.get(), a, keep));
-  if (kind == kValuedRows) XF_TRY(build_valued(st, b.get(), a));
+  if (kind == kValuedRows) XF_TRY(build_valued(st, b.get(), a, keep));
   // (a failure of the fielded build is agreed on before any exchange)
   if (kind == kFieldedRows) XF_TRY(build_agreed(st, build_fielded(st, b.get(), a), who));
   if (st->fused) {

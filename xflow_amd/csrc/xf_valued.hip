@@ -7,9 +7,10 @@
 // canonical FM (VAL = true).  The values are streamed with the index they belong to (coalesced,
 // next to uidx / coo_row), never gathered.
 //
-// LR has no valued form of its cell kernels: a valued LR step is the w half of the canonical
-// step — Pull of the key list, a wavefront per row over the CSR, the gradient tiles with the
-// optimizer step in place, heavy keys through the canonical pair of kernels with k = 0.
+// On the GENERIC minibatch a valued LR step is the w half of the canonical step — Pull of the
+// key list, a wavefront per row over the CSR, the gradient tiles with the optimizer step in place,
+// heavy keys through the canonical pair of kernels with k = 0.  (The valued form of LR's cell
+// kernels, on a local minibatch whose cells carry the values: xf_cells_valued.hip.)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

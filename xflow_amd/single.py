@@ -44,8 +44,13 @@ class SingleGpuTrainer:
             assert fgid is not None, "fm_mode='field_aware': compile(..., fgid=...)"
             return capi.Batch(rowptr, keys, labels, on_gpu=True, values=values,
                               fields=self.fields, fgid=fgid)
-        if self.feature_values:  # a valued minibatch always takes the generic build
+        if self.feature_values:
             assert values is not None, "feature_values=True: compile(..., values=...)"
+            # LR: straight to state rows and cells that carry the values, as the one-rank
+            # trainer's compile (capi.tune("valued_lr", 1) pins the generic build); FM: the
+            # generic build
+            if self.model == "lr" and capi.tuned("valued_lr") != 1:
+                return capi.LocalBatch(self.w, rowptr, keys, labels, values=values)
             return capi.Batch(rowptr, keys, labels, on_gpu=True, values=values)
         assert values is None, "values need SingleGpuTrainer(feature_values=True)"
         if self.model == "lr":   # sort-free key build against the table (cells)
