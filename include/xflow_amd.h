@@ -828,9 +828,32 @@ int xf_sharded_load(xf_sharded *st, const char *prefix);
  * xf_admit_export / _import: the 2^log2_slots counters as bytes.  xf_admit_save / _load: a file
  * whose header carries the four parameters; a load into a filter with other parameters is
  * XF_EINVAL naming both sets, a missing or damaged file XF_EIO naming the path.
- * xf_admit_stats: nonzeros seen / kept, summed over the update != 0 applies. */
+ * xf_admit_stats: nonzeros seen / kept, summed over the update != 0 applies.
+ *
+ * One filter shared by the ranks of a group (xf_admit_create_shared, COLLECTIVE; g == NULL: a
+ * plain filter; a group of one computes what a plain filter computes, through the routed kernels
+ * — which is how tools/admit_leg.py times them without a transport): the same logical state, the counters sharded by slot range — per = 4 *
+ * ceil(ceil(2^log2_slots / world) / 4) slots a rank, rank r owns [r * per, min((r + 1) * per,
+ * 2^log2_slots)), possibly nothing (xf_admit_range, host code; xf_admit_range_of: this filter's).
+ * xf_admit_apply_dev / _apply are COLLECTIVE on it (R = 0 / NNZ = 0 is a normal participant): the
+ * minibatches that the ranks hand in at the same call are counted together — c[s] = min(count,
+ * c_old[s] + the occurrences over ALL ranks' nonzeros) — and after the whole count every rank
+ * filters its own minibatch.  The counters equal those of a one-worker filter applied to the
+ * concatenation of the ranks' minibatches, rank r's output is what that filter keeps of r's
+ * arrays: nothing depends on the world size.  Every rank passes the same `update`; differing
+ * flags, or a rank whose arguments are refused, are XF_EINVAL naming the rank on EVERY rank, before
+ * any exchange.  The slots travel by the group's all-to-all-v on the caller's stream, channel 0
+ * (4 bytes out, 1 byte back per nonzero and hash); NNZ * hashes must stay below 2^32, world at
+ * most 256.  xf_admit_export / _import move this rank's range; xf_admit_save (COLLECTIVE: rank 0
+ * gathers the ranges over the bootstrap and writes) and xf_admit_load (COLLECTIVE: every rank
+ * reads its own range) use the one-worker file unchanged, so a file moves between world sizes.
+ * xf_admit_stats stays per rank. */
 typedef struct xf_admit xf_admit;
 uint64_t xf_admit_slot(uint64_t key, uint64_t seed, int log2_slots, int j);
+int xf_admit_range(int log2_slots, int world, int rank, uint64_t *first, uint64_t *n);
+int xf_admit_create_shared(xf_admit **out, xf_group *g, int log2_slots, int hashes, int count,
+                           uint64_t seed);
+int xf_admit_range_of(const xf_admit *a, uint64_t *first, uint64_t *n);
 int xf_admit_create(xf_admit **out, int log2_slots, int hashes, int count, uint64_t seed);
 int xf_admit_destroy(xf_admit *a);
 int xf_admit_params(const xf_admit *a, int *log2_slots, int *hashes, int *count, uint64_t *seed);
@@ -891,7 +914,10 @@ int XFDestroy(void **h);
  *        enters the tables once the filter has seen it that many times; one worker, core_num 1,
  *        key_build=gpu, parity=exact) admit_log2_slots(2 .. 32, default 26) admit_hashes(1 .. 8,
  *        default 3); the filter's seed is `seed`; XFSaveModel writes <path>.admit beside the
- *        model, XFLoadModel needs it.  XFGetMetric: admit_seen admit_kept (nonzeros) */
+ *        model, XFLoadModel needs it.  XFGetMetric: admit_seen admit_kept (nonzeros)
+ *        admit_shared(0|1: the workers of a group share one filter, xf_admit_create_shared, which
+ *        lifts "one worker" — every turn of the training loop and of predict applies collectively,
+ *        the empty minibatch where a rank has no rows; not with schedule=owner / owner_stale1) */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

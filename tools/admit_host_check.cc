@@ -9,6 +9,10 @@
 // Covers: every out-of-range parameter; a save / load round trip; loads of hand-made files — a
 // missing one, a wrong magic, a header that ends early, each of the four parameters off by one,
 // a wrong counter count, a file that ends inside its counters, a counter above the threshold.
+// A shared filter's host side: xf_admit_range over L x world (disjoint, ordered, word-aligned,
+// covering, empty ranges last); the file rank 0 writes from the gathered ranges, byte for byte the
+// one-worker file; every rank's ranged read of it, of a file cut short in another rank's range, and
+// of a counter above the threshold inside and outside its own range.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -124,6 +128,72 @@ int main(int argc, char **argv) {
          "counter above the threshold");
   write_raw(path, raw_file(0xffffffffu, 3, 5, p.seed, 1024, 0, 0));
   expect(xf::admit_file_read(path.c_str(), p, &back) == XF_EINVAL, "absurd header");
+
+  // ---- a shared filter: the slot partition
+  for (int L : {2, 3, 10, 26, 32})
+    for (int world : {1, 2, 3, 7, 8, 255, 256}) {
+      uint64_t at = 0;
+      bool empty_seen = false, ok = true;
+      for (int r = 0; r < world; ++r) {
+        uint64_t first = 1, n = 1;
+        ok = ok && xf_admit_range(L, world, r, &first, &n) == XF_OK && first == at &&
+             first % 4 == 0 && n % 4 == 0 && !(empty_seen && n) && n <= (1ull << 32);
+        empty_seen = empty_seen || n == 0;
+        at += n;
+      }
+      expect(ok && at == (1ull << L), "the ranges partition the slots");
+    }
+  {
+    uint64_t first = 0, n = 0;
+    expect(xf_admit_range(2, 3, 1, &first, &n) == XF_OK && first == 4 && n == 0, "L 2, world 3");
+    expect(xf_admit_range(10, 1, 0, nullptr, nullptr) == XF_OK, "null outputs");
+    expect(xf_admit_range(1, 1, 0, &first, &n) == XF_EINVAL && names("admit_log2_slots"), "L = 1");
+    expect(xf_admit_range(10, 0, 0, &first, &n) == XF_EINVAL, "world 0");
+    expect(xf_admit_range(10, 3, 3, &first, &n) == XF_EINVAL && names("rank 3"), "rank = world");
+    expect(xf_admit_range(10, 3, -1, &first, &n) == XF_EINVAL, "rank -1");
+  }
+  // ---- the gathered write and the ranged reads
+  for (int world : {1, 3, 7}) {
+    // what rank 0 holds after the gather: the ranks' ranges one after the other
+    std::vector<uint8_t> gathered;
+    for (int r = 0; r < world; ++r) {
+      uint64_t first = 0, n = 0;
+      expect(xf_admit_range(p.L, world, r, &first, &n) == XF_OK, "range");
+      gathered.insert(gathered.end(), c.begin() + first, c.begin() + first + n);
+    }
+    expect(gathered == c, "the gathered ranges are the counters in slot order");
+    expect(xf::admit_file_write(path.c_str(), p, gathered.data()) == XF_OK, "gathered write");
+    expect(xf::admit_file_read(path.c_str(), p, &back) == XF_OK && back == c, "one worker reads it");
+    for (int r = 0; r < world; ++r) {
+      uint64_t first = 0, n = 0;
+      xf_admit_range(p.L, world, r, &first, &n);
+      expect(xf::admit_file_read_range(path.c_str(), p, first, n, &back) == XF_OK &&
+                 back == std::vector<uint8_t>(c.begin() + first, c.begin() + first + n),
+             "a rank reads its range");
+    }
+  }
+  expect(xf::admit_file_read_range(path.c_str(), p, 1024, 0, &back) == XF_OK && back.empty(),
+         "a rank that owns nothing");
+  expect(xf::admit_file_read_range(path.c_str(), p, 1000, 25, &back) == XF_EINVAL &&
+             names("outside"), "a range beyond the counters");
+  expect(xf::admit_file_read_range(path.c_str(), p, 1025, 0, &back) == XF_EINVAL, "first > 2^L");
+  expect(xf::admit_file_read_range(path.c_str(), p, 0, 4, nullptr) == XF_EINVAL, "null vector");
+  {
+    xf::AdmitParams q = p;
+    q.N = 6;
+    expect(xf::admit_file_read_range(path.c_str(), q, 0, 4, &back) == XF_EINVAL &&
+               names("saved with"), "ranged read, other parameters");
+  }
+  write_raw(path, raw_file(10, 3, 5, p.seed, 1024, 1000, 5));
+  expect(xf::admit_file_read_range(path.c_str(), p, 0, 344, &back) == XF_EIO &&
+             names("ends before"), "cut short in another rank's range");
+  f = raw_file(10, 3, 5, p.seed, 1024, 1024, 5);
+  f[40 + 700] = 6;
+  write_raw(path, f);
+  expect(xf::admit_file_read_range(path.c_str(), p, 688, 336, &back) == XF_EIO &&
+             names("counter 700") && names("above admit_count"), "a bad counter in its range");
+  expect(xf::admit_file_read_range(path.c_str(), p, 0, 344, &back) == XF_OK && back.size() == 344,
+         "a bad counter in another rank's range is that rank's to refuse");
   remove(path.c_str());
 
   if (failures) {

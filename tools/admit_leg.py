@@ -15,10 +15,17 @@ in ms:
     admit_readonly  block B with update = 0 (predict), median of 5
     key_build_first xf_sharded_compile_dev of B into an empty LR table (first-touch inserts)
     key_build_again the same minibatch compiled again (every key in the table), median of 5
-The filter is the worker's default: 2^26 counters, 3 hashes; admit_count = 2."""
+The filter is the worker's default: 2^26 counters, 3 hashes; admit_count = 2.
+A shared filter (xf_admit_create_shared) on a group of ONE runs beside the plain one on the same
+two blocks: routing, count-by-slot, answer and test-from-answers with every slot staying on the
+rank — what the shared path costs before any transport (`shared_transport` says how the group
+moved the rank's slice to itself: 0 RCCL — a copy on the device —, 1 staged through the host):
+    plain_next5 / shared_next5          block B on a filter that has seen A, median over 5 filters
+    plain_readonly / shared_readonly    block B with update = 0, median of 5"""
 import ctypes as C
 import json
 import os
+import socket
 import statistics
 import sys
 import time
@@ -73,7 +80,28 @@ def ms(fn, repeat=1):
     return statistics.median(out), r
 
 
-def leg(name, zipf, block_mb):
+def next_block(make, a_args, b_args):
+    """median over five fresh filters of: block B on a filter that has seen block A; the last
+    filter and its result come back for the read-only call"""
+    out = []
+    for _ in range(5):
+        flt = make()
+        flt.filter_dev(*a_args)
+        t, r = ms(lambda: flt.filter_dev(*b_args))
+        out.append(t)
+    return statistics.median(out), flt, r
+
+
+def group_of_one():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    # (RCCL when it comes up: the rank's slice to itself is then a copy on the device)
+    return capi.Group(0, 1, "127.0.0.1", port, capi.TRANSPORT_AUTO, device=-1)
+
+
+def leg(name, zipf, block_mb, group):
     rng = np.random.RandomState(7)
     cap = block_mb << 20
     a, b = block_text(rng, cap, zipf), block_text(rng, cap, zipf)
@@ -89,6 +117,14 @@ def leg(name, zipf, block_mb):
     t_next, rb_out = ms(lambda: flt.filter_dev(kb, rb, Rb, Nb))
     t_rep, rb_rep = ms(lambda: flt.filter_dev(kb, rb, Rb, Nb), 5)
     t_ro, _ = ms(lambda: flt.filter_dev(kb, rb, Rb, Nb, update=False), 5)
+    # the shared filter on a group of one beside the plain one
+    capi.Admit(10, 2, group=group).filter_dev(kb, rb, Rb, Nb)          # (warm)
+    A_, B_ = (ka, ra, Ra, Na), (kb, rb, Rb, Nb)
+    t_pn, _, kept_p = next_block(lambda: capi.Admit(26, 2), A_, B_)
+    t_sn, sh, kept_s = next_block(lambda: capi.Admit(26, 2, group=group), A_, B_)
+    assert kept_p[2] == kept_s[2] == rb_out[2]
+    t_sro, _ = ms(lambda: sh.filter_dev(kb, rb, Rb, Nb, update=False), 5)
+    del sh
     warm = capi.Sharded(model="lr", capacity=1 << 12)
     warm.compile_dev(ka, ra, la, min(Ra, 100), 100 * NNZ if Ra >= 100 else 0)
     st = capi.Sharded(model="lr", capacity=30_000_000)
@@ -100,14 +136,17 @@ def leg(name, zipf, block_mb):
             "kept_fresh": ra_out[2], "nnz_a": Na, "kept_next": rb_out[2], "kept_repeat": rb_rep[2],
             "tokenise_ms": t_tok, "admit_fresh_ms": t_fresh, "admit_next_ms": t_next,
             "admit_repeat_ms": t_rep, "admit_readonly_ms": t_ro, "key_build_first_ms": t_kb1,
-            "key_build_again_ms": t_kb2}
+            "key_build_again_ms": t_kb2, "plain_next5_ms": t_pn, "shared_next5_ms": t_sn,
+            "plain_readonly_ms": t_ro, "shared_readonly_ms": t_sro,
+            "shared_transport": group.transport}
 
 
 if __name__ == "__main__":
     capi.require_gpu()
     block_mb = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+    group = group_of_one()
     with open(sys.argv[1], "a") as out:
         for name, zipf in (("uniform", None), ("zipf1.1", 1.1)):
-            rec = leg(name, zipf, block_mb)
+            rec = leg(name, zipf, block_mb, group)
             print(json.dumps(rec), flush=True)
             out.write(json.dumps(rec) + "\n")

@@ -251,6 +251,10 @@ SIGNATURES = {
                                  C.POINTER(C.c_int), C.POINTER(C.c_double)]),
     "xf_admit_slot": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int, C.c_int]),
     "xf_admit_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_uint64]),
+    "xf_admit_create_shared": (C.c_int, [C.POINTER(vp), vp, C.c_int, C.c_int, C.c_int,
+                                         C.c_uint64]),
+    "xf_admit_range": (C.c_int, [C.c_int, C.c_int, C.c_int, u64p, u64p]),
+    "xf_admit_range_of": (C.c_int, [vp, u64p, u64p]),
     "xf_admit_destroy": (C.c_int, [vp]),
     "xf_admit_params": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                   C.POINTER(C.c_uint64)]),
@@ -559,6 +563,15 @@ def admit_slot(key, seed, log2_slots, j):
     return int(lib().xf_admit_slot(int(key), int(seed), int(log2_slots), int(j)))
 
 
+def admit_range(log2_slots, world, rank):
+    """(first slot, number of slots) that `rank` of `world` owns of a shared filter's 2^log2_slots
+    counters (xf_admit_range; host code)"""
+    first, n = C.c_uint64(), C.c_uint64()
+    check(lib().xf_admit_range(int(log2_slots), int(world), int(rank), C.byref(first),
+                               C.byref(n)))
+    return first.value, n.value
+
+
 class AdmitDev(collections.namedtuple(
         "AdmitDev", "d_keys d_rowptr d_labels R NNZ d_fgid d_vals")):
     """A filtered minibatch on the device: pointers (ints; None for an array that was not given)
@@ -569,12 +582,27 @@ class AdmitDev(collections.namedtuple(
 class Admit:
     """Feature admission (xf_admit_*): a counting Bloom filter over 2^log2_slots saturating 8-bit
     counters.  apply() counts a minibatch's nonzeros (update=True) and returns the minibatch
-    without the nonzeros whose key the filter has not seen `count` times."""
+    without the nonzeros whose key the filter has not seen `count` times.  group: one filter
+    shared by the group's ranks (xf_admit_create_shared) — creation, apply, save and load are
+    collective, export / import_ move this rank's range [first_slot, first_slot + n_slots)."""
 
-    def __init__(self, log2_slots, count, hashes=3, seed=0):
+    def __init__(self, log2_slots, count, hashes=3, seed=0, group=None):
         self.h = vp()
         self.log2_slots, self.count, self.hashes, self.seed = log2_slots, count, hashes, seed
-        check(lib().xf_admit_create(C.byref(self.h), log2_slots, hashes, count, seed))
+        self.group = group          # (the filter uses the group: it must outlive it)
+        if group is None:
+            check(lib().xf_admit_create(C.byref(self.h), log2_slots, hashes, count, seed))
+        else:
+            check(lib().xf_admit_create_shared(C.byref(self.h), group.h, log2_slots, hashes,
+                                               count, seed))
+
+    def _range(self):
+        first, n = C.c_uint64(), C.c_uint64()
+        check(lib().xf_admit_range_of(self.h, C.byref(first), C.byref(n)))
+        return first.value, n.value
+
+    first_slot = property(lambda self: self._range()[0])
+    n_slots = property(lambda self: self._range()[1])
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -643,13 +671,15 @@ class Admit:
         return tuple(a for a, _ in out)
 
     def export(self):
-        out = np.empty(1 << self.log2_slots, np.uint8)
+        n = self.n_slots
+        out = np.empty(max(n, 1), np.uint8)
         check(lib().xf_admit_export(self.h, _p(out, C.POINTER(C.c_uint8))))
-        return out
+        return out[:n]
 
     def import_(self, counters):
         counters = np.ascontiguousarray(counters, dtype=np.uint8)
-        assert len(counters) == 1 << self.log2_slots
+        assert len(counters) == self.n_slots
+        counters = counters if len(counters) else np.zeros(1, np.uint8)
         check(lib().xf_admit_import(self.h, _p(counters, C.POINTER(C.c_uint8))))
 
     def save(self, path):

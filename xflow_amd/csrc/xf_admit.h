@@ -35,6 +35,15 @@ XF_ADMIT_HD uint64_t admit_slot(uint64_t key, uint64_t seed, int L, int j) {
   return admit_slot_salted(key, admit_salt(seed, j), L);
 }
 
+// ---- a filter shared by the `world` ranks of a group: the counters sharded by slot range.
+// per = 4 * ceil(ceil(2^L / world) / 4) slots a rank (whole counter words); rank r owns
+// [r * per, min((r + 1) * per, 2^L)) — possibly nothing; owner(s) = s / per, and the local slot
+// s - owner * per fits 32 bits for every L <= 32
+XF_ADMIT_HD uint64_t admit_per(int L, int world) {
+  const uint64_t slots = 1ull << L, w = (uint64_t)world;
+  return ((slots + w - 1) / w + 3) / 4 * 4;
+}
+
 // ---- host only (xf_admit_host.cc)
 struct AdmitParams {
   int L = 0, h = 0, N = 0;
@@ -48,6 +57,10 @@ int admit_file_write(const char *path, const AdmitParams &p, const uint8_t *coun
 // reads a file written for exactly `want` (XF_EINVAL naming both parameter sets otherwise; XF_EIO:
 // missing, short or not such a file — the message names the path) into `counters` (2^L bytes)
 int admit_file_read(const char *path, const AdmitParams &want, std::vector<uint8_t> *counters);
+// the same refusals, but only the counters [first, first + n) are read (and looked at): what a
+// rank of a shared filter loads.  The file must still be as long as its header says.
+int admit_file_read_range(const char *path, const AdmitParams &want, uint64_t first, uint64_t n,
+                          std::vector<uint8_t> *counters);
 
 }  // namespace xf
 #endif  // XF_ADMIT_H_

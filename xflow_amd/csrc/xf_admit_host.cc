@@ -4,6 +4,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+
 #include "xf_admit.h"
 #include "xf_common.h"
 
@@ -55,14 +57,13 @@ int admit_file_write(const char *path, const AdmitParams &p, const uint8_t *coun
   return XF_OK;
 }
 
-int admit_file_read(const char *path, const AdmitParams &want, std::vector<uint8_t> *counters) {
-  XF_REQUIRE(path && counters, "xf_admit_load: null argument");
+// the header of `path`, checked against `want`; the file is left open behind the header
+static int admit_file_open(const char *path, const AdmitParams &want, File *in) {
   XF_TRY(admit_check_params("xf_admit_load", want.L, want.h, want.N));
-  File in;
-  in.f = fopen(path, "rb");
-  if (!in.f) return set_error(XF_EIO, "xf_admit_load: cannot open the admission file %s", path);
+  in->f = fopen(path, "rb");
+  if (!in->f) return set_error(XF_EIO, "xf_admit_load: cannot open the admission file %s", path);
   FileHeader hd;
-  if (fread(&hd, sizeof(hd), 1, in.f) != 1 || memcmp(hd.magic, kMagic, 8) != 0)
+  if (fread(&hd, sizeof(hd), 1, in->f) != 1 || memcmp(hd.magic, kMagic, 8) != 0)
     return set_error(XF_EIO, "xf_admit_load: %s is not an admission file", path);
   XF_REQUIRE(hd.L == (uint32_t)want.L && hd.h == (uint32_t)want.h && hd.N == (uint32_t)want.N &&
                  hd.seed == want.seed,
@@ -74,6 +75,14 @@ int admit_file_read(const char *path, const AdmitParams &want, std::vector<uint8
   if (hd.slots != slots)
     return set_error(XF_EIO, "xf_admit_load: %s names %llu counters, 2^%d = %llu expected", path,
                      (unsigned long long)hd.slots, want.L, (unsigned long long)slots);
+  return XF_OK;
+}
+
+int admit_file_read(const char *path, const AdmitParams &want, std::vector<uint8_t> *counters) {
+  XF_REQUIRE(path && counters, "xf_admit_load: null argument");
+  File in;
+  XF_TRY(admit_file_open(path, want, &in));
+  const uint64_t slots = 1ull << want.L;
   counters->resize((size_t)slots);
   if (fread(counters->data(), 1, (size_t)slots, in.f) != (size_t)slots)
     return set_error(XF_EIO, "xf_admit_load: %s ends before its %llu counters", path,
@@ -85,9 +94,46 @@ int admit_file_read(const char *path, const AdmitParams &want, std::vector<uint8
   return XF_OK;
 }
 
+int admit_file_read_range(const char *path, const AdmitParams &want, uint64_t first, uint64_t n,
+                          std::vector<uint8_t> *counters) {
+  XF_REQUIRE(path && counters, "xf_admit_load: null argument");
+  File in;
+  XF_TRY(admit_file_open(path, want, &in));
+  const uint64_t slots = 1ull << want.L;
+  XF_REQUIRE(first <= slots && n <= slots - first,
+             "xf_admit_load: the range [%llu, +%llu) lies outside the 2^%d counters",
+             (unsigned long long)first, (unsigned long long)n, want.L);
+  // (a file cut short is damaged for every rank, whichever range lost its counters)
+  if (fseeko(in.f, 0, SEEK_END) != 0 || (uint64_t)ftello(in.f) < sizeof(FileHeader) + slots)
+    return set_error(XF_EIO, "xf_admit_load: %s ends before its %llu counters", path,
+                     (unsigned long long)slots);
+  counters->resize((size_t)n);
+  if (fseeko(in.f, (off_t)(sizeof(FileHeader) + first), SEEK_SET) != 0 ||
+      fread(counters->data(), 1, (size_t)n, in.f) != (size_t)n)
+    return set_error(XF_EIO, "xf_admit_load: %s ends before its %llu counters", path,
+                     (unsigned long long)slots);
+  for (size_t i = 0; i < (size_t)n; ++i)
+    if ((*counters)[i] > (uint32_t)want.N)
+      return set_error(XF_EIO, "xf_admit_load: %s: counter %llu holds %u, above admit_count=%d",
+                       path, (unsigned long long)(first + i), (unsigned)(*counters)[i], want.N);
+  return XF_OK;
+}
+
 }  // namespace xf
 
 extern "C" uint64_t xf_admit_slot(uint64_t key, uint64_t seed, int L, int j) {
   if (L < 2 || L > 32 || j < 0) return 0;
   return xf::admit_slot(key, seed, L, j);
+}
+
+extern "C" int xf_admit_range(int log2_slots, int world, int rank, uint64_t *first, uint64_t *n) {
+  XF_REQUIRE(log2_slots >= 2 && log2_slots <= 32,
+             "xf_admit_range: admit_log2_slots must be in 2 .. 32, not %d", log2_slots);
+  XF_REQUIRE(world >= 1 && rank >= 0 && rank < world, "xf_admit_range: rank %d of world %d", rank,
+             world);
+  const uint64_t slots = 1ull << log2_slots, per = xf::admit_per(log2_slots, world);
+  const uint64_t lo = std::min(slots, (uint64_t)rank * per), hi = std::min(slots, lo + per);
+  if (first) *first = lo;
+  if (n) *n = hi - lo;
+  return XF_OK;
 }

@@ -28,7 +28,7 @@ int main(int argc, char *argv[]) {
                  "(also fgid and val, for field_aware and feature_values)\n"
               << "feature admission (a key enters the model once a counting Bloom filter has seen "
                  "it N times; one worker): append admit_count=N [admit_log2_slots=26 "
-                 "admit_hashes=3]\n";
+                 "admit_hashes=3]; several workers sharing one filter: admit_shared=1\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler
@@ -65,6 +65,13 @@ int main(int argc, char *argv[]) {
   if (rc != XF_OK) {
     std::cerr << "xflow_lr: error " << rc << ": " << xf_last_error() << "\n";
     return 1;
+  }
+  if (worker->admit_count && worker->admit_shared) {  // (the filter's stats stay per rank)
+    double seen = 0, kept = 0;
+    worker->get_metric("admit_seen", &seen);
+    worker->get_metric("admit_kept", &kept);
+    std::cout << "rank " << worker->rank << " admit_seen = " << (unsigned long long)seen
+              << " admit_kept = " << (unsigned long long)kept << std::endl;
   }
   double eps = 0;
   worker->get_metric("examples_per_sec", &eps);

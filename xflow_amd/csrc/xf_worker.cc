@@ -140,8 +140,9 @@ static int world_from_env(int world) {
 
 // Feature admission is a filter in front of ONE worker's key build on the GPU: each rank of a
 // group would count only its own shard of the data (and rank 0's predict would test keys other
-// ranks admitted), core_num > 1 slices a block after it was read, the host key build and the
-// reference-order forward take host arrays.  All refused by name, before any rendezvous.
+// ranks admitted) — unless the ranks share one filter (admit_shared=1: xf_admit_create_shared,
+// every apply collective); core_num > 1 slices a block after it was read, the host key build and
+// the reference-order forward take host arrays.  All refused by name, before any rendezvous.
 int Worker::check_admit() const {
   if (admit_count == 0) return XF_OK;
   XF_REQUIRE(admit_count >= 1 && admit_count <= 255,
@@ -152,8 +153,14 @@ int Worker::check_admit() const {
   XF_REQUIRE(admit_hashes >= 1 && admit_hashes <= 8,
              "XFStartTrain: admit_hashes must be in 1 .. 8, not %d", admit_hashes);
   const int w = sharded_ ? world : world_from_env(world);
-  XF_REQUIRE(w <= 1, "XFStartTrain: admit_count=%d runs on one worker only (world %d): every rank "
-             "would count its own shard of the data", admit_count, w);
+  XF_REQUIRE(w <= 1 || admit_shared, "XFStartTrain: admit_count=%d runs on one worker only "
+             "(world %d): every rank would count its own shard of the data (admit_shared=1 shares "
+             "one filter between the ranks)", admit_count, w);
+  // (the owner-compute schedules compile through a path of their own, compile_owner: admission
+  // inside that dataflow is not built)
+  XF_REQUIRE(w <= 1 || (schedule != XF_SCHEDULE_OWNER && schedule != XF_SCHEDULE_OWNER_STALE1),
+             "XFStartTrain: admit_count=%d admit_shared=1 together with schedule=owner / "
+             "owner_stale1 (world %d): use schedule=sequential or stale1", admit_count, w);
   XF_REQUIRE(core_num <= 1, "XFStartTrain: admit_count=%d needs core_num=1, not core_num=%d",
              admit_count, core_num);
   XF_REQUIRE(key_build_gpu, "XFStartTrain: admit_count=%d together with key_build=host: the "
@@ -166,6 +173,10 @@ int Worker::check_admit() const {
 int Worker::create_admit() {
   if (admit_count == 0 || admit_) return XF_OK;
   XF_TRY(check_admit());
+  // (admit_shared=1: one filter on the worker's group — COLLECTIVE; one worker has no group)
+  if (admit_shared)
+    return xf_admit_create_shared(&admit_, group_, admit_log2_slots, admit_hashes, admit_count,
+                                  seed);
   return xf_admit_create(&admit_, admit_log2_slots, admit_hashes, admit_count, seed);
 }
 
@@ -180,8 +191,13 @@ int Worker::compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep) {
 int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
                          const uint64_t *keys, const int32_t *fgid, const float *vals,
                          const int32_t *labels, size_t start, size_t end, int keep) {
-  if (admit_ && trainer == sharded_)  // (one worker, core_num 1: filtered, compiled from device arrays)
+  if (admit_ && trainer == sharded_) {  // (core_num 1: filtered, compiled from device arrays)
+    // (a rank without rows of its own — a shared filter — is in the collective apply all the same)
+    if (!rowptr)
+      return compile_admitted_dev(b, update, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
+                                  keep);
     return compile_admitted(b, update, rowptr, keys, fgid, vals, labels, start, end, keep);
+  }
   if (fm_mode == XF_FM_FIELD_AWARE)
     return xf_sharded_compile_fielded(trainer, b, rowptr, keys, fgid,
                                       feature_values ? vals : nullptr, labels, start, end, keep);
@@ -684,14 +700,15 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
           rc = xf_reader_parse_text(rd, buf, p->len, blocks_[0], &rows, &nnz, &rowptr, &keys,
                                     &fgid, &labels);
         if (rc == XF_OK && feature_values) rc = xf_block_values(blocks_[0], &vals);
-        // (under admission, with fields or with values — one worker — a block without rows is no
-        // minibatch: b stays null; a plain one is the empty minibatch)
-        if (rc == XF_OK && (rows || !(admit_ || ffm || feature_values)))
+        // (under admission, with fields or with values, on one worker a block without rows is no
+        // minibatch: b stays null; a plain one, and any of a group's turns, is the empty minibatch)
+        if (rc == XF_OK && (rows || world > 1 || !(admit_ || ffm || feature_values)))
           rc = compile_rows(sharded_, &b, 1, rowptr, keys, fgid, vals, labels, 0, rows, keep);
         ++blocks_host;
       }
     } else {  // a rank without rows of its own still takes part in the (collective) step
-      rc = compile_no_rows(sharded_, &b, keep);
+      // (... and, with a shared admission filter, in the collective apply in front of it)
+      rc = compile_rows(sharded_, &b, 1, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, keep);
     }
     const double tc1 = now_s();
     if (rc == XF_OK && b) rc = xf_sharded_step(sharded_, b);
@@ -994,6 +1011,11 @@ int Worker::set_param(const char *name, const char *value) {
   } else if (n == "admit_log2_slots") {
     XF_REQUIRE(!admit_, "XFSetParam: admit_log2_slots cannot change once the filter exists");
     admit_log2_slots = atoi(value);
+  } else if (n == "admit_shared") {
+    XF_REQUIRE(!admit_, "XFSetParam: admit_shared cannot change once the filter exists");
+    XF_REQUIRE(!strcmp(value, "0") || !strcmp(value, "1"),
+               "XFSetParam: admit_shared must be 0 or 1, not %s", value);
+    admit_shared = atoi(value);
   } else if (n == "admit_hashes") {
     XF_REQUIRE(!admit_, "XFSetParam: admit_hashes cannot change once the filter exists");
     admit_hashes = atoi(value);

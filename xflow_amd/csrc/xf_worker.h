@@ -79,6 +79,11 @@ class Worker {
   int admit_count = 0;
   int admit_log2_slots = 26;  // 2^26 8-bit counters: 64 MiB
   int admit_hashes = 3;
+  // admit_shared = 1: the ranks of a group share ONE filter (xf_admit_create_shared: the counters
+  // sharded by slot range, every apply collective), which lifts "one worker"; every turn of the
+  // training loop and of predict then applies on every rank — the empty minibatch where a rank has
+  // no rows.  Not with the owner-compute schedules.  0: as before.
+  int admit_shared = 0;
 
  private:
   int create_tables();
