@@ -874,6 +874,68 @@ int xf_admit_save(xf_admit *a, const char *path);
 int xf_admit_load(xf_admit *a, const char *path);
 int xf_admit_stats(const xf_admit *a, uint64_t *nonzeros_seen, uint64_t *nonzeros_kept);
 
+/* ---------------------------------------------------------------- negative subsampling */
+/* Subsampling of the negatives with importance weights (not in the reference; the FTRL paper's
+ * "Subsampling Training Data"): every positive row is kept, a negative row with probability
+ * `keep`, and a kept negative's loss — hence its gradient — is multiplied by w = 1 / keep, so the
+ * expected gradient is unchanged.  Like admission it filters a minibatch's CSR arrays ahead of any
+ * key build, but it drops whole rows and keeps no state.
+ * Sampling.  keep: a float in (0, 1]; seed; a 64-bit stream id per apply; a 64-bit ordinal per row.
+ *   T = (uint64) floor((double)keep * 2^32)
+ *   h(ordinal) = mix64(mix64(seed ^ stream) + ordinal), mix64 as for admission (64-bit wrapping)
+ *   a row is kept iff label != 0 or (h >> 32) < T
+ * and on nothing else: not the keys, the block boundaries, the ingest path or the launch shape.
+ * xf_negsample_keep is that decision for a negative row as host code (0 or 1; 0 for a keep
+ * outside (0, 1]), from the one definition the kernels use.
+ * One apply = one minibatch: row i of the input has ordinal first_ordinal + i; kept rows keep their
+ * order; rowptr (u32, row-relative), labels, keys and fgid / vals (may be NULL) are compacted
+ * together.  R = 0 is valid, NNZ = 0 with R > 0 is valid, rows without nonzeros are kept or
+ * dropped like any other row.  keep = 1 returns the inputs byte for byte.
+ * xf_negsample_apply_dev: device arrays (d_rowptr R + 1 offsets, d_labels R).  The outputs are
+ * device arrays owned by the sampler, valid until its next apply (NULL for fgid / vals that were
+ * not given), written in the order of `stream`; *R_out / *NNZ_out: kept rows and their nonzeros.
+ * One wait for the stream, for those two counts (none with R = 0).
+ * xf_negsample_apply: the reader's host arrays and a row slice: uploads the slice (rowptr rebased
+ * to u32) and runs the same kernels — one implementation, the device one.
+ * xf_negsample_stats, summed over the applies: rows seen, rows kept, negatives seen, negatives
+ * kept.  The sampler allocates on the device only in its first apply.
+ * Weight.  xf_negsample_weight: w = fp32(1) / fp32(keep), one fp32 division on the host.  A trainer
+ * takes w >= 1 through xf_workspace_neg_weight / xf_sharded_set_neg_weight (default 1).  In every
+ * training step (xf_lr_step — cells, local, valued, local valued — and xf_lr_update_dev after its
+ * LAST forward segment; xf_fm_step in the reference form with and without table-resident records,
+ * canonical and field-aware, with and without values; xf_sharded_step on XF_SCHEDULE_SEQUENTIAL and
+ * XF_SCHEDULE_STALE1), after the forward has written the rows' losses and before anything reads
+ * them:  loss[r] = labels[r] != 0 ? loss[r] : fp32(w * loss[r])  — one fp32 multiply, contraction
+ * off.  Everything downstream is as before: the gradient, 1 / R with R the rows of the minibatch as
+ * compiled (the kept rows), the optimizer step; xf_workspace_fetch returns the weighted loss.
+ * Predict never weights.  With w == 1 no kernel is launched: the step is launch for launch what it
+ * was.  XF_EINVAL: w < 1 or not finite; xf_sharded_set_neg_weight with w != 1 on a several-rank
+ * trainer on XF_SCHEDULE_OWNER / _OWNER_STALE1 (the loss is formed inside the owners' finalize
+ * kernels), and xf_sharded_set_schedule to one of those two while w != 1. */
+typedef struct xf_negsample xf_negsample;
+int xf_negsample_create(xf_negsample **out, float keep, uint64_t seed);
+int xf_negsample_destroy(xf_negsample *s);
+int xf_negsample_params(const xf_negsample *s, float *keep, uint64_t *seed);
+int xf_negsample_weight(const xf_negsample *s, float *weight);
+int xf_negsample_keep(uint64_t seed, uint64_t stream, uint64_t ordinal, float keep);
+int xf_negsample_apply_dev(xf_negsample *s, uint64_t stream_id, uint64_t first_ordinal,
+                           const uint64_t *d_keys, const int32_t *d_fgid, const float *d_vals,
+                           const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
+                           uint32_t NNZ, void *stream, const uint64_t **d_keys_out,
+                           const int32_t **d_fgid_out, const float **d_vals_out,
+                           const uint32_t **d_rowptr_out, const int32_t **d_labels_out,
+                           uint32_t *R_out, uint32_t *NNZ_out);
+int xf_negsample_apply(xf_negsample *s, uint64_t stream_id, uint64_t first_ordinal,
+                       const uint64_t *rowptr, const uint64_t *keys, const int32_t *fgid,
+                       const float *vals, const int32_t *labels, size_t row_begin, size_t row_end,
+                       void *stream, const uint64_t **d_keys_out, const int32_t **d_fgid_out,
+                       const float **d_vals_out, const uint32_t **d_rowptr_out,
+                       const int32_t **d_labels_out, uint32_t *R_out, uint32_t *NNZ_out);
+int xf_negsample_stats(const xf_negsample *s, uint64_t *rows_seen, uint64_t *rows_kept,
+                       uint64_t *neg_seen, uint64_t *neg_kept);
+int xf_workspace_neg_weight(xf_workspace *ws, float weight);
+int xf_sharded_set_neg_weight(xf_sharded *st, float weight);
+
 /* ---------------------------------------------------------------- metrics             */
 /* Base::calculate_auc (base.h:84-110): reference-format logloss (mean of y*log2 p +
  * (1-y)*log2(1-p), negative), AUC by descending-pctr rank sum, plus the conventional
@@ -917,7 +979,15 @@ int XFDestroy(void **h);
  *        model, XFLoadModel needs it.  XFGetMetric: admit_seen admit_kept (nonzeros)
  *        admit_shared(0|1: the workers of a group share one filter, xf_admit_create_shared, which
  *        lifts "one worker" — every turn of the training loop and of predict applies collectively,
- *        the empty minibatch where a rank has no rows; not with schedule=owner / owner_stale1) */
+ *        the empty minibatch where a rank has no rows; not with schedule=owner / owner_stale1)
+ *        neg_keep(r in (0, 1], default 1 = off: negative subsampling, xf_negsample_* — every
+ *        TRAINING block is sampled before admission and its key build: a row with label 0 is kept
+ *        iff xf_negsample_keep(seed, (epoch << 32) | rank, the row's index in this rank's training
+ *        file in this epoch, r), every other row always; the trainer weights a kept negative's loss
+ *        by 1 / r (xf_sharded_set_neg_weight); test blocks are never sampled; core_num 1,
+ *        key_build=gpu, parity=exact, not with schedule=owner / owner_stale1 on several workers;
+ *        nothing is saved with the model).  XFGetMetric: neg_seen neg_kept (negative rows)
+ *        rows_kept; rows_trained counts kept rows */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

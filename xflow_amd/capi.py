@@ -270,6 +270,23 @@ SIGNATURES = {
     "xf_admit_save": (C.c_int, [vp, C.c_char_p]),
     "xf_admit_load": (C.c_int, [vp, C.c_char_p]),
     "xf_admit_stats": (C.c_int, [vp, u64p, u64p]),
+    "xf_negsample_create": (C.c_int, [C.POINTER(vp), C.c_float, C.c_uint64]),
+    "xf_negsample_destroy": (C.c_int, [vp]),
+    "xf_negsample_params": (C.c_int, [vp, C.POINTER(C.c_float), u64p]),
+    "xf_negsample_weight": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "xf_negsample_keep": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_float]),
+    "xf_negsample_apply_dev": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp,
+                                         C.c_uint32, C.c_uint32, vp, C.POINTER(vp),
+                                         C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                         C.POINTER(vp), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint32)]),
+    "xf_negsample_apply": (C.c_int, [vp, C.c_uint64, C.c_uint64, u64p, u64p, i32p, f32p, i32p,
+                                     C.c_size_t, C.c_size_t, vp, C.POINTER(vp), C.POINTER(vp),
+                                     C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "xf_negsample_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "xf_workspace_neg_weight": (C.c_int, [vp, C.c_float]),
+    "xf_sharded_set_neg_weight": (C.c_int, [vp, C.c_float]),
     "XFCreate": (C.c_int, [C.POINTER(vp), C.c_char_p, C.c_char_p]),
     "XFStartTrain": (C.c_int, [C.POINTER(vp)]),
     "XFDestroy": (C.c_int, [C.POINTER(vp)]),
@@ -695,6 +712,103 @@ class Admit:
         return seen.value, kept.value
 
 
+def negsample_keep(seed, stream, ordinal, keep):
+    """whether a NEGATIVE row of this ordinal is kept (xf_negsample_keep; host code, the kernels'
+    own definition)"""
+    return bool(lib().xf_negsample_keep(int(seed), int(stream), int(ordinal), float(keep)))
+
+
+class NegSample:
+    """Negative subsampling (xf_negsample_*): apply() keeps every positive row of a minibatch and
+    a negative row with probability `keep`, decided by a hash of (seed, stream, the row's ordinal);
+    weight is what a trainer multiplies a kept negative's loss by (Workspace.neg_weight,
+    Sharded.set_neg_weight).  Stateless but for the statistics."""
+
+    def __init__(self, keep, seed=0):
+        self.h = vp()
+        self.keep, self.seed = float(np.float32(keep)), seed
+        check(lib().xf_negsample_create(C.byref(self.h), keep, seed))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().xf_negsample_destroy(self.h)
+            self.h = None
+
+    @property
+    def weight(self):
+        w = C.c_float()
+        check(lib().xf_negsample_weight(self.h, C.byref(w)))
+        return np.float32(w.value)
+
+    def params(self):
+        keep, seed = C.c_float(), C.c_uint64()
+        check(lib().xf_negsample_params(self.h, C.byref(keep), C.byref(seed)))
+        return keep.value, seed.value
+
+    def apply_dev(self, stream_id, first_ordinal, rowptr, keys, labels, fgid=None, values=None,
+                  stream=None):
+        """host arrays in (uploaded as they are), the sampled minibatch as an AdmitDev out (device
+        pointers owned by the sampler, valid until its next apply)"""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert len(rowptr) >= 1 and int(rowptr[-1]) - int(rowptr[0]) <= len(keys)
+        R = len(rowptr) - 1
+        args = []
+        for a, dt, pt in ((fgid, np.int32, i32p), (values, np.float32, f32p)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=dt)
+                assert len(a) == len(keys), "one entry per key"
+                a = a if len(a) else np.zeros(1, dt)
+            args.append((a, pt))
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        assert len(labels) == R, "one label per row"
+        labels = labels if R else np.zeros(1, np.int32)
+        if len(keys) == 0:
+            keys = np.zeros(1, np.uint64)
+        ptr = [(_p(a, pt) if a is not None else None) for a, pt in args]
+        dk, dfg, dv, dr, dl = vp(), vp(), vp(), vp(), vp()
+        Ro, No = C.c_uint32(), C.c_uint32()
+        check(lib().xf_negsample_apply(self.h, int(stream_id), int(first_ordinal),
+                                       _p(rowptr, u64p), _p(keys, u64p), ptr[0], ptr[1],
+                                       _p(labels, i32p), 0, R, stream, C.byref(dk), C.byref(dfg),
+                                       C.byref(dv), C.byref(dr), C.byref(dl), C.byref(Ro),
+                                       C.byref(No)))
+        return AdmitDev(dk.value, dr.value, dl.value, Ro.value, No.value, dfg.value, dv.value)
+
+    def sample_dev(self, stream_id, first_ordinal, d_keys, d_rowptr, d_labels, R, NNZ,
+                   d_fgid=None, d_vals=None, stream=None):
+        """xf_negsample_apply_dev: device pointers in (ints), the sampled minibatch as an AdmitDev"""
+        dk, dfg, dv, dr, dl = vp(), vp(), vp(), vp(), vp()
+        Ro, No = C.c_uint32(), C.c_uint32()
+        check(lib().xf_negsample_apply_dev(self.h, int(stream_id), int(first_ordinal), d_keys,
+                                           d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, stream,
+                                           C.byref(dk), C.byref(dfg), C.byref(dv), C.byref(dr),
+                                           C.byref(dl), C.byref(Ro), C.byref(No)))
+        return AdmitDev(dk.value, dr.value, dl.value, Ro.value, No.value, dfg.value, dv.value)
+
+    def apply(self, stream_id, first_ordinal, rowptr, keys, labels, fgid=None, values=None):
+        """the sampled host arrays (downloaded): (rowptr uint32, keys, labels) and then, for each
+        of fgid / values that was given, its sampled array in that order"""
+        d = self.apply_dev(stream_id, first_ordinal, rowptr, keys, labels, fgid, values)
+        check(lib().xf_stream_sync(None))
+        out = [(np.zeros(d.R + 1, np.uint32), d.d_rowptr), (np.zeros(d.NNZ, np.uint64), d.d_keys),
+               (np.zeros(d.R, np.int32), d.d_labels)]
+        if fgid is not None:
+            out.append((np.zeros(d.NNZ, np.int32), d.d_fgid))
+        if values is not None:
+            out.append((np.zeros(d.NNZ, np.float32), d.d_vals))
+        for a, ptr in out:
+            if a.nbytes:
+                check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
+        return tuple(a for a, _ in out)
+
+    def stats(self):
+        """(rows seen, rows kept, negatives seen, negatives kept), summed over the applies"""
+        v = [C.c_uint64() for _ in range(4)]
+        check(lib().xf_negsample_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
 class Batch:
     """A compiled minibatch (host arrays; device mirror after upload())."""
 
@@ -1080,6 +1194,11 @@ class Workspace:
         """the number of fields of 'field_aware' (1 .. 64): before fm_mode('field_aware')"""
         check(lib().xf_workspace_fm_fields(self.h, int(fields)))
 
+    def neg_weight(self, weight):
+        """the weight of a kept negative (negative subsampling, NegSample.weight): every training
+        step multiplies the losses of its label-0 rows by it; 1 (default): nothing is launched"""
+        check(lib().xf_workspace_neg_weight(self.h, float(weight)))
+
     def fetch(self, U, R):
         wu = np.empty(U, np.float32)
         loss = np.empty(R, np.float32)
@@ -1282,6 +1401,11 @@ class Sharded:
         """'reference', 'canonical' or 'field_aware': before the first step (the tables empty);
         several ranks: schedules 'sequential' and 'stale1' only"""
         check(lib().xf_sharded_set_fm_mode(self.h, FM_MODES[mode]))
+
+    def set_neg_weight(self, weight):
+        """the weight of a kept negative (Workspace.neg_weight); several ranks: schedules
+        'sequential' and 'stale1' only"""
+        check(lib().xf_sharded_set_neg_weight(self.h, float(weight)))
 
     def close(self):
         if getattr(self, "h", None):

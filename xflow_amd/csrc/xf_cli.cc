@@ -28,7 +28,9 @@ int main(int argc, char *argv[]) {
                  "(also fgid and val, for field_aware and feature_values)\n"
               << "feature admission (a key enters the model once a counting Bloom filter has seen "
                  "it N times; one worker): append admit_count=N [admit_log2_slots=26 "
-                 "admit_hashes=3]; several workers sharing one filter: admit_shared=1\n";
+                 "admit_hashes=3]; several workers sharing one filter: admit_shared=1\n"
+              << "negative subsampling (every positive row kept, a negative with probability r, "
+                 "a kept negative's loss weighted by 1 / r): append neg_keep=r\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler
@@ -72,6 +74,15 @@ int main(int argc, char *argv[]) {
     worker->get_metric("admit_kept", &kept);
     std::cout << "rank " << worker->rank << " admit_seen = " << (unsigned long long)seen
               << " admit_kept = " << (unsigned long long)kept << std::endl;
+  }
+  if (worker->neg_keep < 1.0f) {  // (every rank samples its own rows)
+    double seen = 0, kept = 0, rows = 0;
+    worker->get_metric("neg_seen", &seen);
+    worker->get_metric("neg_kept", &kept);
+    worker->get_metric("rows_kept", &rows);
+    std::cout << "rank " << worker->rank << " neg_seen = " << (unsigned long long)seen
+              << " neg_kept = " << (unsigned long long)kept << " rows_kept = "
+              << (unsigned long long)rows << std::endl;
   }
   double eps = 0;
   worker->get_metric("examples_per_sec", &eps);

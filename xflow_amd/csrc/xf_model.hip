@@ -23,6 +23,8 @@
 // then rounded to fp32 where the reference holds an fp32 value.
 #include <hip/hip_runtime.h>
 
+#include <math.h>
+
 #include <algorithm>
 
 #include "xf_batch.h"
@@ -31,6 +33,7 @@
 #include "xf_device.h"
 #include "xf_ffm.h"
 #include "xf_fm_canonical.h"
+#include "xf_negsample.h"
 #include "xf_scratch.h"
 #include "xf_wave.h"
 
@@ -1597,6 +1600,9 @@ struct xf_workspace {
   double *fmc_hpart = nullptr; // canonical FM: the heavy keys' chunk sums
   size_t capHpart = 0;
   uint32_t lastU = 0, lastR = 0;
+  // negative subsampling: a training step multiplies the losses of its label-0 rows by this,
+  // between forward and gradient (xf::weigh_negatives: no launch at 1)
+  float neg_weight = 1.0f;
   // optional per-kernel HIP-event timing (same stream, inside the caller's timed region)
   bool profiling = false;
   // A ring of event sets: a step records into the oldest set, whose own step finished long
@@ -1829,6 +1835,15 @@ static int fm_forward_reforder(xf_batch *b, int k, const float *wu, const float 
   return XF_OK;
 }
 
+extern "C" int xf_workspace_neg_weight(xf_workspace *ws, float weight) {
+  XF_REQUIRE(ws, "xf_workspace_neg_weight: null workspace");
+  XF_REQUIRE(isfinite(weight) && weight >= 1.0f,
+             "xf_workspace_neg_weight: the weight of a kept negative is 1 / neg_keep >= 1 and "
+             "finite, not %g", (double)weight);
+  ws->neg_weight = weight;
+  return XF_OK;
+}
+
 extern "C" int xf_workspace_capture(xf_workspace *ws, int enable) {
   XF_REQUIRE(ws, "xf_workspace_capture: null workspace");
   XF_REQUIRE(!enable || ws->fm_mode != XF_FM_FIELD_AWARE,
@@ -1889,6 +1904,7 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
                                   S(stream), ws->capPartial == had ? c->next : nullptr));
     }
   }
+  XF_TRY(xf::weigh_negatives(ws->loss, labels, b->R, ws->neg_weight, S(stream)));
   XF_END(kEvForward);
   if (cap) XF_TRY(xf::gather_f32(T.w, b->d_rows_u, b->U, ws->wu, S(stream)));
   if (ws->parity == XF_PARITY_REFERENCE_ORDER) {
@@ -2204,6 +2220,7 @@ static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
   XF_END(kEvGather);
   XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr,
                          b->valued ? b->d_xval : nullptr, S(stream)));
+  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {
     xf::table_note_write(w);
@@ -2314,6 +2331,7 @@ static int fm_field_aware_step(xf_table *w, xf_table *vt, xf_batch *b, xf_worksp
   XF_END(kEvGather);
   XF_TRY(xf::ffm_forward(&v, k, F, ws->wu, ws->fmc_vu, b->d_xfg, ws->loss, nullptr,
                          b->valued ? b->d_xval : nullptr, S(stream)));
+  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {
     xf::table_note_write(w);
@@ -2378,6 +2396,7 @@ static int lr_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stre
   }
   XF_END(kEvResolve);
   XF_TRY(xf::val_lr_forward(&v, b->d_xval, ws->wu, ws->loss, nullptr, S(stream)));  // :172
+  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {  // :173, :175
     xf::table_note_write(w);
@@ -2418,6 +2437,7 @@ static int lr_local_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void
   XF_BEGIN();
   XF_TRY(xf::cells_lr_forward_valued(c, xf::table_dev(w).w, b->raw_labels, ws->partial, ws->loss,
                                      nullptr, S(stream)));  // :172
+  XF_TRY(xf::weigh_negatives(ws->loss, b->raw_labels, b->R, ws->neg_weight, S(stream)));
   XF_END(kEvForward);
   XF_TRY(xf::cells_lr_grad_update_valued(c, w, ws->loss, S(stream)));  // :173, :175
   XF_END(kEvGrad);
@@ -2486,6 +2506,7 @@ extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *
                        dim3(kBlock), 0, S(stream), v.rowptr, b->d_fm_ridx, (const FmKey *)rec,
                        v.labels, v.R, ws->loss, (float *)nullptr, ws->vsum);  // :237
     XF_HIP(hipGetLastError());
+    XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
     XF_END(kEvForward);
     XF_TRY(fm_grad_update(w, vt, &v, rows_w, rows_v, ws->wu, ws->vu, ws->vsum, ws->loss, ws->g,
                           ws->gv, false, stream, rec));
@@ -2529,6 +2550,7 @@ extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *
     else
       XF_TRY(xf_fm_forward_dev(&v, k, ws->wu, ws->vu, ws->loss, nullptr, ws->vsum, stream));
   }
+  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
   XF_END(kEvForward);
   if (ws->parity == XF_PARITY_REFERENCE_ORDER && v.U) {
     // the reference's own fp32 running sums per key and factor, then the two Pushes

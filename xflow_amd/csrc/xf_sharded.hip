@@ -33,7 +33,7 @@
 // (xf_lr_step / xf_fm_step) on a locally compiled minibatch.
 #include <hip/hip_runtime.h>
 
-
+#include <math.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
@@ -51,6 +51,7 @@
 #include "xf_device.h"
 #include "xf_ffm.h"
 #include "xf_fm_canonical.h"
+#include "xf_negsample.h"
 #include "xf_scratch.h"
 
 namespace xf {
@@ -230,6 +231,7 @@ struct xf_sharded {
   int parity_mode = XF_PARITY_EXACT_SUMS;  // (what xf_sharded_set_parity last set)
   int fm_mode = XF_FM_REFERENCE;           // (what xf_sharded_set_fm_mode last set)
   int fm_fields = 0;                       // (what xf_sharded_set_fm_fields last set)
+  float neg_weight = 1.0f;                 // (what xf_sharded_set_neg_weight last set)
   uint64_t seen_upper = 0;     // world 1: host-side upper bound on the keys in the table
   Dev<double> partial;         // LR forward scratch
   // the owner-compute compile's staging: the worker's nonzeros grouped by owner (sent from
@@ -408,6 +410,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
   if (!fm && hb->valued) {
     // valued LR: the w half of the canonical step (xf_valued.hip), no cells
     XF_TRY(xf::val_lr_forward(&v, hb->d_xval, B.wu.p, B.loss.p, d_pctr, s));
+    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -418,6 +421,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     XF_TRY(B.S.reserve((size_t)b->R * k));
     XF_TRY(xf::fmc_forward(&v, k, B.wu.p, B.vu.p, B.S.p, B.loss.p, d_pctr,
                            hb->valued ? hb->d_xval : nullptr, s));
+    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -430,6 +434,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     const int F = st->fm_fields, kf = k / F;  // (k: the v rows' width, fields x kf)
     XF_TRY(xf::ffm_forward(&v, kf, F, B.wu.p, B.vu.p, hb->d_xfg, B.loss.p, d_pctr,
                            hb->valued ? hb->d_xval : nullptr, s));
+    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -443,6 +448,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     XF_TRY(st->partial.reserve(xf::cells_partial_doubles(b->cells)));
     XF_TRY(xf::cells_lr_forward(b->cells, B.wu.p, b->b->view.labels, st->partial.p, B.loss.p,
                                 d_pctr, s));
+    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -456,6 +462,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     } else {
       XF_TRY(xf_fm_forward_dev(&b->b->view, k, B.wu.p, B.vu.p, B.loss.p, d_pctr, B.vsum.p, s));
     }
+    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -2013,6 +2020,10 @@ extern "C" int xf_sharded_set_schedule(xf_sharded *st, int schedule) {
   XF_REQUIRE(st->cfg.model == 0 || schedule != XF_SCHEDULE_OWNER_STALE1 ||
                  st->cfg.update_rule == XF_UPDATE_RANK_ORDERED,
              "xf_sharded_set_schedule: owner_stale1 for FM needs update_rule rank_ordered");
+  XF_REQUIRE(!owner_dataflow(schedule) || st->fused || st->neg_weight == 1.0f,
+             "xf_sharded_set_schedule: schedule %s with a weight on the negatives "
+             "(xf_sharded_set_neg_weight %g): the owners' finalize kernels form the loss unweighted",
+             schedule_name(schedule), (double)st->neg_weight);
   XF_TRY(xf_sharded_flush(st));
   st->cfg.schedule = schedule;
   return XF_OK;
@@ -2029,6 +2040,22 @@ extern "C" int xf_sharded_set_parity(xf_sharded *st, int mode) {
   // list: the reference-order step refuses those; minibatches compiled from here on are built
   // for the mode set)
   st->parity_mode = mode;
+  return XF_OK;
+}
+
+// the weight of a kept negative (negative subsampling): the fused step reads it from its workspace,
+// the exchange path's front_compute from the trainer
+extern "C" int xf_sharded_set_neg_weight(xf_sharded *st, float weight) {
+  XF_REQUIRE(st, "xf_sharded_set_neg_weight: null trainer");
+  XF_REQUIRE(isfinite(weight) && weight >= 1.0f,
+             "xf_sharded_set_neg_weight: the weight of a kept negative is 1 / neg_keep >= 1 and "
+             "finite, not %g", (double)weight);
+  XF_REQUIRE(weight == 1.0f || st->fused || !owner_dataflow(st->cfg.schedule),
+             "xf_sharded_set_neg_weight: a weight on the negatives (%g) on schedule %s: the owners' "
+             "finalize kernels form the loss unweighted (use schedule sequential or stale1)",
+             (double)weight, schedule_name(st->cfg.schedule));
+  if (st->fused) XF_TRY(xf_workspace_neg_weight(st->ws, weight));
+  st->neg_weight = weight;
   return XF_OK;
 }
 

@@ -52,6 +52,7 @@ Worker::~Worker() {
     if (g) xf_ingest_destroy(g);
   for (xf_sbatch *b : cache_) xf_sbatch_free(b);
   if (admit_) xf_admit_destroy(admit_);
+  if (sample_) xf_negsample_destroy(sample_);
   if (sharded_) xf_sharded_destroy(sharded_);  // owns the tables
   if (group_) xf_group_destroy(group_);
 }
@@ -70,7 +71,10 @@ static const char *env_first(std::initializer_list<const char *> names) {
 // environment, as scripts/local.sh sets it) this process joins the group — one process per
 // GPU — and its tables are one key-range shard of the parameter table.
 int Worker::create_tables() {
-  if (sharded_) return create_admit();
+  if (sharded_) {
+    XF_TRY(create_admit());
+    return create_negsample();
+  }
   int w = world;
   if (w <= 0) {
     const char *v = env_first({"WORLD_SIZE", "XF_WORLD", "DMLC_NUM_WORKER"});
@@ -122,6 +126,10 @@ int Worker::create_tables() {
     const bool ffm = fm_mode == XF_FM_FIELD_AWARE;
     int rc = ffm ? xf_sharded_set_fm_fields(warm, fields) : XF_OK;
     if (rc == XF_OK && fm_mode != XF_FM_REFERENCE) rc = xf_sharded_set_fm_mode(warm, fm_mode);
+    // (neg_keep < 1: the weight kernel's first launch belongs here too — after the parameter's
+    // own check, so that a bad value is refused by its name)
+    if (rc == XF_OK) rc = check_negsample();
+    if (rc == XF_OK && neg_keep < 1.0f) rc = xf_sharded_set_neg_weight(warm, 1.0f / neg_keep);
     if (rc == XF_OK) rc = compile_rows(warm, &b, 0, rp, keys, fg, vals, lab, 0, 2, 1);
     if (rc == XF_OK) rc = xf_sharded_step(warm, b);
     if (rc == XF_OK) rc = xf_sharded_predict(warm, b, p);
@@ -129,7 +137,8 @@ int Worker::create_tables() {
     xf_sharded_destroy(warm);
     XF_TRY(rc);
   }
-  return create_admit();
+  XF_TRY(create_admit());
+  return create_negsample();
 }
 
 static int world_from_env(int world) {
@@ -180,6 +189,93 @@ int Worker::create_admit() {
   return xf_admit_create(&admit_, admit_log2_slots, admit_hashes, admit_count, seed);
 }
 
+// Negative subsampling drops rows of a training block on the GPU ahead of the key build: core_num
+// > 1 slices a block after it was read, the host key build and the reference-order forward take
+// host arrays, and on several workers the owner-compute schedules form the loss inside the owners'
+// finalize kernels, where no weight is applied.  All refused by name, before any rendezvous.
+int Worker::check_negsample() const {
+  XF_REQUIRE(neg_keep > 0.0f && neg_keep <= 1.0f,
+             "XFStartTrain: neg_keep must be in (0, 1] (the share of the negatives that is kept), "
+             "not %g", (double)neg_keep);
+  if (neg_keep == 1.0f) return XF_OK;
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: neg_keep=%g needs core_num=1, not core_num=%d",
+             (double)neg_keep, core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: neg_keep=%g together with key_build=host: the sampled "
+             "minibatch is born on the GPU (use key_build=gpu)", (double)neg_keep);
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: neg_keep=%g together with "
+             "parity=reference_order: that mode builds its keys on the host", (double)neg_keep);
+  const int w = sharded_ ? world : world_from_env(world);
+  XF_REQUIRE(w <= 1 || (schedule != XF_SCHEDULE_OWNER && schedule != XF_SCHEDULE_OWNER_STALE1),
+             "XFStartTrain: neg_keep=%g together with schedule=owner / owner_stale1 (world %d): the "
+             "owners form the loss unweighted (use schedule=sequential or stale1)",
+             (double)neg_keep, w);
+  return XF_OK;
+}
+
+int Worker::create_negsample() {
+  if (neg_keep == 1.0f || sample_) return XF_OK;
+  XF_TRY(check_negsample());
+  XF_TRY(xf_negsample_create(&sample_, neg_keep, seed));
+  float weight = 1.0f;
+  XF_TRY(xf_negsample_weight(sample_, &weight));
+  XF_TRY(xf_sharded_set_neg_weight(sharded_, weight));
+  // the sampler's first launches, on two rows of a private sampler: start-up work like the two-row
+  // update of create_tables (the worker's own sampler keeps its statistics clean)
+  xf_negsample *warm = nullptr;
+  XF_TRY(xf_negsample_create(&warm, neg_keep, seed));
+  static const uint64_t rp[3] = {0, 2, 4}, keys[4] = {11, 12, 12, 13};
+  static const int32_t lab[2] = {0, 1};
+  void *stream = nullptr;
+  int rc = xf_sharded_stream(sharded_, &stream);
+  const uint64_t *fk = nullptr;
+  const uint32_t *fr = nullptr;
+  const int32_t *fl = nullptr;
+  uint32_t R = 0, NNZ = 0;
+  if (rc == XF_OK)
+    rc = xf_negsample_apply(warm, 0, 0, rp, keys, nullptr, nullptr, lab, 0, 2, stream, &fk,
+                            nullptr, nullptr, &fr, &fl, &R, &NNZ);
+  if (rc == XF_OK) rc = xf_stream_sync(stream);
+  xf_negsample_destroy(warm);
+  return rc;
+}
+
+int Worker::sample_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
+                       const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
+                       uint32_t *R, uint32_t *NNZ) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  return xf_negsample_apply_dev(sample_, sample_stream_, ordinal_ + first_row, *d_keys,
+                                fm_mode == XF_FM_FIELD_AWARE ? *d_fgid : nullptr,
+                                feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
+                                stream, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ);
+}
+
+int Worker::compile_sampled_dev(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
+                                const float *d_vals, const uint32_t *d_rowptr,
+                                const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
+  *b = nullptr;
+  if (R == 0 && world <= 1) return XF_OK;  // (every row dropped: a block without rows)
+  if (admit_) return compile_admitted_dev(b, 1, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
+  return compile_dev_arrays(b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
+}
+
+int Worker::compile_sampled(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                            const int32_t *fgid, const float *vals, const int32_t *labels,
+                            size_t start, size_t end, int keep) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const uint64_t *fk = nullptr;
+  const int32_t *ff = nullptr, *fl = nullptr;
+  const float *fv = nullptr;
+  const uint32_t *fr = nullptr;
+  uint32_t R = 0, NNZ = 0;
+  XF_TRY(xf_negsample_apply(sample_, sample_stream_, ordinal_ + start, rowptr, keys,
+                            fm_mode == XF_FM_FIELD_AWARE ? fgid : nullptr,
+                            feature_values ? vals : nullptr, labels, start, end, stream, &fk, &ff,
+                            &fv, &fr, &fl, &R, &NNZ));
+  return compile_sampled_dev(b, fk, ff, fv, fr, fl, R, NNZ, keep);
+}
+
 // a rank without rows of its own still takes part in the (collective) step: the empty minibatch
 int Worker::compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep) {
   static const uint64_t kNoRows[1] = {0};
@@ -191,6 +287,9 @@ int Worker::compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep) {
 int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
                          const uint64_t *keys, const int32_t *fgid, const float *vals,
                          const int32_t *labels, size_t start, size_t end, int keep) {
+  // (training blocks only — predict passes update 0 — and only rows of this rank's own)
+  if (sample_ && update && trainer == sharded_ && rowptr && end > start)
+    return compile_sampled(b, rowptr, keys, fgid, vals, labels, start, end, keep);
   if (admit_ && trainer == sharded_) {  // (core_num 1: filtered, compiled from device arrays)
     // (a rank without rows of its own — a shared filter — is in the collective apply all the same)
     if (!rowptr)
@@ -386,6 +485,9 @@ int Worker::batch_training() {
       // device arrays — unless this rank's shard file cannot be mapped (empty, not a regular
       // file): the host reader below yields zero rows for such a file and the rank still joins
       // every collective with empty minibatches
+      // (negative subsampling: this epoch's stream of decisions, the file's rows numbered from 0)
+      ordinal_ = 0;
+      sample_stream_ = (uint64_t)epoch << 32 | (uint32_t)rank;
       bool took = false;
       if (gpu_ingest_applies()) XF_TRY(text_epoch(epoch, keep, &took));
       if (took) {
@@ -490,19 +592,23 @@ int Worker::batch_training() {
                             keep);
           if (rc != XF_OK) break;
           const double tc1 = now_s();
-          rc = xf_sharded_step(sharded_, b);
+          // (b == nullptr: negative subsampling dropped every row of the block — no minibatch)
+          if (b) rc = xf_sharded_step(sharded_, b);
           if (rc == XF_OK) rc = xf_sharded_check(sharded_);
           t_compile += tc1 - tc0;
           t_step += now_s() - tc1;
           if (rc != XF_OK) {
-            xf_sbatch_free(b);
+            if (b) xf_sbatch_free(b);
             break;
           }
-          rows_trained_ += (long)(end - start);
-          if (keep) cache_.push_back(b);
-          else
+          uint32_t kept_rows = 0;  // (under negative subsampling: the kept rows)
+          if (b) xf_sbatch_dims(b, &kept_rows, nullptr, nullptr, nullptr);
+          rows_trained_ += sample_ ? (long)kept_rows : (long)(end - start);
+          if (keep && b) cache_.push_back(b);
+          else if (b)
             xf_sbatch_free(b);
         }
+        ordinal_ += rows;
         // (the table's maintenance step inside an epoch: local to the shard, but its flush is
         // collective — one worker only)
         if (rc == XF_OK && world <= 1 && model_ == 0) rc = defrag_if_grown(30);
@@ -682,11 +788,14 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
         const int32_t *dfg = nullptr;
         const float *dv = nullptr;
         rc = xf_ingest_fields(ingest_[k], &dfg, &dv);
-        if (rc == XF_OK && admit_)
+        rows = R;
+        if (rc == XF_OK && sample_) {
+          rc = sample_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ);
+          if (rc == XF_OK) rc = compile_sampled_dev(&b, dk, dfg, dv, drp, dl, R, NNZ, keep);
+        } else if (rc == XF_OK && admit_)
           rc = compile_admitted_dev(&b, 1, dk, dfg, dv, drp, dl, R, NNZ, keep);
         else if (rc == XF_OK)
           rc = compile_dev_arrays(&b, dk, dfg, dv, drp, dl, R, NNZ, keep);
-        rows = R;
         on_gpu = true;
         ++blocks_gpu;
       } else if (rc == XF_OK) {  // not of the common shape: the host parser's
@@ -717,7 +826,10 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
       if (b) xf_sbatch_free(b);
       break;
     }
-    rows_trained_ += (long)rows;
+    uint32_t kept_rows = 0;  // (under negative subsampling: the kept rows)
+    if (b) xf_sbatch_dims(b, &kept_rows, nullptr, nullptr, nullptr);
+    rows_trained_ += sample_ ? (long)kept_rows : (long)rows;
+    ordinal_ += rows;
     if (keep && b) cache_.push_back(b);
     else if (b)
       xf_sbatch_free(b);
@@ -877,6 +989,7 @@ int Worker::train() {
                "tokeniser carries no values (use ingest=gpu_fields)");
   }
   XF_TRY(check_admit());  // before any rendezvous of a group
+  XF_TRY(check_negsample());
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
   std::cout << "my rank is = " << rank << std::endl;
@@ -1005,6 +1118,9 @@ int Worker::set_param(const char *name, const char *value) {
     else
       return xf::set_error(XF_EINVAL, "XFSetParam: feature_values must be on or off, not '%s'",
                            value);
+  } else if (n == "neg_keep") {
+    XF_REQUIRE(!sample_, "XFSetParam: neg_keep cannot change once the sampler exists");
+    neg_keep = strtof(value, nullptr);
   } else if (n == "admit_count") {
     XF_REQUIRE(!admit_, "XFSetParam: admit_count cannot change once the filter exists");
     admit_count = atoi(value);
@@ -1041,7 +1157,11 @@ int Worker::get_metric(const char *name, double *value) {
   else if (n == "rows_trained") *value = (double)rows_trained_;
   else if (n == "blocks_gpu") *value = (double)blocks_gpu;
   else if (n == "blocks_host") *value = (double)blocks_host;
-  else if (n == "admit_seen" || n == "admit_kept") {
+  else if (n == "neg_seen" || n == "neg_kept" || n == "rows_kept") {
+    uint64_t rows_kept = 0, seen = 0, kept = 0;
+    if (sample_) XF_TRY(xf_negsample_stats(sample_, nullptr, &rows_kept, &seen, &kept));
+    *value = (double)(n == "neg_seen" ? seen : n == "neg_kept" ? kept : rows_kept);
+  } else if (n == "admit_seen" || n == "admit_kept") {
     uint64_t seen = 0, kept = 0;
     if (admit_) XF_TRY(xf_admit_stats(admit_, &seen, &kept));
     *value = (double)(n == "admit_seen" ? seen : kept);

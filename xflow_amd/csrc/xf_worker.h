@@ -84,6 +84,14 @@ class Worker {
   // training loop and of predict then applies on every rank — the empty minibatch where a rank has
   // no rows.  Not with the owner-compute schedules.  0: as before.
   int admit_shared = 0;
+  // Negative subsampling (xf_negsample.hip): neg_keep = r < 1: every TRAINING block is sampled
+  // first — every positive row kept, a negative row with probability r, decided by a hash of (seed,
+  // (epoch << 32) | rank, the row's index in this rank's training file in this epoch) — then goes
+  // through admission, when on, and into the matching _dev compile; the trainer multiplies a kept
+  // negative's loss by 1 / r.  1 = off, nothing is created.  core_num 1, key_build=gpu,
+  // parity=exact, not with the owner-compute schedules on several workers (checked where training
+  // starts).  Stateless: nothing travels with the model.  Test blocks are never sampled.
+  float neg_keep = 1.0f;
 
  private:
   int create_tables();
@@ -92,6 +100,25 @@ class Worker {
   xf_admit *admit_ = nullptr;  // admit_count >= 1: the filter, created with the tables
   int check_admit() const;     // the refusals of admit_count >= 1, before any rendezvous
   int create_admit();
+  xf_negsample *sample_ = nullptr;  // neg_keep < 1: the sampler, created with the tables
+  uint64_t ordinal_ = 0;            // rows of this rank's training file read so far in this epoch
+  uint64_t sample_stream_ = 0;      // (epoch << 32) | rank of the running epoch
+  int check_negsample() const;      // the refusals of neg_keep, before any rendezvous
+  int create_negsample();
+  // sample a training block (device arrays, replaced in place by the sampler's; fgid / vals only
+  // in the modes that read them), rows numbered from ordinal_ + first_row
+  int sample_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
+                 const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
+                 uint32_t *R, uint32_t *NNZ);
+  // ... or rows [start, end) of host arrays; then admission, when on, and the _dev compile.  A
+  // block whose rows are all dropped is a block without rows: on one worker no minibatch
+  // (*b = nullptr), in a group the empty minibatch
+  int compile_sampled(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                      const int32_t *fgid, const float *vals, const int32_t *labels,
+                      size_t start, size_t end, int keep);
+  int compile_sampled_dev(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
+                          const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
+                          uint32_t R, uint32_t NNZ, int keep);
   // filter a block (host arrays and a row slice / device arrays), then the matching _dev compile
   int compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr, const uint64_t *keys,
                        const int32_t *fgid, const float *vals, const int32_t *labels,
