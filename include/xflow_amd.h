@@ -909,7 +909,10 @@ int xf_admit_stats(const xf_admit *a, uint64_t *nonzeros_seen, uint64_t *nonzero
  * off.  Everything downstream is as before: the gradient, 1 / R with R the rows of the minibatch as
  * compiled (the kept rows), the optimizer step; xf_workspace_fetch returns the weighted loss.
  * Predict never weights.  With w == 1 no kernel is launched: the step is launch for launch what it
- * was.  XF_EINVAL: w < 1 or not finite; xf_sharded_set_neg_weight with w != 1 on a several-rank
+ * was.  With w != 1 the LR steps on cells (xf_lr_step on a cells, local or local valued minibatch,
+ * xf_lr_update_dev) store the weighted loss from the kernel that forms the loss; every other step
+ * launches one small kernel for it (xf_weigh_negatives_launches counts those).
+ * XF_EINVAL: w < 1 or not finite; xf_sharded_set_neg_weight with w != 1 on a several-rank
  * trainer on XF_SCHEDULE_OWNER / _OWNER_STALE1 (the loss is formed inside the owners' finalize
  * kernels), and xf_sharded_set_schedule to one of those two while w != 1. */
 typedef struct xf_negsample xf_negsample;
@@ -934,6 +937,16 @@ int xf_negsample_apply(xf_negsample *s, uint64_t stream_id, uint64_t first_ordin
 int xf_negsample_stats(const xf_negsample *s, uint64_t *rows_seen, uint64_t *rows_kept,
                        uint64_t *neg_seen, uint64_t *neg_kept);
 int xf_workspace_neg_weight(xf_workspace *ws, float weight);
+/* launches of the separate weight kernel since the library was loaded: the LR steps on cells form
+ * the weighted loss in the kernel that forms the loss and make none */
+uint64_t xf_weigh_negatives_launches(void);
+/* the kernel that forms the LR cells steps' losses, on partial row sums the caller holds (device
+ * arrays): d_partial[(v * G + g) * W + i] is workgroup g's share of row v * W + i; loss[r] =
+ * sigmoid(fp32(sum over g)) - label, weighted as above, pctr[r] the sigmoid (either may be NULL).
+ * The forward makes G a multiple of 8; this entry takes any R, W, G (the tests' way in). */
+int xf_cells_finalize_rows(const double *d_partial, const int32_t *d_labels, uint32_t R, uint32_t W,
+                           uint32_t G, float neg_weight, float *d_loss, float *d_pctr,
+                           void *stream);
 int xf_sharded_set_neg_weight(xf_sharded *st, float weight);
 
 /* ---------------------------------------------------------------- metrics             */

@@ -286,6 +286,9 @@ SIGNATURES = {
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "xf_negsample_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
     "xf_workspace_neg_weight": (C.c_int, [vp, C.c_float]),
+    "xf_weigh_negatives_launches": (C.c_uint64, []),
+    "xf_cells_finalize_rows": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                         vp, vp, vp]),
     "xf_sharded_set_neg_weight": (C.c_int, [vp, C.c_float]),
     "XFCreate": (C.c_int, [C.POINTER(vp), C.c_char_p, C.c_char_p]),
     "XFStartTrain": (C.c_int, [C.POINTER(vp)]),

@@ -228,7 +228,7 @@ void blob_pool_limit(int blobs) {
 }  // namespace xf
 
 namespace xf {
-static int g_path[kPathCount] = {0, 0, 0, 0, 0};
+static int g_path[kPathCount] = {0, 0, 0, 0, 0, 0};
 int path_switch(int which) { return g_path[which]; }
 void set_path_switch(int which, int v) { g_path[which] = v; }
 #ifdef XF_EXPERIMENTS
@@ -287,6 +287,8 @@ extern "C" int xf_tune(const char *name, double value) {
     xf::set_path_switch(xf::kPathOldWeight, (int)value);
   else if (!strcmp(name, "lr_gradient") && value >= 0 && value <= 3)
     xf::set_path_switch(xf::kPathLrGradient, (int)value);
+  else if (!strcmp(name, "entry_streams") && (value == 0 || value == 1))
+    xf::set_path_switch(xf::kPathEntryStreams, (int)value);
   else if (!strcmp(name, "owner_pass") && value >= 0 && value <= 4)
     xf::set_path_switch(xf::kPathOwnerPass, (int)value);
   else if (!strcmp(name, "valued_lr") && (value == 0 || value == 1 || value == 2))

@@ -153,9 +153,15 @@ size_t cells_partial_doubles(const xf_cells *c);
 // forward: loss[r] = sigmoid(sum_j w[idx_j]) - label[r]   (lr_worker.cc:121-143)
 // resume_from: a later segment of c's chain — d_partial still holds the partial row sums a call
 // over the segments before it left there: only the rest is run (and the rows finalized again)
+// grad_follows: the caller runs the gradient pass over c next, on the same stream — the launch
+// that forms the losses also fetches the gradient's entries (k_lr_finalize_cells; xf_common.h:
+// entry_streams).  A caller whose last step ran over the same cells passes false: the entries are
+// where that step left them.  neg_weight: the weight of a kept negative in d_loss
+// (xf_negsample.h: loss[r] = label != 0 ? loss : fp32(neg_weight * loss)); d_pctr is never weighted.
 int cells_lr_forward(const xf_cells *c, const float *d_w, const int32_t *d_labels,
                      double *d_partial, float *d_loss, float *d_pctr, hipStream_t stream,
-                     const xf_cells *resume_from = nullptr);
+                     const xf_cells *resume_from = nullptr, bool grad_follows = false,
+                     float neg_weight = 1.0f);
 
 // feature values on cells (xf_cells_valued.hip; c->vals != null, one segment):
 //   wx_r = fp32(sum_j fp32(w[row_j] x_j))      gw = fp32(fp32(sum_occ fp32(loss_r x_occ)) / R)
@@ -166,7 +172,8 @@ int cells_sort_valued(const uint32_t *cid, uint32_t *cid_s, const uint32_t *ent,
                       const float *xval, uint32_t n, int bits, uint32_t *entries, float *vals,
                       hipStream_t stream);
 int cells_lr_forward_valued(const xf_cells *c, const float *d_w, const int32_t *d_labels,
-                            double *d_partial, float *d_loss, float *d_pctr, hipStream_t stream);
+                            double *d_partial, float *d_loss, float *d_pctr, hipStream_t stream,
+                            float neg_weight = 1.0f /* as cells_lr_forward's */);
 int cells_lr_grad_update_valued(const xf_cells *c, const xf_table *t, const float *d_loss,
                                 hipStream_t stream);
 

@@ -40,9 +40,10 @@ __device__ __forceinline__ void fwd_load(FwdBlock &B, const uint32_t *__restrict
 }  // namespace
 
 namespace xf {
-// loss / pctr of every row from the window workgroups' partial sums (k_lr_finalize_cells)
+// loss / pctr of every row from the window workgroups' partial sums (k_lr_finalize_cells);
+// neg_weight: as cells_lr_forward's
 int cells_lr_finalize(const xf_cells *c, const double *d_partial, const int32_t *d_labels,
-                      float *d_loss, float *d_pctr, hipStream_t s);
+                      float *d_loss, float *d_pctr, hipStream_t s, float neg_weight = 1.0f);
 }  // namespace xf
 
 #endif  // XF_CELLS_FWD_H_

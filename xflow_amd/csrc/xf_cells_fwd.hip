@@ -105,11 +105,46 @@ k_lr_fwd_cells(const uint32_t *__restrict__ entries, const uint32_t *__restrict_
 // per row, lane q adding the workgroups g = q mod 4; combined as (s0 + s1) + (s2 + s3): a
 // fixed association, the same bits every run.  (Sixteen lanes per row, every lane's loads in
 // flight at once, were tried: forward + finalize 38.3 -> 41.4 us — a wavefront then reads four
-// rows of sixteen partial arrays, 32 bytes of every line it touches.)
+// rows of sixteen partial arrays, 32 bytes of every line it touches.  Ten or all twenty of a
+// lane's loads in flight instead of four: 9.87 -> 9.73 / 9.64 us in the trace, less than the
+// kernel differs between two boxes — not kept, profiles/entry_streams/.)
+// neg_w: the weight of a kept negative (xf_negsample.h) in the last store — loss[r] = label != 0 ?
+// loss : fp32(neg_w * loss), k_weigh_negatives' expression; pctr is never weighted.
+//
+// Blocks [nfin, gridDim.x) are FETCH blocks (cells_lr_forward: a gradient pass follows and the
+// forward did not read `entries`): block nfin + i reads the 16-byte words [i * kFetchVec,
+// (i + 1) * kFetchVec) of fetch[0 .. nvec) — the gradient's entry stream — once and drops them.
+// This kernel waits for its own 33 MB out of the last-level cache and leaves HBM idle; the
+// gradient kernel, whose entry load sits in the middle of a chain of dependent loads, then finds
+// the lines there instead of in HBM.  The fetch blocks come after the kernel's own in
+// the grid, so those are placed first.
+constexpr uint32_t kFetchVec = 4 * kBlock;  // 16-byte words per fetch block: 4096 entries
+// (an entry's row-in-window is below kWinMax: row bits 13 and 14 set with bit 0 clear is no
+// entry and no hole (all ones) — the test a fetch block's store hangs on)
+static_assert(kWinMax <= 0x6000u, "the fetch blocks' impossible entry");
+
 __global__ void __launch_bounds__(kBlock)
 k_lr_finalize_cells(const double *__restrict__ partial, const int32_t *__restrict__ labels,
                     uint32_t R, uint32_t W, uint32_t G, float *__restrict__ loss,
-                    float *__restrict__ pctr) {
+                    float *__restrict__ pctr, float neg_w, uint32_t nfin,
+                    const uint4 *__restrict__ fetch, uint32_t nvec) {
+  if (blockIdx.x >= nfin) {
+    const uint32_t j0 = (blockIdx.x - nfin) * kFetchVec + threadIdx.x;
+    // (no branch around a load: the four would wait for one another; past the end a lane reads
+    // the stream's last word again — nvec > 0 where there is a fetch block)
+    uint4 u[kFetchVec / kBlock];
+#pragma unroll
+    for (int i = 0; i < (int)(kFetchVec / kBlock); ++i) u[i] = fetch[min(j0 + i * kBlock, nvec - 1)];
+    uint32_t bad = 0;
+#pragma unroll
+    for (int i = 0; i < (int)(kFetchVec / kBlock); ++i)
+      bad |= (u[i].x >> 24 & u[i].x >> 25 & ~(u[i].x >> 11)) |
+             (u[i].y >> 24 & u[i].y >> 25 & ~(u[i].y >> 11)) |
+             (u[i].z >> 24 & u[i].z >> 25 & ~(u[i].z >> 11)) |
+             (u[i].w >> 24 & u[i].w >> 25 & ~(u[i].w >> 11));
+    if ((bad & 1u) && loss) loss[0] = 0.0f;  // (keeps the loads alive: no stream holds such an entry)
+    return;
+  }
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t r = t >> 2, q = t & 3u;
   double a = 0.0;
@@ -133,7 +168,33 @@ k_lr_finalize_cells(const double *__restrict__ partial, const int32_t *__restric
   if (r >= R || q != 0) return;
   const float pr = xf::sigmoid_ref((float)a);  // lr_worker.cc:141, base.h:54-63
   if (pctr) pctr[r] = pr;
-  if (loss) loss[r] = pr - (float)labels[r];
+  if (loss) {
+    const int32_t y = labels[r];
+    const float l = pr - (float)y;
+    loss[r] = y != 0 ? l : neg_w * l;
+  }
+}
+
+// the finalize launch; fetch_c != null: with the fetch blocks for fetch_c->entries behind it
+int launch_finalize(const xf_cells *c, const double *d_partial, const int32_t *d_labels,
+                    float *d_loss, float *d_pctr, float neg_w, const xf_cells *fetch_c,
+                    hipStream_t s) {
+  const uint32_t nfin = (uint32_t)(((size_t)c->R * 4 + kBlock - 1) / kBlock);
+  const uint4 *fetch = nullptr;
+  uint32_t nvec = 0;
+  if (fetch_c && fetch_c->NNZ) {  // the 16-byte words that lie inside entries[0 .. NNZ)
+    const uintptr_t a = (uintptr_t)fetch_c->entries;
+    const uint32_t head = (uint32_t)(((16 - (a & 15)) & 15) >> 2);
+    if (fetch_c->NNZ > head) {
+      fetch = (const uint4 *)(fetch_c->entries + head);
+      nvec = (fetch_c->NNZ - head) >> 2;
+    }
+  }
+  const uint32_t nfetch = (nvec + kFetchVec - 1) / kFetchVec;
+  hipLaunchKernelGGL(k_lr_finalize_cells, dim3(nfin + nfetch), dim3(kBlock), 0, s, d_partial,
+                     d_labels, c->R, c->W, c->G, d_loss, d_pctr, neg_w, nfin, fetch, nvec);
+  XF_HIP(hipGetLastError());
+  return XF_OK;
 }
 }  // namespace
 
@@ -141,7 +202,7 @@ namespace xf {
 
 int cells_lr_forward(const xf_cells *c, const float *d_w, const int32_t *d_labels,
                      double *d_partial, float *d_loss, float *d_pctr, hipStream_t s,
-                     const xf_cells *resume_from) {
+                     const xf_cells *resume_from, bool grad_follows, float neg_weight) {
   XF_REQUIRE(c && d_w && d_partial && (d_loss || d_pctr), "cells_lr_forward: null argument");
   if (c->R == 0) return XF_OK;
   int acc = 0;
@@ -154,21 +215,19 @@ int cells_lr_forward(const xf_cells *c, const float *d_w, const int32_t *d_label
     hipLaunchKernelGGL(k_lr_fwd_cells, dim3(q->nwin * q->G), dim3(kFwdBlock), 0, s, q->fwd_entries(),
                        q->cellptr, q->blk_cell, q->nchunk, q->W, q->G,
                        d_w + (size_t)q->chunk0 * kChunk, d_partial, acc);
-  hipLaunchKernelGGL(k_lr_finalize_cells,
-                     dim3((unsigned)(((size_t)c->R * 4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                     d_partial, d_labels, c->R, c->W, c->G, d_loss, d_pctr);
-  XF_HIP(hipGetLastError());
-  return XF_OK;
+  // The gradient's entries fetched under the finalize: the FIRST segment's, when the forward
+  // read its key-sorted copy (a forward over `entries` itself has just brought them in).  Later
+  // segments of a chain hold the keys that arrived after the table was settled: few, and their
+  // entries have just been written.  (entry_streams = 1, xf_common.h: the finalize launch alone.)
+  const bool fetch = grad_follows && !resume_from && path_switch(kPathEntryStreams) == 0 &&
+                     c->entries_k_ready && c->entries_k != c->entries;
+  return launch_finalize(c, d_partial, d_labels, d_loss, d_pctr, neg_weight, fetch ? c : nullptr, s);
 }
 
 // the rows' losses from the partial sums a forward kernel of another file left (xf_cells_valued.hip)
 int cells_lr_finalize(const xf_cells *c, const double *d_partial, const int32_t *d_labels,
-                      float *d_loss, float *d_pctr, hipStream_t s) {
-  hipLaunchKernelGGL(k_lr_finalize_cells,
-                     dim3((unsigned)(((size_t)c->R * 4 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                     d_partial, d_labels, c->R, c->W, c->G, d_loss, d_pctr);
-  XF_HIP(hipGetLastError());
-  return XF_OK;
+                      float *d_loss, float *d_pctr, hipStream_t s, float neg_weight) {
+  return launch_finalize(c, d_partial, d_labels, d_loss, d_pctr, neg_weight, nullptr, s);
 }
 
 // forward up to the row sums: d_rowsum[window * W + row-in-window] = sum of the row's weights
@@ -215,3 +274,20 @@ int cells_lr_forward_sums(const xf_cells *c, const float *d_w, double *d_partial
 }
 
 }  // namespace xf
+
+// k_lr_finalize_cells on partial sums the caller holds: d_partial[(v * G + g) * W + row-in-window],
+// v = r / W, device arrays.  For the tests: the forward only ever makes G a multiple of 8, the
+// kernel takes any.
+extern "C" int xf_cells_finalize_rows(const double *d_partial, const int32_t *d_labels, uint32_t R,
+                                      uint32_t W, uint32_t G, float neg_weight, float *d_loss,
+                                      float *d_pctr, void *stream) {
+  XF_REQUIRE(d_partial && d_labels && (d_loss || d_pctr) && W && G,
+             "xf_cells_finalize_rows: null argument");
+  if (R == 0) return XF_OK;
+  xf_cells c;
+  c.R = R;
+  c.W = W;
+  c.G = G;
+  return launch_finalize(&c, d_partial, d_labels, d_loss, d_pctr, neg_weight, nullptr,
+                         (hipStream_t)stream);
+}

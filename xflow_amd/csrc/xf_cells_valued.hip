@@ -344,7 +344,8 @@ int cells_sort_valued(const uint32_t *cid, uint32_t *cid_s, const uint32_t *ent,
 }
 
 int cells_lr_forward_valued(const xf_cells *c, const float *d_w, const int32_t *d_labels,
-                            double *d_partial, float *d_loss, float *d_pctr, hipStream_t s) {
+                            double *d_partial, float *d_loss, float *d_pctr, hipStream_t s,
+                            float neg_weight) {
   XF_REQUIRE(c && d_w && d_partial && (d_loss || d_pctr),
              "cells_lr_forward_valued: null argument");
   XF_REQUIRE(!c->next && c->chunk0 == 0 && c->entries_k == c->entries && (c->vals || c->NNZ == 0),
@@ -354,7 +355,7 @@ int cells_lr_forward_valued(const xf_cells *c, const float *d_w, const int32_t *
   hipLaunchKernelGGL(k_lr_fwd_cells_valued, dim3(c->nwin * c->G), dim3(kFwdBlock), 0, s, c->entries,
                      c->vals, c->cellptr, c->blk_cell, c->nchunk, c->W, c->G, d_w, d_partial);
   XF_HIP(hipGetLastError());
-  return cells_lr_finalize(c, d_partial, d_labels, d_loss, d_pctr, s);
+  return cells_lr_finalize(c, d_partial, d_labels, d_loss, d_pctr, s, neg_weight);
 }
 
 int cells_lr_grad_update_valued(const xf_cells *c, const xf_table *t, const float *d_loss,

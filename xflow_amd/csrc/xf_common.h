@@ -30,6 +30,9 @@ void scratch_poison();
 //                2 they derive it from (n, z) wherever the table vouches for it
 //   lr_gradient  0 by shape; 1 the general kernel also where the dense one applies; 2 / 3 the
 //                dense kernel with byte-masked / whole-line stores whatever the touch density
+//   entry_streams  where the gradient + Push of a kept minibatch finds its entries (xf_cells_fwd.hip,
+//                DESIGN 3): 0 fetched by extra blocks of the finalize launch; 1 the finalize launch
+//                alone, the entries from wherever they are (HBM, when many minibatches are cycled)
 //   owner_pass   an owner's gradient + Pushes for several workers: 0 by shape; 1 the general
 //                loop (a sweep per worker); 2 the workers' phases merged (k_lr_grad_ranked);
 //                3 the same with 32-bit worker masks; 4 a phase per worker (k_lr_grad_multi)
@@ -38,7 +41,7 @@ void scratch_poison();
 //                tile kernels (xf_valued.hip); 2 the local build + the valued cell kernels
 //                (xf_cells_valued.hip)
 enum PathSwitch { kPathKeyBuild = 0, kPathOldWeight, kPathLrGradient, kPathOwnerPass,
-                  kPathValuedLr, kPathCount };
+                  kPathValuedLr, kPathEntryStreams, kPathCount };
 int path_switch(int which);
 void set_path_switch(int which, int v);
 inline int key_build_mode() { return path_switch(kPathKeyBuild); }

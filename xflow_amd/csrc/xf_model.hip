@@ -1600,9 +1600,13 @@ struct xf_workspace {
   double *fmc_hpart = nullptr; // canonical FM: the heavy keys' chunk sums
   size_t capHpart = 0;
   uint32_t lastU = 0, lastR = 0;
-  // negative subsampling: a training step multiplies the losses of its label-0 rows by this,
-  // between forward and gradient (xf::weigh_negatives: no launch at 1)
+  // negative subsampling: a training step multiplies the losses of its label-0 rows by this —
+  // the LR cells steps in the finalize kernel's last store (cells_lr_forward), every other step
+  // with a launch between forward and gradient (xf::weigh_negatives: no launch at 1)
   float neg_weight = 1.0f;
+  // the cells lr_step last ran over (compared, never dereferenced): a minibatch stepped twice in
+  // a row has its entries where the step before left them, and nothing is fetched for it
+  const xf_cells *last_cells = nullptr;
   // optional per-kernel HIP-event timing (same stream, inside the caller's timed region)
   bool profiling = false;
   // A ring of event sets: a step records into the oldest set, whose own step finished long
@@ -1887,10 +1891,16 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
   const xf::TableDev &T = xf::table_dev(w);
   const int32_t *labels = b->local ? b->raw_labels : b->view.labels;
   XF_BEGIN();
-  if (ws->parity == XF_PARITY_REFERENCE_ORDER)
+  // (the weight of a kept negative rides in the finalize kernel's last store; the reference-order
+  // forward is another kernel and keeps the separate launch)
+  if (ws->parity == XF_PARITY_REFERENCE_ORDER) {
     XF_TRY(lr_forward_reforder(w, b, ws->loss, nullptr, S(stream)));
-  else
-    XF_TRY(xf::cells_lr_forward(c, T.w, labels, ws->partial, ws->loss, nullptr, S(stream)));  // :172
+    XF_TRY(xf::weigh_negatives(ws->loss, labels, b->R, ws->neg_weight, S(stream)));
+  } else {
+    XF_TRY(xf::cells_lr_forward(c, T.w, labels, ws->partial, ws->loss, nullptr, S(stream),
+                                nullptr, ws->last_cells != c, ws->neg_weight));  // :172
+  }
+  ws->last_cells = c;
   if (settle.d) {  // the build's wait, under the forward
     xf::KbDeferred *d = settle.d;
     settle.d = nullptr;
@@ -1901,10 +1911,10 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
       const size_t had = ws->capPartial;
       XF_TRY(ws_reserve_cells(ws, c, cap));
       XF_TRY(xf::cells_lr_forward(c, xf::table_dev(w).w, labels, ws->partial, ws->loss, nullptr,
-                                  S(stream), ws->capPartial == had ? c->next : nullptr));
+                                  S(stream), ws->capPartial == had ? c->next : nullptr, true,
+                                  ws->neg_weight));
     }
   }
-  XF_TRY(xf::weigh_negatives(ws->loss, labels, b->R, ws->neg_weight, S(stream)));
   XF_END(kEvForward);
   if (cap) XF_TRY(xf::gather_f32(T.w, b->d_rows_u, b->U, ws->wu, S(stream)));
   if (ws->parity == XF_PARITY_REFERENCE_ORDER) {
@@ -2436,8 +2446,7 @@ static int lr_local_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void
   ws->lastR = b->R;
   XF_BEGIN();
   XF_TRY(xf::cells_lr_forward_valued(c, xf::table_dev(w).w, b->raw_labels, ws->partial, ws->loss,
-                                     nullptr, S(stream)));  // :172
-  XF_TRY(xf::weigh_negatives(ws->loss, b->raw_labels, b->R, ws->neg_weight, S(stream)));
+                                     nullptr, S(stream), ws->neg_weight));  // :172
   XF_END(kEvForward);
   XF_TRY(xf::cells_lr_grad_update_valued(c, w, ws->loss, S(stream)));  // :173, :175
   XF_END(kEvGrad);

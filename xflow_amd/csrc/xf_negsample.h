@@ -31,6 +31,8 @@ XF_ADMIT_HD bool negsample_keep_row(uint64_t base, uint64_t ordinal, uint64_t T)
 namespace xf {
 // loss[r] = labels[r] != 0 ? loss[r] : fp32(w * loss[r]) over R rows on `s` (k_weigh_negatives);
 // w == 1 or R == 0: no launch.  Between a training step's forward and whatever reads its losses.
+// (The LR cells steps do not come here: k_lr_finalize_cells stores the weighted loss itself.
+// xf_weigh_negatives_launches counts the launches made, for the tests that hold them to that.)
 int weigh_negatives(float *loss, const int32_t *labels, uint32_t R, float w, hipStream_t s);
 }  // namespace xf
 #endif

@@ -31,6 +31,7 @@
 
 #include <math.h>
 
+#include <atomic>
 #include <vector>
 
 #include "xf_common.h"
@@ -226,12 +227,19 @@ int check_keep(const char *who, float keep) {
 
 }  // namespace
 
+static std::atomic<uint64_t> g_weigh_launches{0};
+
 int xf::weigh_negatives(float *loss, const int32_t *labels, uint32_t R, float w, hipStream_t s) {
   if (w == 1.0f || R == 0) return XF_OK;
   XF_REQUIRE(loss && labels, "weigh_negatives: null argument");
   hipLaunchKernelGGL(k_weigh_negatives, dim3((R + 255) / 256), dim3(256), 0, s, loss, labels, R, w);
   XF_HIP(hipGetLastError());
+  g_weigh_launches.fetch_add(1, std::memory_order_relaxed);
   return XF_OK;
+}
+
+extern "C" uint64_t xf_weigh_negatives_launches(void) {
+  return g_weigh_launches.load(std::memory_order_relaxed);
 }
 
 struct xf_negsample {
