@@ -468,6 +468,13 @@ int xf_table_import(xf_table *t, const uint64_t *keys, size_t n, const float *w,
  * GPU, a model file saved under the same hyper-parameters passes — or xf_table_set_hyper
  * changes alpha / beta / lambda1 / lambda2 with keys in the table.  Same table bits either way. */
 int xf_table_w_derived(xf_table *t, int *yes);
+/* *out = 1: the table has found its alpha an exact divisor — the double product with 1 / alpha,
+ * rounded to float, is x / alpha for every finite x — and its FTRL steps divide without the
+ * guard of the subnormal range (the verdict rides in the sign of the device's inv_alpha). */
+int xf_table_div_exact(xf_table *t, int *out);
+/* out[i] = the step's x[i] / d (the product with 1.0 / (double)d, with its guard of the subnormal
+ * range or, exact != 0, without it), computed on the GPU; host arrays of n floats.  For tests. */
+int xf_div_by_const_probe(const float *x, size_t n, float d, int exact, float *out);
 
 /* ---------------------------------------------------------------- model kernels       */
 /* All pointers are device pointers; asynchronous on `stream`. */

@@ -137,13 +137,17 @@ E2E_EPOCHS = 2
 
 
 def run_files(form, opt, fields, k, train_path, test_path, judge, valued=True,
-              block_bytes=2 << 20):
+              block_bytes=2 << 20, hyper=None):
     """XFlow(model=1, core_num=1) in the canonical ('fm') or the field-aware ('ffm') form: the
     key-0 init push, one update per block and epoch, then the test file block by block (a block's
     Pull inserts its unseen keys) -> the stores, (labels, pctr), the metrics.  The low candidates
     throughout: a caller that compares anything with these asserts judge.open_count() == 0
-    first, after which they are the only candidates."""
+    first, after which they are the only candidates.  hyper (tests/_hyper_cases.py: a Hyper):
+    both stores' hyper-parameters, the worker's one set for its tables."""
     ws, vs = stores(form, opt, fields, k, seed=0)           # the worker's seed: 0
+    if hyper is not None:
+        hyper.to_store(ws)
+        hyper.to_store(vs)
     ws.push(np.zeros(1, np.uint64), np.zeros(1, np.float32))
     vs.push(np.zeros(1, np.uint64), np.zeros(vs.dim, np.float32))
     run = G.Run(form, ws, vs, judge, fields)

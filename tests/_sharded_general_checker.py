@@ -41,6 +41,7 @@ import numpy as np
 
 from tests import _general_cases as GC
 from tests import _general_checker as G
+from tests import _hyper_cases as _HC
 from tests import _interval as I
 from tests import _sharded_modes_checker as M
 
@@ -242,7 +243,7 @@ class Run:
     shares from that one state and chains the pushes; adopt() sets the stores to given tables;
     predict(rank) gives the candidates of a rank's held-out minibatch."""
 
-    def __init__(self, spec, strs, judge, seed=GC.SEED):
+    def __init__(self, spec, strs, judge, seed=GC.SEED, hyper=None):
         mode, world, F, k, opt, schedule, case, valued = spec
         assert mode in M.MODES and schedule in ("sequential", "stale1") and len(strs) == world
         assert valued or mode != "lr", "binary LR is the reference's: the oracle's own update"
@@ -250,6 +251,9 @@ class Run:
         self.form, self.valued = FORM[mode], valued
         self.Fd = F if mode == "field_aware" else 0
         self.ws, self.vs = GC.stores(self.form, opt, self.Fd, k, seed)
+        if hyper is not None:       # (tests/_hyper_cases.py: a Hyper) one set for both tables
+            hyper.to_store(self.ws)
+            hyper.to_store(self.vs)
 
     def _run(self):
         return G.Run(self.form, self.ws, self.vs, self.judge, self.Fd)
@@ -282,10 +286,10 @@ class Run:
         return run._forward()[1]
 
 
-def run_cpu(spec, judge, empty_ranks=(), seed=None):
+def run_cpu(spec, judge, empty_ranks=(), seed=None, hyper=None):
     """the checker alone, following its low candidates -> Run, [Point], [pctr candidates per rank]"""
     strs = streams(spec, empty_ranks)
-    run = Run(spec, strs, judge, init_seed(spec) if seed is None else seed)
+    run = Run(spec, strs, judge, init_seed(spec) if seed is None else seed, hyper)
     pts = [run.point(st) for st in points(spec[5], len(strs[0][0]))]
     return run, pts, [run.predict(r) for r in range(spec[1])]
 
@@ -338,6 +342,15 @@ GENERAL = (("canonical", 1, 0, 80, "ftrl", "sequential", "ragged", True),
            ("field_aware", 1, 18, 4, "ftrl", "sequential", "zipf_chunks", True))
 # world 2, rank 1 without rows
 EMPTY_RANK = (("field_aware", 2, 18, 4, "ftrl", "sequential", "ragged", True),)
+
+# away from the default hyper-parameters (tests/_hyper_cases.py), one set for both tables
+HYPER = ((("field_aware", 2, 18, 4, "ftrl", "sequential", "ragged", True), _HC.SPARSE),
+         (("canonical", 3, 0, 16, "sgd", "stale1", "zipf_chunks", True), _HC.SGD_HI))
+
+
+def hyper_id(v):
+    return case_id(v) if isinstance(v, tuple) else repr(v)
+
 
 # The seed of the hash-normal init is GC.SEED = 7 for every case: it is the one
 # tests/test_gpu_sharded_modes.py's _trainer gives the GPU tables.  Where a case's open sums do not

@@ -5,16 +5,54 @@ the division itself only where the result is in or next to the subnormal range (
 div_by_const) — three instructions instead of an IEEE fp32 division's eleven in VALU-bound
 kernels.  This must be the SAME float for every x: checked here exhaustively, all 2^32 bit
 patterns of x, for the reference's default alpha, divisors with exact midpoints among their
-subnormal quotients (50000, the bench's row count: the guard's reason) and other row counts, on the host (IEEE double multiply
-and double -> float rounding are what the GPU's v_mul_f64 / v_cvt_f32_f64 do; the GPU side is
-covered by the bit-exact parity tests).  Without the guard the unguarded product differs for
-d = 50000 at 1308 values of x, all with subnormal quotients (exact rounding midpoints exist
-there: x = 25000 * 2^-149): checked too."""
+subnormal quotients (50000, the bench's row count: the guard's reason) and other row counts, on
+the host (IEEE double multiply and double -> float rounding are what the GPU's v_mul_f64 /
+v_cvt_f32_f64 do).  Without the guard the unguarded product differs for d = 50000 at 1308 values
+of x, all with subnormal quotients (exact rounding midpoints exist there: x = 25000 * 2^-149):
+checked too.
+
+The GPU side: the bit-exact parity tests run at alpha = 0.05 (and 0.1, 0.3, 0.01), which the
+table finds exact divisors, so they run the unguarded product only.  The function itself with its
+guard, at d = 50000 on the list inexact_list() makes here, and the table's verdict kernel, run on
+the device in tests/test_gpu_hyper.py."""
 import os
 import shutil
 import subprocess
 
+import numpy as np
 import pytest
+
+
+def inexact_list(d, chunk=1 << 24):
+    """the bit patterns (uint32) of every x with |x| < 2^-120 d at which the bare product
+    (float)((double)x * (1.0 / d)) is not the float x / d, the positive ones ascending, then their
+    negatives (the two operations are odd functions of x).  All x above the bound have quotients
+    of at least 2^-120, where the two agree for every d (xf_device.h: div_by_const)."""
+    d = np.float32(d)
+    inv = 1.0 / np.float64(d)
+    stop = int(np.float32(np.float32(2.0 ** -120) * d).view(np.uint32))
+    found = []
+    with np.errstate(under="ignore"):
+        for a in range(1, stop, chunk):
+            u = np.arange(a, min(a + chunk, stop), dtype=np.uint32)
+            x = u.view(np.float32)
+            bare = (x.astype(np.float64) * inv).astype(np.float32)
+            found.append(u[(x / d).view(np.uint32) != bare.view(np.uint32)])
+    pos = np.concatenate(found)
+    return np.concatenate([pos, pos | np.uint32(0x80000000)])
+
+
+def test_the_host_list_of_inexact_quotients_of_50000():
+    """the 1308 of the exhaustive run below, found again in seconds: 654 positive x, every one
+    with a subnormal quotient, 0x02432b61 among them"""
+    bad = inexact_list(50000.0)
+    assert len(bad) == 1308 and len(np.unique(bad)) == 1308
+    assert 0x02432B61 in bad[:654]
+    with np.errstate(under="ignore"):
+        q = np.abs(bad.view(np.float32) / np.float32(50000.0))
+    assert np.all(q < np.finfo(np.float32).tiny)
+    for d in (0.05, 0.1):
+        assert len(inexact_list(d)) == 0
 
 SRC = r"""
 #include <math.h>

@@ -10,6 +10,7 @@ import pytest
 
 from . import _general_cases as GC
 from . import _general_checker as G
+from . import _hyper_cases as HC
 from . import _interval as I
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -206,3 +207,68 @@ def test_golden_files_under_ftrl_have_no_open_sum(form, fields, k, valued):
     assert t["y2"][0] == 600 and t["wx"][0] == 600
     assert t["y2"][1] > 0, "every sum is proven: the exact audit would pass too"
     assert j.open_count() == 0, t
+
+
+# ------------------------------------------------- away from the default hyper-parameters
+@pytest.mark.parametrize("plan", HC.PLANS, ids=HC.ids(HC.PLANS))
+def test_hyper_streams_stay_under_the_cap(plan):
+    """every run of tests/test_gpu_hyper.py that goes through the interval checker, formed by the
+    oracle alone under the same hyper-parameters (per table, and changed in mid-run where the GPU
+    test changes them): the cap, and SPARSE's condition where a table runs under SPARSE to the
+    end — 20 to 80 % of the touched coordinates exactly 0 after the last step, and a coordinate
+    that was 0 after the first step is not later"""
+    j, track = I.Judge(), HC.Track()
+    HC.run_cpu(plan, j, track)
+    print(j.format(plan.id))
+    j.assert_cap()
+    if HC.sparse_table(plan) is not None:
+        HC.assert_sparse(track, plan.id)
+
+
+def test_sparse_condition_on_the_oracle_made_steps():
+    """the binary LR cells stream and the pooled FM stream (tests/test_gpu_hyper.py steps them
+    against O.lr_update / O.fm_update: exact sums, no cap to hold)"""
+    track = HC.Track()
+    HC.cells_oracle(HC.cells_raw(), [HC.SPARSE], track)
+    HC.assert_sparse(track, "binary LR cells")
+    track = HC.Track()
+    HC.pooled_oracle(HC.pooled_raw(), "ftrl", [HC.PAIR["ftrl"]], track)
+    HC.assert_sparse(track, "pooled FM, the factor table")
+
+
+@pytest.mark.parametrize("valued", [False, True], ids=["binary", "valued"])
+def test_golden_files_under_set_A_have_no_open_sum(valued):
+    """what the worker run under A of tests/test_gpu_ffm.py relies on"""
+    j = I.Judge()
+    GC.run_files("ffm", "ftrl", 18, 4, TRAIN, TEST, j, valued, hyper=HC.A)
+    print(j.format("golden files, ftrl A, %s" % ("valued" if valued else "binary")))
+    assert j.open_count() == 0, j.table()
+
+
+BITE = [HC.FM[0], HC.FM[1], HC.FFM[2], HC.FFM[3]]       # canonical k = 7 ragged, 39 x 7 valued
+
+
+def _swapped(phase):
+    return phase[1], phase[0]
+
+
+def _default_lr(phase):
+    return HC.SGD_DEFAULT, HC.SGD_DEFAULT
+
+
+def _l1_default(phase):
+    return tuple(h.but("NO_L1 with the default lambda1", lambda1=HC.DEFAULT[2])
+                 if h is HC.NO_L1 else h for h in phase)
+
+
+@pytest.mark.parametrize("plan,wrong", [(p, w) for p in BITE for w in (
+    (_swapped, _l1_default) if p.opt == "ftrl" else (_swapped, _default_lr))],
+    ids=lambda v: v.id if isinstance(v, HC.Plan) else v.__name__)
+def test_the_hyper_checks_bite(plan, wrong):
+    """three mistakes a kernel could make, each restated with a second checker that makes every
+    step from the right checker's state under the wrong sets: the two tables' sets swapped, the
+    default lr, and NO_L1's lambda1 = 0 taken for the default 5e-5.  Each leaves coordinates whose
+    state none of the right checker's candidates holds: the GPU test would fail there."""
+    _, bad = HC.run_cpu(plan, I.Judge(), wrong=wrong)
+    print("%s, %s: %d coordinates hold no candidate's state" % (plan.id, wrong.__name__, bad))
+    assert bad > 0

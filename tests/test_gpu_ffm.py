@@ -16,6 +16,7 @@ from xflow_amd.single import SingleGpuTrainer
 
 from . import _ffm_checker as F
 from . import _general_cases as GC
+from . import _hyper_cases as HC
 from . import _interval as I
 from . import _valued_cases as Cs
 
@@ -334,6 +335,46 @@ def test_worker_end_to_end(sample_prefixes, tmp_path, valued, opt):
     with pytest.raises(capi.XFError, match=r"fgid \d+.*fields = 17"):
         capi.XFlow(tr, te, model=1, fm_mode="field_aware", fields=17, epochs=1, k=k,
                    optimizer=opt, capacity=4096, pred_path=str(tmp_path / "t.txt")).train()
+
+
+@pytest.mark.parametrize("valued", [False, True], ids=["binary", "valued"])
+def test_worker_and_cli_under_other_ftrl_hyper_parameters(sample_prefixes, tmp_path, valued):
+    """XFlow(alpha=, beta=, lambda1=, lambda2=) and the CLI's alpha= beta= lambda1= lambda2=
+    options, set A of tests/_hyper_cases.py: the worker hands every value to both tables.  The
+    interval rule pins every sum on the golden files under A too (asserted here and in
+    tests/test_general_position_cpu.py), so tables, metrics and the pctr file are compared as
+    exactly as under the defaults"""
+    tr, te = sample_prefixes
+    Fd, k, h = F.E2E_FIELDS, F.E2E_K, HC.A
+    judge = I.Judge()
+    sw, sv, lab, p, (ll, auc, tp, fp) = GC.run_files("ffm", "ftrl", Fd, k, tr + "-00000",
+                                                     te + "-00000", judge, valued, hyper=h)
+    assert judge.open_count() == 0, judge.table()
+    dw, dv = GC.run_files("ffm", "ftrl", Fd, k, tr + "-00000", te + "-00000", I.Judge(), valued)[:2]
+    assert not np.array_equal(sw.export()[1], dw.export()[1])     # not the default's tables
+    assert not np.array_equal(sv.export()[1], dv.export()[1])
+    extra = {"feature_values": "on"} if valued else {}
+    pred = str(tmp_path / "p.txt")
+    x = capi.XFlow(tr, te, model=1, fm_mode="field_aware", fields=Fd, epochs=F.E2E_EPOCHS, k=k,
+                   optimizer="ftrl", capacity=4096, pred_path=pred, **extra, **h.kw())
+    x.train()
+    wh, vh = x.tables()
+    same_table(capi.Table.from_handle(wh, 1, capi.OPT_FTRL), sw)
+    same_table(capi.Table.from_handle(vh, Fd * k, capi.OPT_FTRL), sv)
+    assert (np.float32(x.metric("logloss_ref")), np.float32(x.metric("auc"))) == \
+        (np.float32(ll), np.float32(auc))
+    assert (x.metric("tp"), x.metric("fp")) == (tp, fp)
+    want = ["%g\t%d\t%d" % (a, 1 - b, b) for a, b in zip(p, lab)]
+    assert open(pred).read().split("\n")[:-1] == want
+    if valued:
+        return
+    args = [os.path.join(build.LIBDIR, "xflow_lr"), tr, te, "1", str(F.E2E_EPOCHS),
+            "fm_mode=field_aware", "fields=%d" % Fd, "optimizer=ftrl", "k=%d" % k,
+            "pred_path=cli.txt"] + ["%s=%r" % kv for kv in h.kw().items() if kv[0] != "lr"]
+    out = subprocess.run(args, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))
+    assert out.returncode == 0, out.stderr
+    assert O.format_auc_line(ll, auc, tp, fp) in out.stdout.splitlines(), out.stdout
+    assert open(str(tmp_path / "cli.txt")).read().split("\n")[:-1] == want
 
 
 # ---------------------------------------------------------------------------- refusals

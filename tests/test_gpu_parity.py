@@ -24,6 +24,8 @@ import pytest
 from oracle import pyoracle as O
 from xflow_amd import capi
 
+from ._hyper_cases import synth     # (the generator lives where the CPU tests can import it)
+
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-6        # north_star: "within 1e-6 relative on the float loss/weights"
@@ -67,20 +69,6 @@ def state_distance(a, b):
     """max |a-b| / (|b| + rms(b)) — the measure near_state bounds"""
     a64, b64 = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.max(np.abs(a64 - b64) / (np.abs(b64) + np.sqrt(np.mean(b64 * b64)) + ATOL)))
-
-
-def synth(rng, R, nnz_per_row, nkeys, zipf=None, ragged=False):
-    lens = rng.randint(0, 2 * nnz_per_row + 1, size=R) if ragged else np.full(R, nnz_per_row)
-    rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    n = int(lens.sum())
-    if zipf:
-        fid = np.minimum(rng.zipf(zipf, size=n), nkeys) - 1
-    else:
-        fid = rng.randint(0, nkeys, size=n)
-    table = np.array([O.hash_str(str(i)) for i in range(nkeys)], dtype=np.uint64)
-    keys = table[fid]
-    labels = rng.randint(0, 2, size=R).astype(np.int32)
-    return rowptr, keys, labels
 
 
 # ------------------------------------------------------------------------- table (a4, a8-a10)

@@ -21,6 +21,7 @@ from xflow_amd import capi
 
 from .test_gpu_parity import same
 from .test_group_cpu import free_port
+from ._hyper_cases import NO_L1, SGD_HI
 from .test_sharded_gloo import _data, _simulate
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +42,7 @@ def _big_data(rank, step):
 
 
 def _rank(rank, world, port, transport, model, optimizer, schedule, steps, outdir, save, q,
-          data="small", update="rank_ordered", k=4):
+          data="small", update="rank_ordered", k=4, hyper=None, tune=None):
     _data = _big_data if data == "big" else globals()["_data"]
     try:
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -53,7 +54,9 @@ def _rank(rank, world, port, transport, model, optimizer, schedule, steps, outdi
             assert g.transport == (capi.TRANSPORT_RCCL if ndev.value >= world
                                    else capi.TRANSPORT_HOST)
         st = capi.Sharded(g, model=model, optimizer=optimizer, k=k, capacity=64,
-                          schedule=schedule, seed=7, update=update)
+                          schedule=schedule, seed=7, update=update, **(hyper or {}))
+        if tune:
+            capi.tune(*tune)
         alive = []   # freeing a minibatch whose Push is still outstanding would flush it early
         for s in range(steps):
             b = st.compile(*_data(rank, s))
@@ -83,12 +86,13 @@ def _rank(rank, world, port, transport, model, optimizer, schedule, steps, outdi
 
 
 def _run(world, transport, model, optimizer, schedule, outdir, save=False, steps=4,
-         data="small", update="rank_ordered", k=4):
+         data="small", update="rank_ordered", k=4, hyper=None, tune=None):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = free_port()
     ps = [ctx.Process(target=_rank, args=(r, world, port, transport, model, optimizer, schedule,
-                                          steps, str(outdir), save, q, data, update, k))
+                                          steps, str(outdir), save, q, data, update, k,
+                                          hyper.kw() if hyper else None, tune))
           for r in range(world)]
     for p in ps:
         p.start()
@@ -127,9 +131,9 @@ def _fm_replay_rank(port, outdir, q):
         q.put(traceback.format_exc())
 
 
-def _check_against_oracle(world, model, optimizer, schedule, outdir, steps=4):
+def _check_against_oracle(world, model, optimizer, schedule, outdir, steps=4, hyper=None):
     with O.sum_mode(1):
-        w, v, losses = _simulate(world, model, optimizer, steps, schedule)
+        w, v, losses = _simulate(world, model, optimizer, steps, schedule, hyper)
     parts = [np.load(os.path.join(str(outdir), "rank%d.npz" % r)) for r in range(world)]
     for nm, store in (("w", w), ("v", v)):
         if store is None:
@@ -178,6 +182,22 @@ def test_owner_compute_dataflow_ranks_share_one_gpu(tmp_path, world, optimizer):
     (tables after 4 steps with a defrag in between, and the forward of a fifth minibatch)"""
     _run(world, capi.TRANSPORT_HOST, "lr", optimizer, "owner", tmp_path)
     _check_against_oracle(world, "lr", optimizer, "sequential", tmp_path)
+
+
+@pytest.mark.parametrize("owner_pass", [4, 2], ids=["k_lr_grad_multi", "k_lr_grad_ranked"])
+@pytest.mark.parametrize("hyper", [NO_L1, SGD_HI], ids=repr)
+def test_owner_compute_dataflow_away_from_the_default_hyper_parameters(tmp_path, hyper,
+                                                                       owner_pass):
+    """capi.Sharded(alpha=0.3, beta=0.25, lambda1=0, lambda2=0.5) and capi.Sharded(lr=0.2) on the
+    owner-compute dataflow, two workers: the owner's steps for several workers run under that set
+    in a phase per worker (owner_pass = 4: k_lr_grad_multi, which the shape would pick too) and
+    in the merged phases (owner_pass = 2: k_lr_grad_ranked), and so does the oracle"""
+    _run(2, capi.TRANSPORT_HOST, "lr", hyper.opt, "owner", tmp_path, hyper=hyper,
+         tune=("owner_pass", owner_pass))
+    w, _ = _check_against_oracle(2, "lr", hyper.opt, "sequential", tmp_path, hyper=hyper)
+    with O.sum_mode(1):
+        d, _, _ = _simulate(2, "lr", hyper.opt, 4, "sequential")
+    assert not np.array_equal(w.export()[1], d.export()[1])       # not the default's table
 
 
 @pytest.mark.parametrize("world,optimizer,data", [(2, "ftrl", "small"), (3, "sgd", "small"),

@@ -29,14 +29,14 @@ bits = S.bits
 
 
 # ---------------------------------------------------------------- what a rank does
-def _rank(rank, spec, port, outdir, empty_ranks, general, q):
+def _rank(rank, spec, port, outdir, empty_ranks, general, hyper, q):
     try:
         if general:
             os.environ["XF_SHARDED_GENERAL"] = "1"
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         world, schedule = spec[1], spec[5]
         g = capi.Group(rank, world, "127.0.0.1", port, capi.TRANSPORT_HOST, device=0)
-        st = T._trainer(g, spec)
+        st = T._trainer(g, spec, **hyper)
         train, held = S.streams(spec, empty_ranks)[rank]
         last = [p[-1] for p in S.points(schedule, len(train))]
         out, alive = {}, []     # (a freed minibatch would flush its outstanding Push early)
@@ -87,15 +87,15 @@ def _table_is(parts, i, nm, adm, world, ftrl, what):
     return (adm.keys,) + tuple(cols)
 
 
-def _judge(spec, tmp_path, empty_ranks=(), general=False):
+def _judge(spec, tmp_path, empty_ranks=(), general=False, hyper=None):
     mode, world, F, k, opt, schedule, case, valued = spec
     port = free_port()
-    T._spawn(_rank, [(r, spec, port, str(tmp_path), tuple(empty_ranks), general)
-                     for r in range(world)])
+    T._spawn(_rank, [(r, spec, port, str(tmp_path), tuple(empty_ranks), general,
+                      hyper.kw() if hyper else {}) for r in range(world)])
     parts = [np.load(os.path.join(str(tmp_path), "rank%d.npz" % r)) for r in range(world)]
     judge = I.Judge()
     strs = S.streams(spec, empty_ranks)
-    run = S.Run(spec, strs, judge, S.init_seed(spec))
+    run = S.Run(spec, strs, judge, S.init_seed(spec), hyper)
     ftrl = opt == "ftrl"
     for i, steps in enumerate(S.points(schedule, len(strs[0][0]))):
         p = run.point(steps)
@@ -135,3 +135,10 @@ def test_a_rank_without_rows_in_general_position(tmp_path, spec):
     never computes on, and owns its share of the keys"""
     parts = _judge(spec, tmp_path, empty_ranks=(1,))
     assert len(parts[1]["p0_w_k"]) and len(parts[1]["p0_v_k"]) and len(parts[1]["pctr"]) == 0
+
+
+@pytest.mark.parametrize("spec,hyper", S.HYPER, ids=S.hyper_id)
+def test_ranks_away_from_the_default_hyper_parameters(tmp_path, spec, hyper):
+    """capi.Sharded(alpha=, beta=, lambda1=, lambda2=, lr=): xf_sharded_create hands the five
+    values to every rank's shard of both tables, the owners' steps use them"""
+    _judge(spec, tmp_path, hyper=hyper)

@@ -28,12 +28,12 @@ _TIMEOUT = 150      # seconds the parent waits for a rank's report
 
 
 # ---------------------------------------------------------------- what a rank does
-def _trainer(g, spec, schedule=None, capacity=1 << 15):
+def _trainer(g, spec, schedule=None, capacity=1 << 15, **hyper):
     mode, world, F, k, opt, sched, case, valued = spec
     kw = {"canonical": dict(fm_mode="canonical"),
           "field_aware": dict(fm_mode="field_aware", fields=F), "lr": {}}[mode]
     return capi.Sharded(g, model="lr" if mode == "lr" else "fm", optimizer=opt, k=k or 10,
-                        capacity=capacity, schedule=schedule or sched, seed=7, **kw)
+                        capacity=capacity, schedule=schedule or sched, seed=7, **kw, **hyper)
 
 
 def _import_old(st, spec, strs, rank, world):

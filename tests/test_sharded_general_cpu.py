@@ -11,6 +11,7 @@ import pytest
 
 from tests import _general_cases as GC
 from tests import _general_checker as G
+from tests import _hyper_cases as HC
 from tests import _interval as I
 from tests import _sharded_general_checker as S
 from tests import _sharded_modes_checker as M
@@ -404,3 +405,21 @@ def test_ored_masks_are_invisible_to_the_exact_cases():
             assert a.dtype == b.dtype and np.array_equal(
                 a.view(np.uint32) if a.dtype == np.float32 else a,
                 b.view(np.uint32) if b.dtype == np.float32 else b), S.case_id(spec)
+
+
+# ------------------------------------------------- away from the default hyper-parameters
+@pytest.mark.parametrize("spec,hyper", S.HYPER, ids=S.hyper_id)
+def test_hyper_cases_stay_under_the_cap(spec, hyper):
+    """the runs of test_ranks_away_from_the_default_hyper_parameters, the checker alone under the
+    same set: the caps, and where the set is SPARSE its condition on the factor table (20 to
+    80 % of the touched coordinates exactly 0 after the last step, some that were 0 after the
+    first step not later)"""
+    j = I.Judge()
+    run, pts, pctr = S.run_cpu(spec, j, hyper=hyper)
+    print(j.format(S.case_id(spec) + " " + repr(hyper)))
+    j.assert_cap()
+    if hyper is HC.SPARSE:
+        track = HC.Track()
+        for i, p in enumerate(pts):
+            track.note(i, p.v.keys, p.v.tables[0][0], p.v.stepped)
+        HC.assert_sparse(track, S.case_id(spec))

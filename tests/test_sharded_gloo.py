@@ -54,13 +54,16 @@ def _worker(rank, world, port, model, optimizer, steps, outdir, schedule="sequen
     dist.destroy_process_group()
 
 
-def _simulate(world, model, optimizer, steps, schedule="sequential"):
+def _simulate(world, model, optimizer, steps, schedule="sequential", hyper=None):
     from oracle import pyoracle as O
     opt = O.OPT_FTRL if optimizer == "ftrl" else O.OPT_SGD
     w = O.Store(opt, 1)
     v = None
     if model == "fm":
         v = O.Store(opt, 4, O.INIT_HASHNORM if opt == O.OPT_FTRL else O.INIT_CONST, 0.001, 7)
+    if hyper is not None:   # (tests/_hyper_cases.py: a Hyper) one set for both tables
+        hyper.to_store(w)
+        hyper.to_store(v)
     outstanding = None      # stale1: the Push of the previous step, applied after this Pull
     for s in range(steps):
         obs = [O.Batch(*_data(r, s)) for r in range(world)]

@@ -190,6 +190,8 @@ SIGNATURES = {
                                   C.POINTER(C.c_size_t)]),
     "xf_table_import": (C.c_int, [vp, u64p, C.c_size_t, f32p, f32p, f32p]),
     "xf_table_w_derived": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "xf_table_div_exact": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "xf_div_by_const_probe": (C.c_int, [f32p, C.c_size_t, C.c_float, C.c_int, f32p]),
     "xf_lr_forward_dev": (C.c_int, [C.POINTER(DevBatch), vp, vp, vp, vp]),
     "xf_lr_grad_dev": (C.c_int, [C.POINTER(DevBatch), vp, vp, vp]),
     "xf_fm_forward_dev": (C.c_int, [C.POINTER(DevBatch), C.c_int, vp, vp, vp, vp, vp, vp]),
@@ -1049,6 +1051,16 @@ def cells_info(batch):
     return dict(zip(names, list(out)))
 
 
+def div_by_const_probe(x, d, exact=False):
+    """the FTRL step's x / d on the GPU, element by element (xf_div_by_const_probe): with the
+    guard of the subnormal range, or — exact — the bare product with 1 / d"""
+    require_gpu()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.empty_like(x)
+    check(lib().xf_div_by_const_probe(_p(x, f32p), x.size, d, int(bool(exact)), _p(out, f32p)))
+    return out
+
+
 class Table:
     """One GPU's shard of the parameter table (ps-lite server replacement)."""
 
@@ -1150,6 +1162,13 @@ class Table:
         """the gradient + Push kernels derive the old weight from (n, z) (xf_table_w_derived)"""
         yes = C.c_int(0)
         check(lib().xf_table_w_derived(self.h, C.byref(yes)))
+        return bool(yes.value)
+
+    def div_exact(self):
+        """the table found its alpha an exact divisor: its steps divide by it without the guard
+        of the subnormal range (xf_table_div_exact)"""
+        yes = C.c_int(0)
+        check(lib().xf_table_div_exact(self.h, C.byref(yes)))
         return bool(yes.value)
 
     # device-pointer API (ints = raw device addresses, e.g. torch.Tensor.data_ptr())

@@ -127,7 +127,9 @@ __device__ __forceinline__ float hashnorm(uint64_t seed, uint64_t key, uint32_t 
 // that d, all with subnormal quotients) — the division itself is done (a branch no wavefront
 // takes in practice; x == 0 stays on the fast path: +-0 either way).  Checked on the host for
 // all 2^32 values of x at five divisors and for random (x, d) pairs
-// (tests/test_div_by_alpha_cpu.py), on the GPU by the bit-exact parity tests.
+// (tests/test_div_by_alpha_cpu.py); on the GPU the function itself, guarded and bare, at d = 50000
+// on those 1308 values and around the guard's threshold (xf_div_by_const_probe,
+// tests/test_gpu_hyper.py) — the parity tests' alphas are exact divisors and never take the guard.
 //
 // `exact` (round 5): the table has checked its alpha on the GPU — every one of the 2^32 values of
 // x, the bare product against the division, when the hyper-parameters were set (xf_table.hip:

@@ -2087,6 +2087,46 @@ extern "C" int xf_table_w_derived(xf_table *t, int *yes) {
   return XF_OK;
 }
 
+// the verdict of div_exact_for on the table's alpha, as the kernels see it: the sign of
+// TableDev::inv_alpha (tests)
+extern "C" int xf_table_div_exact(xf_table *t, int *out) {
+  XF_REQUIRE(t && out, "xf_table_div_exact: null argument");
+  *out = std::signbit(t->T.inv_alpha) ? 1 : 0;
+  return XF_OK;
+}
+
+// out[i] = xf::div_by_const(x[i], d, 1.0 / (double)d, exact), the function as the steps call it
+__global__ void __launch_bounds__(kBlock)
+k_div_by_const_probe(const float *__restrict__ x, size_t n, float d, double inv_d, bool exact,
+                     float *__restrict__ out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (size_t)gridDim.x * blockDim.x)
+    out[i] = xf::div_by_const(x[i], d, inv_d, exact);
+}
+
+// xf::div_by_const on n host values, with its guard (exact = 0) or without (exact = 1).  For the
+// tests: inside a step the guard's range cannot be reached (x is 0 or at least about 2^-75).
+extern "C" int xf_div_by_const_probe(const float *x, size_t n, float d, int exact, float *out) {
+  XF_REQUIRE(x && out, "xf_div_by_const_probe: null argument");
+  XF_REQUIRE(d > 0.0f && std::isfinite(d), "xf_div_by_const_probe: d must be finite and > 0");
+  if (n == 0) return XF_OK;
+  float *dx = nullptr, *dout = nullptr;
+  hipError_t e = hipMalloc((void **)&dx, n * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void **)&dout, n * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(dx, x, n * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const size_t blocks = (n + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_div_by_const_probe, dim3((unsigned)(blocks < 4096 ? blocks : 4096)),
+                       dim3(kBlock), 0, nullptr, dx, n, d, 1.0 / (double)d, exact != 0, dout);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out, dout, n * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(dx);
+  (void)hipFree(dout);
+  XF_HIP(e);
+  return XF_OK;
+}
+
 // keys[i] (or keys[list[i]]) for i < n into out
 __global__ void __launch_bounds__(kBlock)
 k_take_keys(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ list, size_t n,
