@@ -956,6 +956,68 @@ int xf_cells_finalize_rows(const double *d_partial, const int32_t *d_labels, uin
                            void *stream);
 int xf_sharded_set_neg_weight(xf_sharded *st, float weight);
 
+/* ---------------------------------------------------------------- feature crosses      */
+/* Crossed features as a GPU stage ahead of the key build (not in the reference).  Like admission
+ * and negative subsampling it works on a minibatch's CSR arrays and its result goes to any *_dev
+ * compile; it keeps no state and ADDS nonzeros.  It reads the nonzeros' field ids (fgid).
+ * Definition.  mix64 as for admission (add 0x9e3779b97f4a7c15, then the splitmix64 finaliser):
+ *   salt(fa, fb)              = mix64((uint64)(uint32)fa << 32 | (uint32)fb)
+ *   cross_key(ka, kb, fa, fb) = mix64(mix64(ka ^ salt(fa, fb)) + kb)          (64-bit wrapping)
+ * xf_cross_key is that function as host code, from the one definition the kernels use.  The key
+ * depends on the two field ids, not on the pair's place in the spec: reordering or extending a
+ * spec leaves existing crossed keys, and a saved model, valid.
+ * A spec is 1 .. 32 ordered pairs (fa_p, fb_p), fa != fb, both in 0 .. 2^31 - 1, no pair twice;
+ * (a, b) and (b, a) are different pairs.  xf_cross_parse reads "2*3,16*17" (decimal, no blanks)
+ * into arrays of `cap` entries; a malformed spec is XF_EINVAL naming the offending piece.
+ * xf_cross_create checks the same rules, and fgid_base >= 0 with fgid_base + npairs <= 2^31.
+ * One apply = one minibatch.  The output row is the input row, unchanged and in order, then for
+ * p = 0, 1, ...: for every nonzero i of the row with fgid == fa_p, in row order, and every nonzero
+ * j with fgid == fb_p, in row order, one nonzero with key cross_key(key_i, key_j, fa_p, fb_p), fgid
+ * fgid_base + p and value fp32(val_i * val_j).  A multi-valued field gives all |A| x |B|
+ * combinations; a row without a member on either side gains nothing from the pair; a row whose
+ * offsets descend or leave the arrays has length 0.  Labels and the row count do not change.  A
+ * spec none of whose fields occur returns the inputs byte for byte.  Nothing depends on the launch
+ * shape: every output position is arithmetic on counts.
+ * xf_cross_apply_dev: device arrays (d_rowptr row-relative u32, R + 1).  d_fgid is required (NULL:
+ * XF_EINVAL); d_vals may be NULL, and then no values come out; want_fgid_out = 0: no fgid comes
+ * out (LR and canonical FM do not read it).  The outputs are device arrays owned by the stage,
+ * valid until its next apply, written in the order of `stream` and grown geometrically; *NNZ_out =
+ * the output nonzeros.  The stage allocates on the device only in an apply.  R = 0 and NNZ = 0 are
+ * valid.  One wait for the stream, for the total (none with R = 0), after the count and before the
+ * emit, which is where the buffers grow.  The total is counted in 64 bits: 2^32 - 1 or more is
+ * XF_EINVAL naming it, with nothing emitted and no buffer grown.  Rows that overlap (their lengths
+ * sum to more than NNZ) are XF_EINVAL.
+ * xf_cross_apply: the reader's host arrays and a row slice: uploads the slice (rowptr rebased to
+ * u32; labels, when given, to *d_labels_out unchanged) and runs the same kernels — one
+ * implementation, the device one.
+ * xf_cross_stats, summed over the applies: rows seen, input nonzeros, crossed nonzeros.
+ * xf_tune: cross_short_max (0 .. 64, default 64: rows of at most that many nonzeros take the
+ * wave-per-row emit, longer ones the workgroup-per-row emit) and cross_lds_chunks (1 .. 2048,
+ * default 2048: a long row of more 64-nonzero chunks keeps its member lists in a global scratch
+ * instead of LDS) move rows between the emit's paths, for tests and measurements; the result is
+ * the same. */
+typedef struct xf_cross xf_cross;
+uint64_t xf_cross_key(uint64_t ka, uint64_t kb, int32_t fa, int32_t fb);
+int xf_cross_parse(const char *spec, int32_t *fa, int32_t *fb, int cap, int *npairs);
+int xf_cross_create(xf_cross **out, const int32_t *fa, const int32_t *fb, int npairs,
+                    int32_t fgid_base);
+int xf_cross_destroy(xf_cross *x);
+int xf_cross_params(const xf_cross *x, int32_t *fa, int32_t *fb, int cap, int *npairs,
+                    int32_t *fgid_base);
+int xf_cross_apply_dev(xf_cross *x, const uint64_t *d_keys, const int32_t *d_fgid,
+                       const float *d_vals, const uint32_t *d_rowptr, uint32_t R, uint32_t NNZ,
+                       void *stream, int want_fgid_out, const uint64_t **d_keys_out,
+                       const int32_t **d_fgid_out, const float **d_vals_out,
+                       const uint32_t **d_rowptr_out, uint32_t *NNZ_out);
+int xf_cross_apply(xf_cross *x, const uint64_t *rowptr, const uint64_t *keys, const int32_t *fgid,
+                   const float *vals, const int32_t *labels, size_t row_begin, size_t row_end,
+                   void *stream, int want_fgid_out, const uint64_t **d_keys_out,
+                   const int32_t **d_fgid_out, const float **d_vals_out,
+                   const uint32_t **d_rowptr_out, const int32_t **d_labels_out, uint32_t *R_out,
+                   uint32_t *NNZ_out);
+int xf_cross_stats(const xf_cross *x, uint64_t *rows_seen, uint64_t *nonzeros_in,
+                   uint64_t *nonzeros_crossed);
+
 /* ---------------------------------------------------------------- metrics             */
 /* Base::calculate_auc (base.h:84-110): reference-format logloss (mean of y*log2 p +
  * (1-y)*log2(1-p), negative), AUC by descending-pctr rank sum, plus the conventional
@@ -1007,7 +1069,15 @@ int XFDestroy(void **h);
  *        by 1 / r (xf_sharded_set_neg_weight); test blocks are never sampled; core_num 1,
  *        key_build=gpu, parity=exact, not with schedule=owner / owner_stale1 on several workers;
  *        nothing is saved with the model).  XFGetMetric: neg_seen neg_kept (negative rows)
- *        rows_kept; rows_trained counts kept rows */
+ *        rows_kept; rows_trained counts kept rows
+ *        cross(SPEC, e.g. 2*3,16*17; default off: feature crosses, xf_cross_* — every block gains
+ *        its crossed nonzeros on the GPU: training after negative subsampling and before
+ *        admission, predict before admission; every rank crosses its own rows, on every schedule;
+ *        core_num 1, key_build=gpu, parity=exact, not with ingest=gpu (use ingest=gpu_fields); the
+ *        spec is not saved with the model: predict needs the same cross=)
+ *        cross_fgid_base(N, default 0: the crossed nonzeros' fgids are N + the pair's index; read
+ *        only with fm_mode=field_aware, where N + pairs <= fields).  XFGetMetric: cross_in
+ *        cross_out (nonzeros into and out of the stage) */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

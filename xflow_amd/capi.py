@@ -292,6 +292,20 @@ SIGNATURES = {
     "xf_cells_finalize_rows": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                          vp, vp, vp]),
     "xf_sharded_set_neg_weight": (C.c_int, [vp, C.c_float]),
+    "xf_cross_key": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
+    "xf_cross_parse": (C.c_int, [C.c_char_p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
+    "xf_cross_create": (C.c_int, [C.POINTER(vp), i32p, i32p, C.c_int, C.c_int32]),
+    "xf_cross_destroy": (C.c_int, [vp]),
+    "xf_cross_params": (C.c_int, [vp, i32p, i32p, C.c_int, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int32)]),
+    "xf_cross_apply_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_int,
+                                     C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                     C.POINTER(C.c_uint32)]),
+    "xf_cross_apply": (C.c_int, [vp, u64p, u64p, i32p, f32p, i32p, C.c_size_t, C.c_size_t, vp,
+                                 C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                 C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_uint32)]),
+    "xf_cross_stats": (C.c_int, [vp, u64p, u64p, u64p]),
     "XFCreate": (C.c_int, [C.POINTER(vp), C.c_char_p, C.c_char_p]),
     "XFStartTrain": (C.c_int, [C.POINTER(vp)]),
     "XFDestroy": (C.c_int, [C.POINTER(vp)]),
@@ -811,6 +825,119 @@ class NegSample:
         """(rows seen, rows kept, negatives seen, negatives kept), summed over the applies"""
         v = [C.c_uint64() for _ in range(4)]
         check(lib().xf_negsample_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
+def cross_key(ka, kb, fa, fb):
+    """the key of the nonzero that crosses key ka of field fa with key kb of field fb
+    (xf_cross_key; host code, the kernels' own definition)"""
+    return int(lib().xf_cross_key(int(ka) & (2**64 - 1), int(kb) & (2**64 - 1), int(fa), int(fb)))
+
+
+def cross_parse(spec):
+    """"2*3,16*17" as a list of (fa, fb) pairs (xf_cross_parse; a malformed spec raises, naming
+    the offending piece)"""
+    fa, fb = np.zeros(32, np.int32), np.zeros(32, np.int32)
+    n = C.c_int()
+    check(lib().xf_cross_parse(str(spec).encode(), _p(fa, i32p), _p(fb, i32p), 32, C.byref(n)))
+    return [(int(fa[p]), int(fb[p])) for p in range(n.value)]
+
+
+class Cross:
+    """Feature crosses (xf_cross_*): apply() returns a minibatch with, behind every row's own
+    nonzeros, one nonzero per listed pair of fields and per (member of the first, member of the
+    second), keyed by cross_key, with fgid fgid_base + the pair's index and the product of the two
+    values.  spec_or_pairs: "2*3,16*17" or a list of (fa, fb).  Stateless but for the statistics."""
+
+    def __init__(self, spec_or_pairs, fgid_base=0):
+        self.h = vp()
+        pairs = cross_parse(spec_or_pairs) if isinstance(spec_or_pairs, str) else \
+            [(int(a), int(b)) for a, b in spec_or_pairs]
+        fa = np.array([a for a, _ in pairs] or [0], np.int32)
+        fb = np.array([b for _, b in pairs] or [0], np.int32)
+        check(lib().xf_cross_create(C.byref(self.h), _p(fa, i32p), _p(fb, i32p), len(pairs),
+                                    int(fgid_base)))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().xf_cross_destroy(self.h)
+            self.h = None
+
+    def params(self):
+        """(pairs, fgid_base)"""
+        fa, fb = np.zeros(32, np.int32), np.zeros(32, np.int32)
+        n, base = C.c_int(), C.c_int32()
+        check(lib().xf_cross_params(self.h, _p(fa, i32p), _p(fb, i32p), 32, C.byref(n),
+                                    C.byref(base)))
+        return [(int(fa[p]), int(fb[p])) for p in range(n.value)], base.value
+
+    def apply_dev(self, rowptr, keys, fgid, labels=None, values=None, want_fgid=True,
+                  row_begin=0, row_end=None, stream=None):
+        """host arrays in (rows [row_begin, row_end) uploaded as they are), the crossed minibatch
+        as an AdmitDev out (device pointers owned by the stage, valid until its next apply).  The
+        arrays are WRITTEN IN THE ORDER OF `stream` and the call does not wait for them: hand them
+        to work on the same stream (Sharded.stream() for a trainer's compile_dev), or wait for
+        `stream` first"""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert len(rowptr) >= 1
+        row_end = len(rowptr) - 1 if row_end is None else row_end
+        args = []
+        for a, dt, pt in ((fgid, np.int32, i32p), (values, np.float32, f32p)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=dt)
+                assert len(a) == len(keys), "one entry per key"
+                a = a if len(a) else np.zeros(1, dt)
+            args.append((a, pt))
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            assert len(labels) == len(rowptr) - 1, "one label per row"
+            labels = labels if len(labels) else np.zeros(1, np.int32)
+        args.append((labels, i32p))
+        if len(keys) == 0:
+            keys = np.zeros(1, np.uint64)
+        ptr = [(_p(a, pt) if a is not None else None) for a, pt in args]
+        dk, dfg, dv, dr, dl = vp(), vp(), vp(), vp(), vp()
+        Ro, No = C.c_uint32(), C.c_uint32()
+        check(lib().xf_cross_apply(self.h, _p(rowptr, u64p), _p(keys, u64p), ptr[0], ptr[1],
+                                   ptr[2], row_begin, row_end, stream, 1 if want_fgid else 0,
+                                   C.byref(dk), C.byref(dfg), C.byref(dv), C.byref(dr),
+                                   C.byref(dl), C.byref(Ro), C.byref(No)))
+        return AdmitDev(dk.value, dr.value, dl.value, Ro.value, No.value, dfg.value, dv.value)
+
+    def cross_dev(self, d_keys, d_rowptr, R, NNZ, d_fgid, d_vals=None, want_fgid=True,
+                  stream=None):
+        """xf_cross_apply_dev: device pointers in (ints), (d_keys, d_rowptr, NNZ, d_fgid, d_vals)
+        of the crossed minibatch out; labels and R are the caller's, untouched"""
+        dk, dfg, dv, dr = vp(), vp(), vp(), vp()
+        No = C.c_uint32()
+        check(lib().xf_cross_apply_dev(self.h, d_keys, d_fgid, d_vals, d_rowptr, R, NNZ, stream,
+                                       1 if want_fgid else 0, C.byref(dk), C.byref(dfg),
+                                       C.byref(dv), C.byref(dr), C.byref(No)))
+        return dk.value, dr.value, No.value, dfg.value, dv.value
+
+    def apply(self, rowptr, keys, fgid, labels=None, values=None, want_fgid=True, row_begin=0,
+              row_end=None):
+        """the crossed host arrays (downloaded): (rowptr uint32, keys) and then, for each of
+        labels / fgid (want_fgid) / values that was given, its array in that order"""
+        d = self.apply_dev(rowptr, keys, fgid, labels, values, want_fgid, row_begin, row_end)
+        check(lib().xf_stream_sync(None))
+        out = [(np.zeros(d.R + 1, np.uint32), d.d_rowptr), (np.zeros(d.NNZ, np.uint64), d.d_keys)]
+        if labels is not None:
+            out.append((np.zeros(d.R, np.int32), d.d_labels))
+        if want_fgid:
+            out.append((np.zeros(d.NNZ, np.int32), d.d_fgid))
+        if values is not None:
+            out.append((np.zeros(d.NNZ, np.float32), d.d_vals))
+        for a, ptr in out:
+            if a.nbytes:
+                check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
+        return tuple(a for a, _ in out)
+
+    def stats(self):
+        """(rows seen, input nonzeros, crossed nonzeros), summed over the applies"""
+        v = [C.c_uint64() for _ in range(3)]
+        check(lib().xf_cross_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
 
@@ -1423,6 +1550,13 @@ class Sharded:
         """'reference', 'canonical' or 'field_aware': before the first step (the tables empty);
         several ranks: schedules 'sequential' and 'stale1' only"""
         check(lib().xf_sharded_set_fm_mode(self.h, FM_MODES[mode]))
+
+    def stream(self):
+        """the stream the trainer compiles and steps on (xf_sharded_stream; non-blocking): what a
+        stage whose outputs are written in stream order — Cross.apply_dev — is given"""
+        st = vp()
+        check(lib().xf_sharded_stream(self.h, C.byref(st)))
+        return st
 
     def set_neg_weight(self, weight):
         """the weight of a kept negative (Workspace.neg_weight); several ranks: schedules

@@ -10,6 +10,7 @@
 // The result depends only on the input rows, so a compiled batch can be cached across
 // epochs (the reference re-parses and re-sorts every epoch, lr_worker.cc:184).
 #include "xf_batch.h"
+#include "xf_cross.h"
 #include "xf_scratch.h"
 #include "xf_tiling.h"
 
@@ -297,6 +298,7 @@ extern "C" int xf_tune(const char *name, double value) {
   else if (!strcmp(name, "exp_knob")) xf::set_exp_knob((int)value);
 #endif
   else if (!strcmp(name, "batch_pool_blobs")) xf::blob_pool_limit((int)value);
+  else if (xf::cross_set_knob(name, value) == XF_OK) return XF_OK;
   else
     return xf::set_error(XF_EINVAL, "xf_tune: unknown knob '%s' (or a value it does not take)", name);
   return XF_OK;

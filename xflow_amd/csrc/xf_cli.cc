@@ -30,7 +30,10 @@ int main(int argc, char *argv[]) {
                  "it N times; one worker): append admit_count=N [admit_log2_slots=26 "
                  "admit_hashes=3]; several workers sharing one filter: admit_shared=1\n"
               << "negative subsampling (every positive row kept, a negative with probability r, "
-                 "a kept negative's loss weighted by 1 / r): append neg_keep=r\n";
+                 "a kept negative's loss weighted by 1 / r): append neg_keep=r\n"
+              << "feature crosses (a nonzero per listed pair of fields and per pair of their "
+                 "members, formed on the GPU; predict needs the same spec): append cross=2*3,16*17 "
+                 "[cross_fgid_base=N with fm_mode=field_aware]\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler
@@ -83,6 +86,13 @@ int main(int argc, char *argv[]) {
     std::cout << "rank " << worker->rank << " neg_seen = " << (unsigned long long)seen
               << " neg_kept = " << (unsigned long long)kept << " rows_kept = "
               << (unsigned long long)rows << std::endl;
+  }
+  if (!worker->cross_spec.empty()) {  // (every rank crosses its own rows)
+    double in = 0, out = 0;
+    worker->get_metric("cross_in", &in);
+    worker->get_metric("cross_out", &out);
+    std::cout << "rank " << worker->rank << " cross_in = " << (unsigned long long)in
+              << " cross_out = " << (unsigned long long)out << std::endl;
   }
   double eps = 0;
   worker->get_metric("examples_per_sec", &eps);

@@ -53,6 +53,7 @@ Worker::~Worker() {
   for (xf_sbatch *b : cache_) xf_sbatch_free(b);
   if (admit_) xf_admit_destroy(admit_);
   if (sample_) xf_negsample_destroy(sample_);
+  if (cross_) xf_cross_destroy(cross_);
   if (sharded_) xf_sharded_destroy(sharded_);  // owns the tables
   if (group_) xf_group_destroy(group_);
 }
@@ -73,7 +74,8 @@ static const char *env_first(std::initializer_list<const char *> names) {
 int Worker::create_tables() {
   if (sharded_) {
     XF_TRY(create_admit());
-    return create_negsample();
+    XF_TRY(create_negsample());
+    return create_cross();
   }
   int w = world;
   if (w <= 0) {
@@ -138,7 +140,8 @@ int Worker::create_tables() {
     XF_TRY(rc);
   }
   XF_TRY(create_admit());
-  return create_negsample();
+  XF_TRY(create_negsample());
+  return create_cross();
 }
 
 static int world_from_env(int world) {
@@ -245,7 +248,7 @@ int Worker::sample_dev(size_t first_row, const uint64_t **d_keys, const int32_t 
   void *stream = nullptr;
   XF_TRY(xf_sharded_stream(sharded_, &stream));
   return xf_negsample_apply_dev(sample_, sample_stream_, ordinal_ + first_row, *d_keys,
-                                fm_mode == XF_FM_FIELD_AWARE ? *d_fgid : nullptr,
+                                fm_mode == XF_FM_FIELD_AWARE || cross_ ? *d_fgid : nullptr,
                                 feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
                                 stream, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ);
 }
@@ -255,8 +258,102 @@ int Worker::compile_sampled_dev(xf_sbatch **b, const uint64_t *d_keys, const int
                                 const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
   *b = nullptr;
   if (R == 0 && world <= 1) return XF_OK;  // (every row dropped: a block without rows)
-  if (admit_) return compile_admitted_dev(b, 1, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
+  return compile_staged_dev(b, 1, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
+}
+
+// Feature crosses add nonzeros to a block on the GPU ahead of the key build, from the nonzeros'
+// field ids: core_num > 1 slices a block after it was read, the host key build and the
+// reference-order forward take host arrays, and ingest=gpu hands out no fgid.  Every schedule and
+// any number of workers: a rank crosses its own rows and the trainers see keys only.  All refused
+// by name, before any rendezvous.
+int Worker::check_cross() const {
+  if (cross_spec.empty()) return XF_OK;
+  int32_t fa[32], fb[32];
+  int npairs = 0;
+  XF_TRY(xf_cross_parse(cross_spec.c_str(), fa, fb, 32, &npairs));
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: cross=%s needs core_num=1, not core_num=%d",
+             cross_spec.c_str(), core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: cross=%s together with key_build=host: the crossed "
+             "minibatch is born on the GPU (use key_build=gpu)", cross_spec.c_str());
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: cross=%s together with "
+             "parity=reference_order: that mode builds its keys on the host", cross_spec.c_str());
+  XF_REQUIRE(!ingest_gpu, "XFStartTrain: cross=%s together with ingest=gpu: the GPU tokeniser "
+             "hands out no fgid (use ingest=gpu_fields)", cross_spec.c_str());
+  if (fm_mode == XF_FM_FIELD_AWARE)
+    XF_REQUIRE(cross_fgid_base >= 0 && (long)cross_fgid_base + npairs <= (long)fields,
+               "XFStartTrain: cross_fgid_base=%d with %d pairs needs fields >= %ld, not fields=%d "
+               "(fm_mode=field_aware: a crossed nonzero's fgid is cross_fgid_base + its pair's "
+               "index)", cross_fgid_base, npairs, (long)cross_fgid_base + npairs, fields);
+  return XF_OK;
+}
+
+int Worker::create_cross() {
+  if (cross_spec.empty() || cross_) return XF_OK;
+  XF_TRY(check_cross());
+  int32_t fa[32], fb[32];
+  int npairs = 0;
+  XF_TRY(xf_cross_parse(cross_spec.c_str(), fa, fb, 32, &npairs));
+  // (the base is read only with fm_mode=field_aware: no other mode looks at a nonzero's fgid)
+  const int32_t base = fm_mode == XF_FM_FIELD_AWARE ? cross_fgid_base : 0;
+  XF_TRY(xf_cross_create(&cross_, fa, fb, npairs, base));
+  // the stage's first launches, on two rows of a private stage: start-up work like the two-row
+  // update of create_tables (the worker's own stage keeps its statistics clean)
+  xf_cross *warm = nullptr;
+  XF_TRY(xf_cross_create(&warm, fa, fb, npairs, base));
+  const uint64_t rp[3] = {0, 2, 4}, keys[4] = {11, 12, 12, 13};
+  const int32_t fg[4] = {fa[0], fb[0], fa[0], fb[0]};
+  void *stream = nullptr;
+  int rc = xf_sharded_stream(sharded_, &stream);
+  const uint64_t *fk = nullptr;
+  const uint32_t *fr = nullptr;
+  uint32_t R = 0, NNZ = 0;
+  if (rc == XF_OK)
+    rc = xf_cross_apply(warm, rp, keys, fg, nullptr, nullptr, 0, 2, stream, 0, &fk, nullptr,
+                        nullptr, &fr, nullptr, &R, &NNZ);
+  if (rc == XF_OK) rc = xf_stream_sync(stream);
+  xf_cross_destroy(warm);
+  return rc;
+}
+
+// the stages that follow sampling, on device arrays: the cross, when on (a block without rows has
+// nothing to cross), admission, when on, and the _dev compile of the worker's mode
+int Worker::compile_staged_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
+                               const int32_t *d_fgid, const float *d_vals,
+                               const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
+                               uint32_t NNZ, int keep) {
+  if (cross_ && R) {
+    void *stream = nullptr;
+    XF_TRY(xf_sharded_stream(sharded_, &stream));
+    const int32_t *ff = nullptr;
+    const float *fv = nullptr;
+    XF_TRY(xf_cross_apply_dev(cross_, d_keys, d_fgid, feature_values ? d_vals : nullptr, d_rowptr,
+                              R, NNZ, stream, fm_mode == XF_FM_FIELD_AWARE, &d_keys, &ff, &fv,
+                              &d_rowptr, &NNZ));
+    d_fgid = ff;
+    d_vals = fv;
+  }
+  if (admit_)
+    return compile_admitted_dev(b, update, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ,
+                                keep);
   return compile_dev_arrays(b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
+}
+
+// rows [start, end) of host arrays through the cross: uploaded by the stage, then as above
+int Worker::compile_crossed(xf_sbatch **b, int update, const uint64_t *rowptr,
+                            const uint64_t *keys, const int32_t *fgid, const float *vals,
+                            const int32_t *labels, size_t start, size_t end, int keep) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const uint64_t *fk = nullptr;
+  const int32_t *ff = nullptr, *fl = nullptr;
+  const float *fv = nullptr;
+  const uint32_t *fr = nullptr;
+  uint32_t R = 0, NNZ = 0;
+  XF_TRY(xf_cross_apply(cross_, rowptr, keys, fgid, feature_values ? vals : nullptr, labels, start,
+                        end, stream, fm_mode == XF_FM_FIELD_AWARE, &fk, &ff, &fv, &fr, &fl, &R,
+                        &NNZ));
+  if (admit_) return compile_admitted_dev(b, update, fk, ff, fv, fr, fl, R, NNZ, keep);
+  return compile_dev_arrays(b, fk, ff, fv, fr, fl, R, NNZ, keep);
 }
 
 int Worker::compile_sampled(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
@@ -270,7 +367,7 @@ int Worker::compile_sampled(xf_sbatch **b, const uint64_t *rowptr, const uint64_
   const uint32_t *fr = nullptr;
   uint32_t R = 0, NNZ = 0;
   XF_TRY(xf_negsample_apply(sample_, sample_stream_, ordinal_ + start, rowptr, keys,
-                            fm_mode == XF_FM_FIELD_AWARE ? fgid : nullptr,
+                            fm_mode == XF_FM_FIELD_AWARE || cross_ ? fgid : nullptr,
                             feature_values ? vals : nullptr, labels, start, end, stream, &fk, &ff,
                             &fv, &fr, &fl, &R, &NNZ));
   return compile_sampled_dev(b, fk, ff, fv, fr, fl, R, NNZ, keep);
@@ -290,6 +387,9 @@ int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const u
   // (training blocks only — predict passes update 0 — and only rows of this rank's own)
   if (sample_ && update && trainer == sharded_ && rowptr && end > start)
     return compile_sampled(b, rowptr, keys, fgid, vals, labels, start, end, keep);
+  // (rows of this rank's own, training and predict; a rank without rows has nothing to cross)
+  if (cross_ && trainer == sharded_ && rowptr && end > start)
+    return compile_crossed(b, update, rowptr, keys, fgid, vals, labels, start, end, keep);
   if (admit_ && trainer == sharded_) {  // (core_num 1: filtered, compiled from device arrays)
     // (a rank without rows of its own — a shared filter — is in the collective apply all the same)
     if (!rowptr)
@@ -359,7 +459,8 @@ int Worker::compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr,
 // ingest = gpu_fields: what the tokeniser reads beside the fid is what the model needs — fgid for
 // field-aware FM, the third field with feature values; neither: the tokeniser of ingest = gpu
 int Worker::set_ingest_fields(xf_ingest *g) {
-  return xf_ingest_set_fields(g, ingest_fields && fm_mode == XF_FM_FIELD_AWARE,
+  return xf_ingest_set_fields(g, ingest_fields && (fm_mode == XF_FM_FIELD_AWARE ||
+                                                   !cross_spec.empty()),
                               ingest_fields && feature_values);
 }
 
@@ -792,10 +893,8 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
         if (rc == XF_OK && sample_) {
           rc = sample_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ);
           if (rc == XF_OK) rc = compile_sampled_dev(&b, dk, dfg, dv, drp, dl, R, NNZ, keep);
-        } else if (rc == XF_OK && admit_)
-          rc = compile_admitted_dev(&b, 1, dk, dfg, dv, drp, dl, R, NNZ, keep);
-        else if (rc == XF_OK)
-          rc = compile_dev_arrays(&b, dk, dfg, dv, drp, dl, R, NNZ, keep);
+        } else if (rc == XF_OK)
+          rc = compile_staged_dev(&b, 1, dk, dfg, dv, drp, dl, R, NNZ, keep);
         on_gpu = true;
         ++blocks_gpu;
       } else if (rc == XF_OK) {  // not of the common shape: the host parser's
@@ -990,6 +1089,7 @@ int Worker::train() {
   }
   XF_TRY(check_admit());  // before any rendezvous of a group
   XF_TRY(check_negsample());
+  XF_TRY(check_cross());
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
   std::cout << "my rank is = " << rank << std::endl;
@@ -1121,6 +1221,12 @@ int Worker::set_param(const char *name, const char *value) {
   } else if (n == "neg_keep") {
     XF_REQUIRE(!sample_, "XFSetParam: neg_keep cannot change once the sampler exists");
     neg_keep = strtof(value, nullptr);
+  } else if (n == "cross") {
+    XF_REQUIRE(!cross_, "XFSetParam: cross cannot change once the stage exists");
+    cross_spec = value;
+  } else if (n == "cross_fgid_base") {
+    XF_REQUIRE(!cross_, "XFSetParam: cross_fgid_base cannot change once the stage exists");
+    cross_fgid_base = atoi(value);
   } else if (n == "admit_count") {
     XF_REQUIRE(!admit_, "XFSetParam: admit_count cannot change once the filter exists");
     admit_count = atoi(value);
@@ -1161,6 +1267,10 @@ int Worker::get_metric(const char *name, double *value) {
     uint64_t rows_kept = 0, seen = 0, kept = 0;
     if (sample_) XF_TRY(xf_negsample_stats(sample_, nullptr, &rows_kept, &seen, &kept));
     *value = (double)(n == "neg_seen" ? seen : n == "neg_kept" ? kept : rows_kept);
+  } else if (n == "cross_in" || n == "cross_out") {
+    uint64_t in = 0, crossed = 0;
+    if (cross_) XF_TRY(xf_cross_stats(cross_, nullptr, &in, &crossed));
+    *value = (double)(n == "cross_in" ? in : in + crossed);
   } else if (n == "admit_seen" || n == "admit_kept") {
     uint64_t seen = 0, kept = 0;
     if (admit_) XF_TRY(xf_admit_stats(admit_, &seen, &kept));

@@ -92,6 +92,15 @@ class Worker {
   // parity=exact, not with the owner-compute schedules on several workers (checked where training
   // starts).  Stateless: nothing travels with the model.  Test blocks are never sampled.
   float neg_keep = 1.0f;
+  // Feature crosses (xf_cross.hip): cross = "2*3,16*17": every block gains, behind each row's own
+  // nonzeros, one nonzero per listed pair of fields and per (member, member), on the GPU — training:
+  // after negative subsampling (which drops rows) and before admission (which must see the crossed
+  // keys); predict: before admission.  Empty = off, nothing is created.  Every rank crosses its own
+  // rows, on every schedule.  core_num 1, key_build=gpu, parity=exact, not ingest=gpu (checked where
+  // training starts).  cross_fgid_base: the crossed nonzeros' fgids are base + the pair's index,
+  // read only with fm_mode=field_aware (base + pairs <= fields).  Nothing travels with the model.
+  std::string cross_spec;
+  int cross_fgid_base = 0;
 
  private:
   int create_tables();
@@ -119,6 +128,17 @@ class Worker {
   int compile_sampled_dev(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
                           const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
                           uint32_t R, uint32_t NNZ, int keep);
+  xf_cross *cross_ = nullptr;  // cross=SPEC: the stage, created with the tables
+  int check_cross() const;     // the refusals of cross, before any rendezvous
+  int create_cross();
+  // device arrays: the cross, when on, then admission, when on, then the _dev compile
+  int compile_staged_dev(xf_sbatch **b, int update, const uint64_t *d_keys, const int32_t *d_fgid,
+                         const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
+                         uint32_t R, uint32_t NNZ, int keep);
+  // ... rows [start, end) of host arrays, uploaded by the cross
+  int compile_crossed(xf_sbatch **b, int update, const uint64_t *rowptr, const uint64_t *keys,
+                      const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
+                      size_t end, int keep);
   // filter a block (host arrays and a row slice / device arrays), then the matching _dev compile
   int compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr, const uint64_t *keys,
                        const int32_t *fgid, const float *vals, const int32_t *labels,
