@@ -947,6 +947,12 @@ int xf_workspace_neg_weight(xf_workspace *ws, float weight);
 /* launches of the separate weight kernel since the library was loaded: the LR steps on cells form
  * the weighted loss in the kernel that forms the loss and make none */
 uint64_t xf_weigh_negatives_launches(void);
+/* launches of the LR gradient (+ Push) kernels since the library was loaded, per kind — which
+ * kernel a step chose is otherwise invisible (read-only, for tests): out[0] k_lr_grad_dense with
+ * byte-masked stores, [1] k_lr_grad_dense with whole-line stores, [2] k_lr_grad_dense deriving
+ * the old weight from (n, z) (each of those also counted in [0] or [1]), [3] the one-source
+ * k_lr_grad_cells, [4] k_lr_grad_split_finish.  Host-side counters: nothing runs on the device. */
+void xf_lr_grad_launches(uint64_t out[5]);
 /* the kernel that forms the LR cells steps' losses, on partial row sums the caller holds (device
  * arrays): d_partial[(v * G + g) * W + i] is workgroup g's share of row v * W + i; loss[r] =
  * sigmoid(fp32(sum over g)) - label, weighted as above, pctr[r] the sigmoid (either may be NULL).

@@ -278,6 +278,28 @@ def cells_raw():
     return [synth(rng, 40000, 30, 120000, 1.2 if i % 2 else None, True) for i in range(3)]
 
 
+def cells_raw_unsplit():
+    """three windows whose chunks all stay whole (40000 rows of 0 to 12 nonzeros over 100 000
+    uniform keys: about 5 000 entries per chunk of 2048 state rows, kSliceMax is 8192).  One split
+    chunk sends a whole minibatch to k_lr_grad_cells, and every chunk of cells_raw() is split: this
+    is the stream on which the knobs reach k_lr_grad_dense (tests/test_cells_edges_cpu.py counts
+    both)."""
+    rng = np.random.RandomState(12)
+    return [synth(rng, 40000, 6, 100000, None, True) for _ in range(2)]
+
+
+def old_weight_raw():
+    """the stream of the old-weight tests (test_gpu_cells.py, test_gpu_hyper.py): split chunks"""
+    rng = np.random.RandomState(23)
+    return [synth(rng, 6000, 40, 30000, 1.2 if i else None, True) for i in range(2)]
+
+
+def old_weight_raw_unsplit():
+    """the same rows over 100 000 uniform keys: no chunk is split"""
+    rng = np.random.RandomState(23)
+    return [synth(rng, 6000, 40, 100000, None, True) for _ in range(2)]
+
+
 def cells_oracle(raw, phases, track=None):
     """O.lr_update in sum_mode(1) over CELLS_STEPS steps; phases: [hyper] or [hyper, hyper after
     SWITCH] -> the store"""
@@ -288,10 +310,10 @@ def cells_oracle(raw, phases, track=None):
         if i == SWITCH and len(phases) > 1:
             phases[1].to_store(s)
         with O.sum_mode(1):
-            O.lr_update(s, obs[i % 3])
+            O.lr_update(s, obs[i % len(obs)])
         if track is not None:
             keys, w = s.export()[:2]
-            at = np.isin(keys, obs[i % 3].ukeys)
+            at = np.isin(keys, obs[i % len(obs)].ukeys)
             track.note(i, keys, w, at)
     return s
 

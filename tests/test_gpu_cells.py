@@ -10,6 +10,7 @@ import pytest
 from oracle import pyoracle as O
 from xflow_amd import capi
 
+from . import _hyper_cases as HC
 from .test_gpu_parity import close, near_state, same, synth, RTOL
 
 pytestmark = pytest.mark.gpu
@@ -66,15 +67,31 @@ def test_local_batches_match_the_oracle(R, nnz, nkeys, zipf, ragged, cap):
         same(capi.lr_predict(t, bs[1], ws), obs[1].lr_loss(s.pull(obs[1].ukeys))[1])
 
 
+_UNSPLIT = []
+
+
+def _unsplit():
+    if not _UNSPLIT:
+        _UNSPLIT.extend(HC.cells_raw_unsplit())
+    return _UNSPLIT
+
+
 @pytest.mark.parametrize("path", [("lr_gradient", 2), ("lr_gradient", 3), ("lr_gradient", 1),
                                   ("old_weight", 2)])
 @pytest.mark.parametrize("opt", ["ftrl", "sgd"])
 def test_every_variant_of_the_gradient_kernel_gives_the_oracle_table(path, opt):
-    """k_lr_grad_dense (the steady-state gradient + Push: one fp32 division for sum / R) with
-    byte-masked and with whole-line stores (lr_gradient = 2 / 3: the shape picks one), the general
-    kernel alone (lr_gradient = 1), and the old weights derived wherever the table vouches for them
-    (old_weight = 2): three windows, split and unsplit chunks side by side (power law), holes and
-    an arrival segment after the defrag — the table bit for bit the exact-sum oracle's each time.
+    """The knobs of the gradient + Push on two streams of three windows, the table bit for bit the
+    exact-sum oracle's each time.
+    The first (power law: split and unsplit chunks side by side, holes and an arrival segment
+    after the defrag) has split chunks in every minibatch, and one split chunk sends the whole
+    minibatch to k_lr_grad_cells: there the knobs exercise the general kernel and the finish
+    kernel (lr_gradient = 1 / 2 / 3 all run them; old_weight = 2: apply_key derives w); only the
+    arrival segments of the steps that bring new keys (a few chunks, none split) run dense.
+    The second (HC.cells_raw_unsplit: no chunk split; tests/test_cells_edges_cpu.py counts both)
+    reaches k_lr_grad_dense (the steady-state kernel: one fp32 division for sum / R) with
+    byte-masked and with whole-line stores (lr_gradient = 2 / 3: the shape picks whole lines), the
+    general kernel alone (lr_gradient = 1), and the old weights derived wherever the table vouches
+    for them (old_weight = 2) — asserted from the launch counters (capi.lr_grad_launches).
     (The measured-and-dropped variants of the kernel live behind -DXF_EXPERIMENTS.)"""
     rng = np.random.RandomState(11)
     oo, go = (O.OPT_FTRL, capi.OPT_FTRL) if opt == "ftrl" else (O.OPT_SGD, capi.OPT_SGD)
@@ -84,6 +101,7 @@ def test_every_variant_of_the_gradient_kernel_gives_the_oracle_table(path, opt):
     obs = [O.Batch(*x) for x in raw]
     capi.tune(*path)
     try:
+        n0 = capi.lr_grad_launches()
         for i in range(4):
             b = capi.LocalBatch(t, *raw[i % 3], retain_keys=False)
             if i == 1:
@@ -95,6 +113,47 @@ def test_every_variant_of_the_gradient_kernel_gives_the_oracle_table(path, opt):
             del b
             if i == 1:
                 t.defrag()
+        n = capi.lr_grad_launches()
+        d = {k: n[k] - n0[k] for k in n}
+        print("split stream", path, opt, d)
+        # four steps, each with split chunks in the segment over the rows the table held: the
+        # general kernel and the finish kernel once a step.  Steps 1 and 2 bring new keys: a second
+        # segment over the arrival rows, a few chunks and none of them split, which runs dense
+        # (under lr_gradient = 1 the general kernel takes it too)
+        forced = path == ("lr_gradient", 1)
+        assert (d["cells"], d["split_finish"]) == (6 if forced else 4, 4), d
+        assert d["dense_masked"] + d["dense_full"] == (0 if forced else 2), d
+        for a, e in zip(t.export(), s.export()):
+            same(a, e)
+        # the stream without a split chunk: the variant the knob names runs, and no other
+        t, s = capi.Table(go, 1, capacity=1 << 19), O.Store(oo, 1)
+        obs = [O.Batch(*x) for x in _unsplit()]
+        n0 = capi.lr_grad_launches()
+        for i in range(3):
+            b = capi.LocalBatch(t, *_unsplit()[i % 2], retain_keys=False)
+            info = b.cells_info()
+            assert info["nsplit_chunks"] == 0 and info["nwin"] == 3, info
+            with O.sum_mode(1):
+                O.lr_update(s, obs[i % 2])
+            capi.lr_step(t, b, ws)
+            t.check()
+            del b
+            if i == 1:
+                t.defrag()
+        n = capi.lr_grad_launches()
+        d = {k: n[k] - n0[k] for k in n}
+        print("unsplit stream", path, opt, d)
+        # three steps and the arrival segment of step 1: four launches, one kernel each
+        if path == ("lr_gradient", 1):
+            assert (d["cells"], d["dense_masked"], d["dense_full"]) == (4, 0, 0), d
+        elif path[0] == "lr_gradient":
+            one, other = (("dense_masked", "dense_full") if path[1] == 2 else
+                          ("dense_full", "dense_masked"))
+            assert (d[one], d[other], d["cells"]) == (4, 0, 0), d
+        else:       # old_weight = 2: the store variant a segment's shape picks, w derived in each
+            assert (d["dense_masked"], d["dense_full"], d["cells"]) == (0, 4, 0), d
+            assert d["dense_derived"] == (4 if opt == "ftrl" else 0), d
+        assert d["split_finish"] == 0, d
     finally:
         capi.tune(path[0], 0)
     for a, e in zip(t.export(), s.export()):
@@ -239,10 +298,36 @@ def test_the_old_weight_is_derived_from_n_and_z_only_while_that_is_the_stored_we
     ends it — the next step of a key uses the STORED w (ftrl.h:63), as the oracle does.  Dense
     kernel, general kernel (lr_gradient = 1), and the kernels made to read w throughout
     (old_weight = 1): the
-    oracle's table bit for bit in every phase."""
-    rng = np.random.RandomState(23)
+    oracle's table bit for bit in every phase.
+    Two streams.  HC.old_weight_raw() splits chunks in every minibatch, so every step of it runs
+    k_lr_grad_cells and the finish kernel whatever the knob (apply_key's and the finish kernel's
+    old weight; the dense kernel gets the arrival segments alone);
+    HC.old_weight_raw_unsplit() splits none: its steps run k_lr_grad_dense unless
+    lr_gradient = 1 — read from the launch counters.  (It touches the table densely, so the dense
+    kernel reads w there: its derivation is tests/test_gpu_grad_dense.py's.)"""
+    for raw, split in ((HC.old_weight_raw(), True), (HC.old_weight_raw_unsplit(), False)):
+        n0 = capi.lr_grad_launches()
+        _old_weight_phases(raw, path)
+        n = capi.lr_grad_launches()
+        d = {k: n[k] - n0[k] for k in n}
+        dense = d["dense_masked"] + d["dense_full"]
+        print("split" if split else "unsplit", path, d)
+        # the phases make 12 steps; three of them have a second segment with entries, over rows
+        # that arrived since the table was last put in order: 15 launches of a gradient kernel
+        forced = path == ("lr_gradient", 1)
+        if split:       # (the arrival segments have no split chunk: dense unless forced)
+            assert (d["cells"], dense, d["split_finish"]) == (15 if forced else 12,
+                                                              0 if forced else 3, 12), d
+        elif forced:
+            assert (d["cells"], dense, d["split_finish"]) == (15, 0, 0), d
+        else:
+            assert (d["cells"], dense, d["split_finish"]) == (0, 15, 0), d
+            if path == ("old_weight", 1):
+                assert d["dense_derived"] == 0, d
+
+
+def _old_weight_phases(raw, path):
     ws = capi.Workspace()
-    raw = [synth(rng, 6000, 40, 30000, 1.2 if i else None, True) for i in range(2)]
     obs = [O.Batch(*x) for x in raw]
     capi.tune(*path)
     try:

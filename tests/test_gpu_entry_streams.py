@@ -40,21 +40,23 @@ def same(a, b, what=""):
             what, i.size, a.size, [(j, a.ravel()[j], b.ravel()[j]) for j in i[:6]]))
 
 
-_POOL = []
+NKEYS_UNSPLIT = 40000      # 1 to 3 nonzeros a row over these: no chunk of 2048 keys is split
+CAP = {NKEYS: 1 << 15, NKEYS_UNSPLIT: 1 << 17}
+_POOL = {}
 
 
-def pool():
-    if not _POOL:
-        _POOL.append(capi.hash_decimal_range(0, NKEYS))
-    return _POOL[0]
+def pool(n=NKEYS):
+    if n not in _POOL:
+        _POOL[n] = capi.hash_decimal_range(0, n)
+    return _POOL[n]
 
 
-def mb(rng, lens, lo=0, hi=NKEYS):
-    """a minibatch with these row lengths, keys uniform over pool()[lo:hi], both labels present
-    where there are two rows"""
+def mb(rng, lens, lo=0, hi=NKEYS, nkeys=NKEYS):
+    """a minibatch with these row lengths, keys uniform over pool(nkeys)[lo:hi], both labels
+    present where there are two rows"""
     lens = np.asarray(lens, np.int64)
     rowptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
-    keys = pool()[rng.randint(lo, hi, size=int(lens.sum()))]
+    keys = pool(nkeys)[rng.randint(lo, hi, size=int(lens.sum()))]
     labels = rng.randint(0, 2, size=len(lens)).astype(np.int32)
     if len(lens) > 1:
         labels[0], labels[1] = 0, 1
@@ -74,15 +76,16 @@ def reference(raws, opt, w=1.0, settle=None):
     return losses, s.export()
 
 
-def gpu_run(raws, opt, form, es, w=1.0, settle=None, tune=None):
+def gpu_run(raws, opt, form, es, w=1.0, settle=None, tune=None, cap=1 << 15):
     """STEPS steps on a fresh table under entry_streams = es -> losses, table, cells_info per step,
-    launches of the separate weight kernel during the steps"""
+    launches of the separate weight kernel during the steps, launches of the gradient kernels by
+    kind (capi.lr_grad_launches)"""
     assert form in ("kept", "one-shot", "one-call kept")
     capi.tune("entry_streams", es)
     if tune:
         capi.tune(*tune)
     try:
-        t = capi.Table(_opt(opt)[0], 1, capacity=1 << 15)
+        t = capi.Table(_opt(opt)[0], 1, capacity=cap)
         ws = capi.Workspace()
         ws.neg_weight(w)
         if settle is not None:
@@ -91,6 +94,7 @@ def gpu_run(raws, opt, form, es, w=1.0, settle=None, tune=None):
         kept = [capi.LocalBatch(t, *r) for r in raws] if form == "kept" else None
         losses, infos = [], []
         n0 = capi.lib().xf_weigh_negatives_launches()
+        g0 = capi.lr_grad_launches()
         for i in range(STEPS):
             if kept:
                 b = kept[i % len(raws)]
@@ -101,18 +105,25 @@ def gpu_run(raws, opt, form, es, w=1.0, settle=None, tune=None):
             losses.append(ws.fetch_loss(b.R) if b.R else np.zeros(0, np.float32))
             infos.append(b.cells_info())
         launches = capi.lib().xf_weigh_negatives_launches() - n0
+        g1 = capi.lr_grad_launches()
         t.check()
-        return losses, t.export(), infos, launches
+        return losses, t.export(), infos, launches, {k: g1[k] - g0[k] for k in g1}
     finally:
         capi.tune("entry_streams", 0)
         if tune:
             capi.tune(tune[0], 0)
 
 
-def check(raws, opt, form, ref, w=1.0, settle=None, tune=None):
-    """entry_streams 0 and 1 against the oracle and against each other -> cells_info per step"""
-    got = {es: gpu_run(raws, opt, form, es, w, settle, tune) for es in (0, 1)}
-    for es, (losses, table, _, launches) in got.items():
+def check(raws, opt, form, ref, w=1.0, settle=None, tune=None, kernel=None, cap=1 << 15):
+    """entry_streams 0 and 1 against the oracle and against each other -> cells_info per step.
+    kernel: (launches of k_lr_grad_cells, of k_lr_grad_split_finish, of k_lr_grad_dense in either
+    store variant) that each run's STEPS steps must have made, from capi.lr_grad_launches"""
+    got = {es: gpu_run(raws, opt, form, es, w, settle, tune, cap) for es in (0, 1)}
+    for es, (losses, table, _, launches, grad) in got.items():
+        dense = grad["dense_masked"] + grad["dense_full"]
+        print(form, opt, tune, grad)
+        if kernel is not None:
+            assert (grad["cells"], grad["split_finish"], dense) == kernel, (grad, kernel)
         for i, (a, e) in enumerate(zip(losses, ref[0])):
             same(a, e, "entry_streams=%d, %s: loss of step %d" % (es, form, i))
         m = 4 if opt == "ftrl" else 2
@@ -149,13 +160,13 @@ def test_stream_ends(nnz, opt):
 _REF = {}
 
 
-def ref_windows(R, opt, seed=0):
+def ref_windows(R, opt, seed=0, nkeys=NKEYS):
     """computed once per shape and optimizer, shared by the forms, left unchanged"""
-    if (R, opt, seed) not in _REF:
+    if (R, opt, seed, nkeys) not in _REF:
         rng = np.random.RandomState(R + seed)
-        raws = [mb(rng, rng.randint(1, 4, size=R)) for _ in range(2)]
-        _REF[(R, opt, seed)] = (raws, reference(raws, opt))
-    return _REF[(R, opt, seed)]
+        raws = [mb(rng, rng.randint(1, 4, size=R), 0, nkeys, nkeys) for _ in range(2)]
+        _REF[(R, opt, seed, nkeys)] = (raws, reference(raws, opt))
+    return _REF[(R, opt, seed, nkeys)]
 
 
 @pytest.mark.parametrize("opt", ["ftrl", "sgd"])
@@ -164,19 +175,36 @@ def ref_windows(R, opt, seed=0):
 def test_windows(R, form, opt):
     """one, two and three row windows (kWinMax = 17408; the rows are dealt out evenly: 17409 rows
     are windows of 8705 and 8704), 1-3 nonzeros per row over 5 000 keys; kept: the forward over
-    the key-sorted copy and the fetch; one-shot: the forward over `entries`, no fetch"""
-    raws, ref = ref_windows(R, opt)
-    info = check(raws, opt, form, ref)
-    assert info[-1]["nwin"] == (R + 17407) // 17408
-    assert info[-1]["G"] == {1: 256, 2: 128, 3: 80}[info[-1]["nwin"]]
+    the key-sorted copy and the fetch; one-shot: the forward over `entries`, no fetch.
+    Over 5 000 keys (three chunks) two or three chunks of every minibatch are split, which sends
+    it to k_lr_grad_cells and the finish kernel; the same rows over 40 000 keys split none and run
+    k_lr_grad_dense behind the fetch — both asserted from the launch counters
+    (tests/test_cells_edges_cpu.py counts the chunks of both)"""
+    for nkeys, seed in ((NKEYS, 0), (NKEYS_UNSPLIT, 50)):
+        raws, ref = ref_windows(R, opt, seed, nkeys)
+        # three steps over two minibatches; the second has a segment of its own over the keys the
+        # first did not hold (an arrival segment, never split: dense) — unless the first held them
+        # all: 34817 rows draw every one of the 5 000 keys
+        new = len(np.setdiff1d(raws[1][1], raws[0][1])) > 0
+        assert new == (nkeys == NKEYS_UNSPLIT or R < 34817)
+        kernel = (3, 3, int(new)) if nkeys == NKEYS else (0, 0, 3 + int(new))
+        info = check(raws, opt, form, ref, kernel=kernel, cap=CAP[nkeys])
+        assert info[-1]["nwin"] == (R + 17407) // 17408
+        assert info[-1]["G"] == {1: 256, 2: 128, 3: 80}[info[-1]["nwin"]]
+        assert all((i["nsplit_chunks"] > 0) == (nkeys == NKEYS) for i in info), info
 
 
 @pytest.mark.parametrize("opt", ["ftrl", "sgd"])
 def test_the_general_gradient_kernel(opt):
     """lr_gradient = 1: the one-source k_lr_grad_cells behind the fetch where the dense kernel
-    would run"""
-    raws, ref = ref_windows(17409, opt)
-    check(raws, opt, "kept", ref, tune=("lr_gradient", 1))
+    would run — on the stream over 40 000 keys, which has no split chunk (test_windows: it runs
+    dense without the knob), and on the one over 5 000, which goes to k_lr_grad_cells anyway"""
+    for nkeys, seed in ((NKEYS_UNSPLIT, 50), (NKEYS, 0)):
+        raws, ref = ref_windows(17409, opt, seed, nkeys)
+        # (three steps and the second minibatch's arrival segment, all through the general kernel)
+        info = check(raws, opt, "kept", ref, tune=("lr_gradient", 1),
+                     kernel=(4, 3 if nkeys == NKEYS else 0, 0), cap=CAP[nkeys])
+        assert all((i["nsplit_chunks"] == 0) == (nkeys == NKEYS_UNSPLIT) for i in info), info
 
 
 @pytest.mark.parametrize("opt", ["ftrl", "sgd"])

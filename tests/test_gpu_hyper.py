@@ -278,14 +278,22 @@ def cells():
     raw = HC.cells_raw()
     known = {}
 
-    def table(*phases):
-        if phases not in known:
-            known[phases] = HC.cells_oracle(raw, list(phases)).export()
-        return known[phases]
+    def table(*phases, **kw):
+        """(unsplit=True: of HC.cells_raw_unsplit(), the stream that reaches k_lr_grad_dense)"""
+        key = phases + (kw.get("unsplit", False),)
+        if key not in known:
+            known[key] = HC.cells_oracle(unsplit() if key[-1] else raw, list(phases)).export()
+        return known[key]
+
+    def unsplit():
+        if "raw" not in known:
+            known["raw"] = HC.cells_raw_unsplit()
+        return known["raw"]
+    table.unsplit = unsplit
     return raw, table
 
 
-def _cells_steps(raw, phases, path, precompiled=False):
+def _cells_steps(raw, phases, path, precompiled=False, split=True):
     t = capi.Table(_go(phases[0].opt), 1, capacity=1 << 19, **phases[0].kw())
     _derived_as_it_should(t, phases[0])
     ws = capi.Workspace()
@@ -296,9 +304,11 @@ def _cells_steps(raw, phases, path, precompiled=False):
             if i == HC.SWITCH and len(phases) > 1:
                 phases[1].to_table(t)
                 assert not t.w_derived()
-            b = pre[i % 3] if pre else capi.LocalBatch(t, *raw[i % 3], retain_keys=False)
-            if i == 1:
-                assert b.cells_info()["nsplit_chunks"] > 0 and b.cells_info()["nwin"] == 3
+            b = pre[i % len(raw)] if pre else capi.LocalBatch(t, *raw[i % len(raw)],
+                                                              retain_keys=False)
+            if i == 1 or not split:
+                assert (b.cells_info()["nsplit_chunks"] > 0) == split
+                assert b.cells_info()["nwin"] == 3
             capi.lr_step(t, b, ws)
             t.check()
             del b
@@ -314,10 +324,39 @@ def _cells_steps(raw, phases, path, precompiled=False):
 def test_every_variant_of_the_gradient_kernel_under_every_set(cells, hyper, path):
     """tests/test_gpu_cells.py's three-window power-law shape (split chunks, a defrag after step
     1), four steps: the table bit for bit the exact-sum oracle's under NO_L1, SPARSE, NEG_L1 (the
-    kernels may not derive w: a fresh row's w is not ftrl_w_of(0, 0) there) and SGD lr 0.2"""
+    kernels may not derive w: a fresh row's w is not ftrl_w_of(0, 0) there) and SGD lr 0.2.
+    Every minibatch of that stream has split chunks, so all four knobs run k_lr_grad_cells and the
+    finish kernel on it (and k_lr_grad_dense on the two small arrival segments only); the same
+    steps over HC.cells_raw_unsplit() (three windows, no chunk split) run what the knob names — k_lr_grad_dense with byte-masked (lr_gradient = 2) or
+    whole-line stores (3, and old_weight = 2 by the shape), the general kernel alone (1) — read
+    from the launch counters."""
     raw, table = cells
+    n0 = capi.lr_grad_launches()
     t = _cells_steps(raw, [hyper], path)
     _table_same(t, table(hyper), "table")
+    n1 = capi.lr_grad_launches()
+    t = _cells_steps(table.unsplit(), [hyper], path, split=False)
+    _table_same(t, table(hyper, unsplit=True), "table of the unsplit stream")
+    n2 = capi.lr_grad_launches()
+    d1, d2 = ({k: b[k] - a[k] for k in a} for a, b in ((n0, n1), (n1, n2)))
+    print(hyper, path, d1, d2)
+    # the split stream: four steps, the general kernel and the finish kernel once each over the
+    # rows the table held; steps 1 and 2 bring new keys, and their arrival segments (a few chunks,
+    # none split) run dense — or the general kernel again under lr_gradient = 1
+    forced = path == ("lr_gradient", 1)
+    assert (d1["cells"], d1["split_finish"]) == (6 if forced else 4, 4), d1
+    assert d1["dense_masked"] + d1["dense_full"] == (0 if forced else 2), d1
+    # the unsplit stream: four steps and the arrival segment of step 1, five launches of the kernel
+    # the knob names
+    want = {("lr_gradient", 1): "cells", ("lr_gradient", 2): "dense_masked"}.get(path, "dense_full")
+    assert d2["split_finish"] == 0, d2
+    if path[0] == "lr_gradient":
+        assert all(d2[k] == (5 if k == want else 0)
+                   for k in ("dense_masked", "dense_full", "cells")), d2
+    else:
+        assert (d2["dense_masked"], d2["dense_full"], d2["cells"]) == (0, 5, 0), d2
+        derives = hyper.opt == "ftrl" and hyper.lambda1 >= 0      # (the table vouches for w)
+        assert d2["dense_derived"] == (5 if derives else 0), d2
 
 
 @pytest.mark.parametrize("hyper", [HC.A, HC.NO_L1], ids=repr)
@@ -326,9 +365,20 @@ def test_import_vouches_for_w_under_the_tables_own_set(hyper):
     model the oracle made under THAT set keeps w_derived() true, one made under the defaults turns
     it false (its w is not ftrl_w_of(n, z) under this table's values) — and the cells steps that
     follow equal the oracle's either way, deriving w in the first case and reading it in the
-    second"""
-    rng = np.random.RandomState(23)
-    raw = [HC.synth(rng, 6000, 40, 30000, 1.2 if i else None, True) for i in range(2)]
+    second.  On HC.old_weight_raw() (split chunks: k_lr_grad_cells and the finish kernel) and on
+    HC.old_weight_raw_unsplit() (none: k_lr_grad_dense), by the launch counters."""
+    for raw, split in ((HC.old_weight_raw(), True), (HC.old_weight_raw_unsplit(), False)):
+        n0 = capi.lr_grad_launches()
+        _import_vouches(hyper, raw)
+        n1 = capi.lr_grad_launches()
+        d = {k: n1[k] - n0[k] for k in n0}
+        print(hyper, "split" if split else "unsplit", d)
+        # two models, two steps each on a table that holds every key: one segment a step
+        dense = d["dense_masked"] + d["dense_full"]
+        assert (d["cells"], d["split_finish"], dense) == ((4, 4, 0) if split else (0, 0, 4)), d
+
+
+def _import_vouches(hyper, raw):
     obs = [O.Batch(*x) for x in raw]
     ws = capi.Workspace()
     for made_under, derived in ((hyper, True), (HC.FTRL_DEFAULT, False)):

@@ -289,6 +289,7 @@ SIGNATURES = {
     "xf_negsample_stats": (C.c_int, [vp, u64p, u64p, u64p, u64p]),
     "xf_workspace_neg_weight": (C.c_int, [vp, C.c_float]),
     "xf_weigh_negatives_launches": (C.c_uint64, []),
+    "xf_lr_grad_launches": (None, [u64p]),
     "xf_cells_finalize_rows": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                          vp, vp, vp]),
     "xf_sharded_set_neg_weight": (C.c_int, [vp, C.c_float]),
@@ -1176,6 +1177,18 @@ def cells_info(batch):
     check(lib().xf_batch_cells_info(batch.h, out))
     names = ["W", "nwin", "nchunk", "G", "nitems", "segments", "nsplit_chunks", "M"]
     return dict(zip(names, list(out)))
+
+
+LR_GRAD_KINDS = ("dense_masked", "dense_full", "dense_derived", "cells", "split_finish")
+
+
+def lr_grad_launches():
+    """launches of the LR gradient kernels so far, by kind (xf_lr_grad_launches): k_lr_grad_dense
+    with byte-masked / whole-line stores, those of them that derived the old weight, the
+    one-source k_lr_grad_cells, k_lr_grad_split_finish.  Subtract two readings."""
+    out = np.zeros(len(LR_GRAD_KINDS), np.uint64)
+    lib().xf_lr_grad_launches(_p(out, u64p))
+    return dict(zip(LR_GRAD_KINDS, (int(x) for x in out)))
 
 
 def div_by_const_probe(x, d, exact=False):

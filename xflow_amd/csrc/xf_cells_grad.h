@@ -120,6 +120,17 @@ constexpr uint32_t kSparseKeys = 2 * 256;  // touched keys of a chunk that are s
 }  // namespace
 
 namespace xf {
+// which gradient kernel an LR step launched (xf_lr_grad_launches: the tests' way to see the choice
+// launch_grad made).  Host-side relaxed counters, bumped where the launch is written.
+enum {
+  kLaunchDenseMasked = 0,  // k_lr_grad_dense, var == 0
+  kLaunchDenseFull,        // k_lr_grad_dense, var == kDenseFullStore
+  kLaunchDenseDerived,     // k_lr_grad_dense with Td.w_of_nz (also counted above)
+  kLaunchCellsOne,         // k_lr_grad_cells, one source
+  kLaunchSplitFinish,      // k_lr_grad_split_finish
+  kLaunchKinds
+};
+void lr_grad_count(int kind);
 int cells_launch_split_finish(int opt, const xf_cells *c, const TableDev &T, hipStream_t s);
 }  // namespace xf
 

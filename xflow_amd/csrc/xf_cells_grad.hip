@@ -927,11 +927,14 @@ static int launch_grad(const xf_cells *c, const TableDev &T_, const float *d_los
                        c->item_slice, c->item_dump, d_loss, src->rows_host, c->M, d_g, gsum,
                        gtouched, 1u, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
                        c->nsplit_chunks, src->d_loss_base, c->chunk0, no_skip);
-    if (c->nsplit_chunks)
+    lr_grad_count(kLaunchCellsOne);
+    if (c->nsplit_chunks) {
       hipLaunchKernelGGL((k_lr_grad_split_finish<OPT, MODE>),
                          dim3(c->nsplit_chunks * (kChunk / kBlock)), dim3(kBlock), 0, s, T,
                          c->split_chunk, gsum, gtouched, src->rows_host, c->M, d_g, 1u,
                          (const uint32_t *)nullptr, c->nsplit_chunks, c->chunk0, 0);
+      lr_grad_count(kLaunchSplitFinish);
+    }
     XF_HIP(hipGetLastError());
     return XF_OK;
   }
@@ -1008,6 +1011,7 @@ static int launch_grad(const xf_cells *c, const TableDev &T_, const float *d_los
                        c->item_slice, c->item_dump, d_loss, c->R, c->M, d_g, gsum, gtouched,
                        src->n, src->d_win, src->d_rows, c->nsplit_chunks, src->d_loss_base,
                        c->chunk0, no_skip);
+    lr_grad_count(kLaunchCellsOne);  // (one source, its rows counted on the device)
   } else {
     // one source: the unsplit chunks go to k_lr_grad_dense (gradient + Push, no dense copy of
     // the gradients wanted, few windows), the general kernel keeps the split ones
@@ -1052,13 +1056,16 @@ static int launch_grad(const xf_cells *c, const TableDev &T_, const float *d_los
                          c->item_slice, c->item_dump, d_loss, c->R, c->M, d_g, gsum, gtouched, 1u,
                          (const uint32_t *)nullptr, (const uint32_t *)nullptr, c->nsplit_chunks,
                          (const uint32_t *)nullptr, c->chunk0, no_skip);
+    if (!dense) lr_grad_count(kLaunchCellsOne);
   }
-  if (c->nsplit_chunks)
+  if (c->nsplit_chunks) {
     hipLaunchKernelGGL((k_lr_grad_split_finish<OPT, MODE>),
                        dim3(c->nsplit_chunks * (kChunk / kBlock)), dim3(kBlock), 0, s, T,
                        c->split_chunk, gsum, gtouched, c->R, c->M, d_g, src ? src->n : 1u,
                        src ? src->d_rows : (const uint32_t *)nullptr, c->nsplit_chunks,
                        c->chunk0, src ? 0 : 1);
+    lr_grad_count(kLaunchSplitFinish);
+  }
   XF_HIP(hipGetLastError());
   if (!src) c->split_dirty = false;
   return XF_OK;
@@ -1128,6 +1135,7 @@ int cells_lr_grad_update_sources(const xf_cells *c, const xf_table *t, const flo
 // slices added into c->gsum / c->gtouched (xf_cells_valued.hip); leaves the accumulators zero
 int cells_launch_split_finish(int opt, const xf_cells *c, const TableDev &T, hipStream_t s) {
   if (!c->nsplit_chunks) return XF_OK;
+  lr_grad_count(kLaunchSplitFinish);
   const dim3 grid(c->nsplit_chunks * (kChunk / kBlock)), blk(kBlock);
   if (opt == XF_OPT_FTRL)
     hipLaunchKernelGGL((k_lr_grad_split_finish<XF_OPT_FTRL, 0>), grid, blk, 0, s, T, c->split_chunk,

@@ -5,6 +5,8 @@
 //   LRWorker::calculate_gradient       src/model/lr/lr_worker.cc:100-119
 //   KVWorker::Push -> FTRL / SGD       src/optimizer/ftrl.h:54-74, sgd.h:52 (fused in the same)
 // HBM-bound integer/byte work, no MFMA.
+#include <atomic>
+
 #include "xf_cells_grad.h"
 
 namespace {
@@ -309,7 +311,20 @@ int cells_launch_grad_dense(int opt, int var, const xf_cells *c, const TableDev 
 #undef XF_DENSE
 #undef XF_DENSE_O
   XF_HIP(hipGetLastError());
+  if (var == 0) lr_grad_count(kLaunchDenseMasked);
+  if (var == kDenseFullStore) lr_grad_count(kLaunchDenseFull);
+  if (opt == XF_OPT_FTRL && Td.w_of_nz) lr_grad_count(kLaunchDenseDerived);
   return XF_OK;
 }
 
+static std::atomic<uint64_t> g_lr_grad_launches[kLaunchKinds];
+
+void lr_grad_count(int kind) { g_lr_grad_launches[kind].fetch_add(1, std::memory_order_relaxed); }
+
 }  // namespace xf
+
+extern "C" void xf_lr_grad_launches(uint64_t out[5]) {
+  static_assert(xf::kLaunchKinds == 5, "xf_lr_grad_launches: the header says five");
+  for (int i = 0; i < xf::kLaunchKinds; ++i)
+    out[i] = xf::g_lr_grad_launches[i].load(std::memory_order_relaxed);
+}
