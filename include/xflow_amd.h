@@ -962,6 +962,79 @@ int xf_cells_finalize_rows(const double *d_partial, const int32_t *d_labels, uin
                            void *stream);
 int xf_sharded_set_neg_weight(xf_sharded *st, float weight);
 
+/* ---------------------------------------------------------------- progressive validation */
+/* The loss of every training row under the weights it met BEFORE it was trained on (the FTRL
+ * paper's progressive validation; not in the reference): in the first epoch a held-out metric that
+ * needs no second file, later the training curve.  The device only counts; every floating-point
+ * figure is formed on the host in fp64 from the counts, so the device's result depends on nothing
+ * but the rows' losses and labels and is compared with ==.
+ * Rank.  loss[r] = sigmoid - label as a training step forms it; pos = labels[r] != 0;
+ * q = |loss[r]| is the probability put on the wrong class (p for a negative, fl(1 - p) for a
+ * positive).  SH = 23 - XF_PROGRESS_MANT, C = bits(0.5f) >> SH:
+ *   q <  0.5f: rank = bits(q) >> SH                     (-0.0 ranks as 0)
+ *   q >= 0.5f: rank = 2C - (bits(1.0f - q) >> SH)       (the subtraction is exact; q = 1: 2C)
+ * XF_PROGRESS_RANKS = 2C + 1 ranks, monotone in q, rank(1 - q) = 2C - rank(q) wherever 1 - q is
+ * exact: a positive's SCORE rank is 2C - rank, a negative's is rank, and equal p means equal score
+ * rank.  A row whose loss is NaN or whose q > 1 has rank XF_PROGRESS_RANKS and is counted in
+ * other[pos] alone.  xf_progress_rank is that function as host code, from the one definition the
+ * kernel uses.
+ * Counts.  counts[2][XF_PROGRESS_RANKS] (class 0 = label 0 first; indexed by the rank of q) and
+ * other[2], 64-bit, on the device, summed over as many accumulates as the caller likes.
+ * xf_progress_accumulate_dev: R rows of device arrays, one launch on `stream` (none with R = 0), no
+ * wait.  xf_progress_read: copies the counts out in the order of the stream of the last accumulate,
+ * zeroes them when reset != 0, and waits for that stream — the one wait.  xf_progress_launches: the
+ * accumulate launches since the library was loaded.  xf_progress_shape: {rows of a workgroup, slots
+ * and probes of its LDS table} of the kernel, for the tests that reach its overflow path.
+ * Summary (host, no GPU): a negative row weighs w = neg_weight (>= 1, finite), a positive 1, so
+ * the figures estimate the unsampled stream under negative subsampling.  A bucket's representative
+ * m is the midpoint of its fp32 bounds — of q below C, of 1 - q above; 0.5 at C; 2^-25 in the
+ * saturated bucket 2C — its row term -log1p(-m) below C and -ln(m) from C on.  Sums run per class
+ * by ascending rank, sum += (double)count * term.
+ *   rows_pos = P, rows_neg = w N, saturated, other (weighted rows)
+ *   logloss = (sum_pos + w sum_neg) / (P + w N), natural log; logloss_bound = -ln(1 - 2^-(MANT+1))
+ *     bounds its distance from the fp64 mean of -log1p(-q) over the rows outside bucket 2C
+ *   auc = fl(U2) / fl(2 P N), U2 = sum over score ranks b of pos_b (2 neg_below_b + neg_b) in exact
+ *     integers; auc_slack = fl(sum_b pos_b neg_b) / fl(2 P N): the exact tie-aware AUC of the rows'
+ *     p lies within auc +- auc_slack.  w cancels.
+ *   ctr = P / (P + w N); pctr = the weighted mean of the buckets' representative p
+ * One class only: auc is NaN and nothing else is.  No rows: every mean is NaN; the call succeeds.
+ * Tap.  xf_workspace_progress(ws, p) attaches a progress to a workspace (NULL: off, the default;
+ * the caller keeps p alive).  Every training step then accumulates its losses after the forward has
+ * written them and before the negatives' weight touches them — the places the weight names above.
+ * The LR steps on cells with w != 1 then finalize with weight 1, accumulate, and launch the weight
+ * kernel (same expression, same bits); at w = 1 they finalize as before and accumulate.  Predict
+ * never accumulates.  With nothing attached a step is launch for launch what it was; with one
+ * attached its tables and outputs are bit for bit the same.
+ * xf_sharded_progress(st, enable): the trainer owns one (created at 1, freed at 0).  XF_EINVAL on a
+ * several-rank trainer on XF_SCHEDULE_OWNER / _OWNER_STALE1 (the loss is formed inside the owners'
+ * finalize kernels), and xf_sharded_set_schedule to one of those two while it is on.
+ * xf_sharded_progress_read: flushes, then reads this rank's counts; merged != 0: COLLECTIVE, the
+ * ranks' counts summed (xf_group_allgather_host), the sum on every rank.
+ * xf_sharded_last_loss: the losses (weighted) the last step of minibatch b left, R of them, for the
+ * tests (flushes). */
+#define XF_PROGRESS_MANT 10
+#define XF_PROGRESS_RANKS 258049u
+typedef struct xf_progress xf_progress;
+typedef struct {
+  double rows_pos, rows_neg, saturated, other;
+  double logloss, logloss_bound, auc, auc_slack, ctr, pctr;
+} xf_progress_metrics;
+int xf_progress_create(xf_progress **out);
+int xf_progress_destroy(xf_progress *p);
+uint32_t xf_progress_rank(float loss);
+int xf_progress_accumulate_dev(xf_progress *p, const float *d_loss, const int32_t *d_labels,
+                               uint32_t R, void *stream);
+int xf_progress_read(xf_progress *p, uint64_t *counts, uint64_t *other, int reset);
+uint64_t xf_progress_launches(void);
+void xf_progress_shape(uint32_t out[3]);
+int xf_progress_summary(const uint64_t *counts, const uint64_t *other, float neg_weight,
+                        xf_progress_metrics *out);
+int xf_workspace_progress(xf_workspace *ws, xf_progress *p);
+int xf_sharded_progress(xf_sharded *st, int enable);
+int xf_sharded_progress_read(xf_sharded *st, uint64_t *counts, uint64_t *other, int reset,
+                             int merged);
+int xf_sharded_last_loss(xf_sharded *st, xf_sbatch *b, float *loss, size_t R);
+
 /* ---------------------------------------------------------------- feature crosses      */
 /* Crossed features as a GPU stage ahead of the key build (not in the reference).  Like admission
  * and negative subsampling it works on a minibatch's CSR arrays and its result goes to any *_dev
@@ -1083,7 +1156,16 @@ int XFDestroy(void **h);
  *        spec is not saved with the model: predict needs the same cross=)
  *        cross_fgid_base(N, default 0: the crossed nonzeros' fgids are N + the pair's index; read
  *        only with fm_mode=field_aware, where N + pairs <= fields).  XFGetMetric: cross_in
- *        cross_out (nonzeros into and out of the stage) */
+ *        cross_out (nonzeros into and out of the stage)
+ *        progress(0|1, default 0: progressive validation, xf_progress_* — every training step
+ *        counts its rows' losses under the weights it is about to change, with no host wait inside
+ *        an epoch; at the end of every epoch, replayed ones included, the counts are read, summed
+ *        over the workers and reset, and rank 0 prints one line "progress epoch E: rows = ...
+ *        logloss = ... (+- bound) auc = ... (+- slack) ctr = ... pctr = ..." and, when nonzero,
+ *        saturated / other; a negative weighs 1 / neg_keep; not with schedule=owner / owner_stale1
+ *        on several workers).  XFGetMetric: progress_logloss progress_auc progress_auc_slack
+ *        progress_ctr progress_pctr progress_rows (the last epoch) progress_logloss_first
+ *        progress_auc_first (epoch 0: the held-out figure) */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

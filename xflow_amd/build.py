@@ -17,7 +17,8 @@ CLI = os.path.join(LIBDIR, "xflow_lr")
 LIB_SOURCES = ["xf_table.hip", "xf_model.hip", "xf_calib.hip", "xf_batch_dev.hip", "xf_cells_build.hip", "xf_cells_fwd.hip", "xf_cells_grad.hip", "xf_cells_grad_dense.hip", "xf_cells_valued.hip", "xf_keybuild.hip", "xf_io.cc", "xf_batch.cc", "xf_metrics.cc",
                "xf_worker.cc", "xf_group.cc", "xf_modelfile.cc", "xf_sharded.hip", "xf_ingest.hip",
                "xf_fm_canonical.hip", "xf_valued.hip", "xf_ffm.hip", "xf_admit.hip",
-               "xf_admit_host.cc", "xf_negsample.hip", "xf_cross.hip", "xf_cross_host.cc"]
+               "xf_admit_host.cc", "xf_negsample.hip", "xf_cross.hip", "xf_cross_host.cc",
+               "xf_progress.hip", "xf_progress_host.cc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-result", "-Wno-unused-value",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

@@ -293,6 +293,18 @@ SIGNATURES = {
     "xf_cells_finalize_rows": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                          vp, vp, vp]),
     "xf_sharded_set_neg_weight": (C.c_int, [vp, C.c_float]),
+    "xf_progress_create": (C.c_int, [C.POINTER(vp)]),
+    "xf_progress_destroy": (C.c_int, [vp]),
+    "xf_progress_rank": (C.c_uint32, [C.c_float]),
+    "xf_progress_accumulate_dev": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+    "xf_progress_read": (C.c_int, [vp, u64p, u64p, C.c_int]),
+    "xf_progress_launches": (C.c_uint64, []),
+    "xf_progress_shape": (None, [C.POINTER(C.c_uint32)]),
+    "xf_progress_summary": (C.c_int, [u64p, u64p, C.c_float, vp]),
+    "xf_workspace_progress": (C.c_int, [vp, vp]),
+    "xf_sharded_progress": (C.c_int, [vp, C.c_int]),
+    "xf_sharded_progress_read": (C.c_int, [vp, u64p, u64p, C.c_int, C.c_int]),
+    "xf_sharded_last_loss": (C.c_int, [vp, vp, f32p, C.c_size_t]),
     "xf_cross_key": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "xf_cross_parse": (C.c_int, [C.c_char_p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
     "xf_cross_create": (C.c_int, [C.POINTER(vp), i32p, i32p, C.c_int, C.c_int32]),
@@ -844,6 +856,83 @@ def cross_parse(spec):
     return [(int(fa[p]), int(fb[p])) for p in range(n.value)]
 
 
+PROGRESS_MANT = 10
+PROGRESS_CENTER = 0x3f000000 >> (23 - PROGRESS_MANT)
+PROGRESS_RANKS = 2 * PROGRESS_CENTER + 1
+
+
+class ProgressMetrics(C.Structure):
+    _fields_ = [(n, C.c_double) for n in
+                ("rows_pos", "rows_neg", "saturated", "other", "logloss", "logloss_bound", "auc",
+                 "auc_slack", "ctr", "pctr")]
+
+
+def progress_rank(loss):
+    """the rank of a row's loss (xf_progress_rank; host code, the kernel's own definition):
+    0 .. 2C for q = |loss| in [0, 1], PROGRESS_RANKS for NaN and q > 1"""
+    return int(lib().xf_progress_rank(float(np.float32(loss))))
+
+
+def progress_summary(counts, other, neg_weight=1.0):
+    """xf_progress_summary (host code): counts uint64 [2, PROGRESS_RANKS] (class 0 = label 0 first),
+    other uint64 [2]; a dict of the metrics' fields"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    other = np.ascontiguousarray(other, dtype=np.uint64).reshape(-1)
+    assert counts.size == 2 * PROGRESS_RANKS and other.size == 2
+    m = ProgressMetrics()
+    check(lib().xf_progress_summary(_p(counts, u64p), _p(other, u64p), float(neg_weight),
+                                    C.byref(m)))
+    return {n: getattr(m, n) for n, _ in ProgressMetrics._fields_}
+
+
+def progress_launches():
+    return int(lib().xf_progress_launches())
+
+
+def progress_shape():
+    """{rows of a workgroup, slots and probes of its LDS table} of the accumulate kernel"""
+    out = (C.c_uint32 * 3)()
+    lib().xf_progress_shape(out)
+    return dict(zip(("rows", "slots", "probe"), list(out)))
+
+
+class Progress:
+    """Progressive validation (xf_progress_*): counts of the ranks of the training rows' losses,
+    kept on the GPU.  Attach it to a Workspace (Workspace.progress) or feed it device arrays
+    (accumulate); read() is the one stream wait; summary() forms the metrics on the host."""
+
+    rank = staticmethod(progress_rank)
+
+    def __init__(self):
+        require_gpu()
+        self.h = vp()
+        check(lib().xf_progress_create(C.byref(self.h)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().xf_progress_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def accumulate(self, d_loss, d_labels, R, stream=None):
+        """device pointers (ints): R losses (f32) and labels (i32); one launch, no wait"""
+        check(lib().xf_progress_accumulate_dev(self.h, d_loss, d_labels, int(R), stream))
+
+    def read(self, reset=False):
+        """(counts [2, PROGRESS_RANKS], other [2]) as uint64 arrays"""
+        counts = np.empty((2, PROGRESS_RANKS), np.uint64)
+        other = np.empty(2, np.uint64)
+        check(lib().xf_progress_read(self.h, _p(counts, u64p), _p(other, u64p),
+                                     1 if reset else 0))
+        return counts, other
+
+    def summary(self, neg_weight=1.0, reset=False):
+        counts, other = self.read(reset)
+        return progress_summary(counts, other, neg_weight)
+
+
 class Cross:
     """Feature crosses (xf_cross_*): apply() returns a minibatch with, behind every row's own
     nonzeros, one nonzero per listed pair of fields and per (member of the first, member of the
@@ -1361,6 +1450,12 @@ class Workspace:
         step multiplies the losses of its label-0 rows by it; 1 (default): nothing is launched"""
         check(lib().xf_workspace_neg_weight(self.h, float(weight)))
 
+    def progress(self, p):
+        """attach a Progress (None: off, the default): every training step counts its losses
+        after the forward has written them and before the negatives' weight touches them"""
+        check(lib().xf_workspace_progress(self.h, p.h if p is not None else None))
+        self._progress = p   # (the workspace holds a pointer to it)
+
     def fetch(self, U, R):
         wu = np.empty(U, np.float32)
         loss = np.empty(R, np.float32)
@@ -1575,6 +1670,25 @@ class Sharded:
         """the weight of a kept negative (Workspace.neg_weight); several ranks: schedules
         'sequential' and 'stale1' only"""
         check(lib().xf_sharded_set_neg_weight(self.h, float(weight)))
+
+    def set_progress(self, enable):
+        """progressive validation on the trainer's training steps (xf_sharded_progress); several
+        ranks: schedules 'sequential' and 'stale1' only"""
+        check(lib().xf_sharded_progress(self.h, 1 if enable else 0))
+
+    def progress_read(self, reset=False, merged=False):
+        """(counts, other) of this rank; merged=True: COLLECTIVE, the sum over the ranks"""
+        counts = np.empty((2, PROGRESS_RANKS), np.uint64)
+        other = np.empty(2, np.uint64)
+        check(lib().xf_sharded_progress_read(self.h, _p(counts, u64p), _p(other, u64p),
+                                             1 if reset else 0, 1 if merged else 0))
+        return counts, other
+
+    def last_loss(self, b):
+        """the (weighted) losses the last step of minibatch b left (xf_sharded_last_loss)"""
+        out = np.empty(max(b.R, 1), np.float32)
+        check(lib().xf_sharded_last_loss(self.h, b.h, _p(out, f32p), b.R))
+        return out[:b.R]
 
     def close(self):
         if getattr(self, "h", None):

@@ -33,7 +33,10 @@ int main(int argc, char *argv[]) {
                  "a kept negative's loss weighted by 1 / r): append neg_keep=r\n"
               << "feature crosses (a nonzero per listed pair of fields and per pair of their "
                  "members, formed on the GPU; predict needs the same spec): append cross=2*3,16*17 "
-                 "[cross_fgid_base=N with fm_mode=field_aware]\n";
+                 "[cross_fgid_base=N with fm_mode=field_aware]\n"
+              << "progressive validation (per epoch: logloss and AUC of every training row under "
+                 "the weights it met before it was trained on, counted on the GPU): append "
+                 "progress=1\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler

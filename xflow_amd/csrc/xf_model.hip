@@ -34,6 +34,7 @@
 #include "xf_ffm.h"
 #include "xf_fm_canonical.h"
 #include "xf_negsample.h"
+#include "xf_progress.h"
 #include "xf_scratch.h"
 #include "xf_wave.h"
 
@@ -1604,6 +1605,9 @@ struct xf_workspace {
   // the LR cells steps in the finalize kernel's last store (cells_lr_forward), every other step
   // with a launch between forward and gradient (xf::weigh_negatives: no launch at 1)
   float neg_weight = 1.0f;
+  // progressive validation (xf_workspace_progress; null: off): a training step counts its losses'
+  // ranks after the forward has written them and before the weight above touches them (ws_tap)
+  xf_progress *progress = nullptr;
   // the cells lr_step last ran over (compared, never dereferenced): a minibatch stepped twice in
   // a row has its entries where the step before left them, and nothing is fetched for it
   const xf_cells *last_cells = nullptr;
@@ -1848,6 +1852,25 @@ extern "C" int xf_workspace_neg_weight(xf_workspace *ws, float weight) {
   return XF_OK;
 }
 
+extern "C" int xf_workspace_progress(xf_workspace *ws, xf_progress *p) {
+  XF_REQUIRE(ws, "xf_workspace_progress: null workspace");
+  ws->progress = p;
+  return XF_OK;
+}
+
+// between a training step's forward and whatever reads its losses: progressive validation counts
+// them as the forward left them, then the negatives take their weight (no launch for either when
+// nothing is attached and the weight is 1)
+static int ws_tap(xf_workspace *ws, const int32_t *labels, uint32_t R, hipStream_t s) {
+  if (ws->progress) XF_TRY(xf::progress_accumulate(ws->progress, ws->loss, labels, R, s));
+  return xf::weigh_negatives(ws->loss, labels, R, ws->neg_weight, s);
+}
+// the LR steps on cells store the weighted loss from the finalize kernel — unless a progress is
+// attached: then they finalize unweighted and ws_tap follows (same expression, same bits)
+static float ws_finalize_weight(const xf_workspace *ws) {
+  return ws->progress ? 1.0f : ws->neg_weight;
+}
+
 extern "C" int xf_workspace_capture(xf_workspace *ws, int enable) {
   XF_REQUIRE(ws, "xf_workspace_capture: null workspace");
   XF_REQUIRE(!enable || ws->fm_mode != XF_FM_FIELD_AWARE,
@@ -1895,10 +1918,10 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
   // forward is another kernel and keeps the separate launch)
   if (ws->parity == XF_PARITY_REFERENCE_ORDER) {
     XF_TRY(lr_forward_reforder(w, b, ws->loss, nullptr, S(stream)));
-    XF_TRY(xf::weigh_negatives(ws->loss, labels, b->R, ws->neg_weight, S(stream)));
+    XF_TRY(ws_tap(ws, labels, b->R, S(stream)));
   } else {
     XF_TRY(xf::cells_lr_forward(c, T.w, labels, ws->partial, ws->loss, nullptr, S(stream),
-                                nullptr, ws->last_cells != c, ws->neg_weight));  // :172
+                                nullptr, ws->last_cells != c, ws_finalize_weight(ws)));  // :172
   }
   ws->last_cells = c;
   if (settle.d) {  // the build's wait, under the forward
@@ -1912,9 +1935,12 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
       XF_TRY(ws_reserve_cells(ws, c, cap));
       XF_TRY(xf::cells_lr_forward(c, xf::table_dev(w).w, labels, ws->partial, ws->loss, nullptr,
                                   S(stream), ws->capPartial == had ? c->next : nullptr, true,
-                                  ws->neg_weight));
+                                  ws_finalize_weight(ws)));
     }
   }
+  // (after the LAST forward segment: the losses are final)
+  if (ws->progress && ws->parity != XF_PARITY_REFERENCE_ORDER)
+    XF_TRY(ws_tap(ws, labels, b->R, S(stream)));
   XF_END(kEvForward);
   if (cap) XF_TRY(xf::gather_f32(T.w, b->d_rows_u, b->U, ws->wu, S(stream)));
   if (ws->parity == XF_PARITY_REFERENCE_ORDER) {
@@ -2230,7 +2256,7 @@ static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
   XF_END(kEvGather);
   XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, nullptr,
                          b->valued ? b->d_xval : nullptr, S(stream)));
-  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
+  XF_TRY(ws_tap(ws, v.labels, v.R, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {
     xf::table_note_write(w);
@@ -2341,7 +2367,7 @@ static int fm_field_aware_step(xf_table *w, xf_table *vt, xf_batch *b, xf_worksp
   XF_END(kEvGather);
   XF_TRY(xf::ffm_forward(&v, k, F, ws->wu, ws->fmc_vu, b->d_xfg, ws->loss, nullptr,
                          b->valued ? b->d_xval : nullptr, S(stream)));
-  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
+  XF_TRY(ws_tap(ws, v.labels, v.R, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {
     xf::table_note_write(w);
@@ -2406,7 +2432,7 @@ static int lr_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stre
   }
   XF_END(kEvResolve);
   XF_TRY(xf::val_lr_forward(&v, b->d_xval, ws->wu, ws->loss, nullptr, S(stream)));  // :172
-  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
+  XF_TRY(ws_tap(ws, v.labels, v.R, S(stream)));
   XF_END(kEvForward);
   if (v.U && v.R) {  // :173, :175
     xf::table_note_write(w);
@@ -2446,7 +2472,8 @@ static int lr_local_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void
   ws->lastR = b->R;
   XF_BEGIN();
   XF_TRY(xf::cells_lr_forward_valued(c, xf::table_dev(w).w, b->raw_labels, ws->partial, ws->loss,
-                                     nullptr, S(stream), ws->neg_weight));  // :172
+                                     nullptr, S(stream), ws_finalize_weight(ws)));  // :172
+  if (ws->progress) XF_TRY(ws_tap(ws, b->raw_labels, b->R, S(stream)));
   XF_END(kEvForward);
   XF_TRY(xf::cells_lr_grad_update_valued(c, w, ws->loss, S(stream)));  // :173, :175
   XF_END(kEvGrad);
@@ -2515,7 +2542,7 @@ extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *
                        dim3(kBlock), 0, S(stream), v.rowptr, b->d_fm_ridx, (const FmKey *)rec,
                        v.labels, v.R, ws->loss, (float *)nullptr, ws->vsum);  // :237
     XF_HIP(hipGetLastError());
-    XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
+    XF_TRY(ws_tap(ws, v.labels, v.R, S(stream)));
     XF_END(kEvForward);
     XF_TRY(fm_grad_update(w, vt, &v, rows_w, rows_v, ws->wu, ws->vu, ws->vsum, ws->loss, ws->g,
                           ws->gv, false, stream, rec));
@@ -2559,7 +2586,7 @@ extern "C" int xf_fm_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *
     else
       XF_TRY(xf_fm_forward_dev(&v, k, ws->wu, ws->vu, ws->loss, nullptr, ws->vsum, stream));
   }
-  XF_TRY(xf::weigh_negatives(ws->loss, v.labels, v.R, ws->neg_weight, S(stream)));
+  XF_TRY(ws_tap(ws, v.labels, v.R, S(stream)));
   XF_END(kEvForward);
   if (ws->parity == XF_PARITY_REFERENCE_ORDER && v.U) {
     // the reference's own fp32 running sums per key and factor, then the two Pushes

@@ -52,6 +52,7 @@
 #include "xf_ffm.h"
 #include "xf_fm_canonical.h"
 #include "xf_negsample.h"
+#include "xf_progress.h"
 #include "xf_scratch.h"
 
 namespace xf {
@@ -232,6 +233,7 @@ struct xf_sharded {
   int fm_mode = XF_FM_REFERENCE;           // (what xf_sharded_set_fm_mode last set)
   int fm_fields = 0;                       // (what xf_sharded_set_fm_fields last set)
   float neg_weight = 1.0f;                 // (what xf_sharded_set_neg_weight last set)
+  xf_progress *progress = nullptr;         // progressive validation (xf_sharded_progress); null: off
   uint64_t seen_upper = 0;     // world 1: host-side upper bound on the keys in the table
   Dev<double> partial;         // LR forward scratch
   // the owner-compute compile's staging: the worker's nonzeros grouped by owner (sent from
@@ -391,6 +393,13 @@ int front_pull(xf_sharded *st, xf_sbatch *b, StepBuf &B, hipStream_t s) {
   return XF_OK;
 }
 
+// between the forward and the gradient of a training step: progressive validation counts the
+// losses as the forward left them, then the negatives take their weight
+int front_tap(xf_sharded *st, float *loss, const int32_t *labels, uint32_t R, hipStream_t s) {
+  if (st->progress) XF_TRY(xf::progress_accumulate(st->progress, loss, labels, R, s));
+  return xf::weigh_negatives(loss, labels, R, st->neg_weight, s);
+}
+
 // weights back to the workers, forward, gradient
 int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool want_grad,
                   hipStream_t s) {
@@ -410,7 +419,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
   if (!fm && hb->valued) {
     // valued LR: the w half of the canonical step (xf_valued.hip), no cells
     XF_TRY(xf::val_lr_forward(&v, hb->d_xval, B.wu.p, B.loss.p, d_pctr, s));
-    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
+    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -421,7 +430,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     XF_TRY(B.S.reserve((size_t)b->R * k));
     XF_TRY(xf::fmc_forward(&v, k, B.wu.p, B.vu.p, B.S.p, B.loss.p, d_pctr,
                            hb->valued ? hb->d_xval : nullptr, s));
-    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
+    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -434,7 +443,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     const int F = st->fm_fields, kf = k / F;  // (k: the v rows' width, fields x kf)
     XF_TRY(xf::ffm_forward(&v, kf, F, B.wu.p, B.vu.p, hb->d_xfg, B.loss.p, d_pctr,
                            hb->valued ? hb->d_xval : nullptr, s));
-    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
+    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -448,7 +457,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     XF_TRY(st->partial.reserve(xf::cells_partial_doubles(b->cells)));
     XF_TRY(xf::cells_lr_forward(b->cells, B.wu.p, b->b->view.labels, st->partial.p, B.loss.p,
                                 d_pctr, s));
-    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
+    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -462,7 +471,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     } else {
       XF_TRY(xf_fm_forward_dev(&b->b->view, k, B.wu.p, B.vu.p, B.loss.p, d_pctr, B.vsum.p, s));
     }
-    if (want_grad) XF_TRY(xf::weigh_negatives(B.loss.p, v.labels, b->R, st->neg_weight, s));
+    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -1406,6 +1415,7 @@ extern "C" int xf_sharded_destroy(xf_sharded *st) {
   (void)hipDeviceSynchronize();
   if (st->h_counts) (void)hipHostFree(st->h_counts);
   if (st->ws) xf_workspace_destroy(st->ws);
+  if (st->progress) xf_progress_destroy(st->progress);
   if (st->tw) xf_table_destroy(st->tw);
   if (st->tv) xf_table_destroy(st->tv);
   if (st->main) (void)hipStreamDestroy(st->main);
@@ -2024,6 +2034,10 @@ extern "C" int xf_sharded_set_schedule(xf_sharded *st, int schedule) {
              "xf_sharded_set_schedule: schedule %s with a weight on the negatives "
              "(xf_sharded_set_neg_weight %g): the owners' finalize kernels form the loss unweighted",
              schedule_name(schedule), (double)st->neg_weight);
+  XF_REQUIRE(!owner_dataflow(schedule) || st->fused || !st->progress,
+             "xf_sharded_set_schedule: schedule %s with progressive validation on "
+             "(xf_sharded_progress): the owners' finalize kernels form the loss where no tap reads it",
+             schedule_name(schedule));
   XF_TRY(xf_sharded_flush(st));
   st->cfg.schedule = schedule;
   return XF_OK;
@@ -2056,6 +2070,62 @@ extern "C" int xf_sharded_set_neg_weight(xf_sharded *st, float weight) {
              (double)weight, schedule_name(st->cfg.schedule));
   if (st->fused) XF_TRY(xf_workspace_neg_weight(st->ws, weight));
   st->neg_weight = weight;
+  return XF_OK;
+}
+
+// progressive validation: the fused step taps through its workspace, the exchange path's
+// front_compute through the trainer
+extern "C" int xf_sharded_progress(xf_sharded *st, int enable) {
+  XF_REQUIRE(st, "xf_sharded_progress: null trainer");
+  XF_ALIVE(st);
+  XF_REQUIRE(!enable || st->fused || !owner_dataflow(st->cfg.schedule),
+             "xf_sharded_progress: progressive validation on schedule %s: the owners' finalize "
+             "kernels form the loss where no tap reads it (use schedule sequential or stale1)",
+             schedule_name(st->cfg.schedule));
+  if (enable && !st->progress) {
+    XF_TRY(xf_progress_create(&st->progress));
+  } else if (!enable && st->progress) {
+    XF_TRY(xf_sharded_flush(st));
+    xf_progress_destroy(st->progress);
+    st->progress = nullptr;
+  }
+  if (st->fused) XF_TRY(xf_workspace_progress(st->ws, st->progress));
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_progress_read(xf_sharded *st, uint64_t *counts, uint64_t *other,
+                                        int reset, int merged) {
+  XF_REQUIRE(st && counts && other, "xf_sharded_progress_read: null argument");
+  XF_REQUIRE(st->progress, "xf_sharded_progress_read: progressive validation is off "
+             "(xf_sharded_progress)");
+  XF_TRY(xf_sharded_flush(st));
+  XF_TRY(xf_progress_read(st->progress, counts, other, reset));
+  if (!merged || !st->g || st->world <= 1) return XF_OK;
+  const size_t nc = 2 * (size_t)XF_PROGRESS_RANKS, n = nc + 2;
+  std::vector<uint64_t> mine(n), all(n * (size_t)st->world);
+  std::copy(counts, counts + nc, mine.begin());
+  mine[nc] = other[0];
+  mine[nc + 1] = other[1];
+  XF_TRY(xf_group_allgather_host(st->g, mine.data(), n * 8, all.data()));
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t sum = 0;
+    for (int r = 0; r < st->world; ++r) sum += all[(size_t)r * n + i];
+    (i < nc ? counts[i] : other[i - nc]) = sum;
+  }
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_last_loss(xf_sharded *st, xf_sbatch *b, float *loss, size_t R) {
+  XF_REQUIRE(st && b && (loss || !R), "xf_sharded_last_loss: null argument");
+  XF_REQUIRE(R == b->R, "xf_sharded_last_loss: the minibatch has %u rows, not %zu", b->R, R);
+  XF_TRY(xf_sharded_flush(st));
+  if (!R) return XF_OK;
+  if (st->fused) return xf_workspace_fetch(st->ws, nullptr, loss, nullptr, 0, R);
+  XF_REQUIRE(!b->oc, "xf_sharded_last_loss: a minibatch of the owner-compute dataflow keeps its "
+             "losses at the owners");
+  const float *d = b->buf[b->flip ^ 1].loss.p;  // (a step flips after it picked its buffers)
+  XF_REQUIRE(d, "xf_sharded_last_loss: the minibatch has not been stepped");
+  XF_HIP(hipMemcpy(loss, d, R * 4, hipMemcpyDeviceToHost));
   return XF_OK;
 }
 

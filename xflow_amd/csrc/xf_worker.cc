@@ -109,6 +109,7 @@ int Worker::create_tables() {
   if (parity != XF_PARITY_EXACT_SUMS) XF_TRY(xf_sharded_set_parity(sharded_, parity));
   if (fm_mode == XF_FM_FIELD_AWARE) XF_TRY(xf_sharded_set_fm_fields(sharded_, fields));
   if (fm_mode != XF_FM_REFERENCE) XF_TRY(xf_sharded_set_fm_mode(sharded_, fm_mode));
+  if (progress) XF_TRY(xf_sharded_progress(sharded_, 1));
   XF_TRY(xf_sharded_tables(sharded_, &table_w_, &table_v_));
   // One update() and one predict of a two-row minibatch on a private single-shard trainer: the
   // first launch of a kernel loads its code object and the builders size their scratch on first
@@ -132,6 +133,7 @@ int Worker::create_tables() {
     // own check, so that a bad value is refused by its name)
     if (rc == XF_OK) rc = check_negsample();
     if (rc == XF_OK && neg_keep < 1.0f) rc = xf_sharded_set_neg_weight(warm, 1.0f / neg_keep);
+    if (rc == XF_OK && progress) rc = xf_sharded_progress(warm, 1);  // (its kernel's first launch)
     if (rc == XF_OK) rc = compile_rows(warm, &b, 0, rp, keys, fg, vals, lab, 0, 2, 1);
     if (rc == XF_OK) rc = xf_sharded_step(warm, b);
     if (rc == XF_OK) rc = xf_sharded_predict(warm, b, p);
@@ -212,6 +214,46 @@ int Worker::check_negsample() const {
              "XFStartTrain: neg_keep=%g together with schedule=owner / owner_stale1 (world %d): the "
              "owners form the loss unweighted (use schedule=sequential or stale1)",
              (double)neg_keep, w);
+  return XF_OK;
+}
+
+// Progressive validation taps the loss between a step's forward and its gradient: on several
+// workers the owner-compute schedules form it inside the owners' finalize kernels.  Refused by
+// name, before any rendezvous.
+int Worker::check_progress() const {
+  XF_REQUIRE(progress == 0 || progress == 1, "XFStartTrain: progress must be 0 or 1, not %d",
+             progress);
+  if (!progress) return XF_OK;
+  const int w = sharded_ ? world : world_from_env(world);
+  XF_REQUIRE(w <= 1 || (schedule != XF_SCHEDULE_OWNER && schedule != XF_SCHEDULE_OWNER_STALE1),
+             "XFStartTrain: progress=1 together with schedule=owner / owner_stale1 (world %d): the "
+             "owners form the loss where no tap reads it (use schedule=sequential or stale1)", w);
+  return XF_OK;
+}
+
+// the end of an epoch, after the flush: the epoch's counts, summed over the ranks, and reset
+int Worker::progress_epoch(int epoch) {
+  if (!progress) return XF_OK;
+  std::vector<uint64_t> counts(2 * (size_t)XF_PROGRESS_RANKS);
+  uint64_t other[2] = {0, 0};
+  XF_TRY(xf_sharded_progress_read(sharded_, counts.data(), other, 1, world > 1));
+  float weight = 1.0f;
+  if (sample_) XF_TRY(xf_negsample_weight(sample_, &weight));
+  XF_TRY(xf_progress_summary(counts.data(), other, weight, &progress_last_));
+  if (!progress_have_) progress_first_ = progress_last_;
+  progress_have_ = true;
+  if (rank != 0) return XF_OK;
+  const xf_progress_metrics &m = progress_last_;
+  char line[512];
+  int at = snprintf(line, sizeof(line),
+                    "progress epoch %d: rows = %.12g logloss = %.6f (+- %.1e) auc = %.6f (+- %.1e) "
+                    "ctr = %.6f pctr = %.6f", epoch, m.rows_pos + m.rows_neg, m.logloss,
+                    m.logloss_bound, m.auc, m.auc_slack, m.ctr, m.pctr);
+  if (m.saturated != 0 && at < (int)sizeof(line))
+    at += snprintf(line + at, sizeof(line) - at, " saturated = %.17g", m.saturated);
+  if (m.other != 0 && at < (int)sizeof(line))
+    snprintf(line + at, sizeof(line) - at, " other = %.17g", m.other);
+  std::cout << line << std::endl;
   return XF_OK;
 }
 
@@ -753,6 +795,7 @@ int Worker::batch_training() {
     // flush is collective (every rank, every epoch); the defrag itself is local to the shard.
     const double tf0 = now_s();
     XF_TRY(xf_sharded_flush(sharded_));
+    XF_TRY(progress_epoch(epoch));
     if (epoch + 1 < epochs) XF_TRY(defrag_if_grown(5));
     if (getenv("XF_TRACE_WORKER"))
       fprintf(stderr, "epoch %d: flush + table maintenance %.2f ms\n", epoch, (now_s() - tf0) * 1e3);
@@ -1089,6 +1132,8 @@ int Worker::train() {
   }
   XF_TRY(check_admit());  // before any rendezvous of a group
   XF_TRY(check_negsample());
+  XF_TRY(check_progress());
+  progress_have_ = false;
   XF_TRY(check_cross());
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
@@ -1221,6 +1266,11 @@ int Worker::set_param(const char *name, const char *value) {
   } else if (n == "neg_keep") {
     XF_REQUIRE(!sample_, "XFSetParam: neg_keep cannot change once the sampler exists");
     neg_keep = strtof(value, nullptr);
+  } else if (n == "progress") {
+    XF_REQUIRE(!sharded_, "XFSetParam: progress cannot change after training started");
+    XF_REQUIRE(!strcmp(value, "0") || !strcmp(value, "1"),
+               "XFSetParam: progress must be 0 or 1, not %s", value);
+    progress = atoi(value);
   } else if (n == "cross") {
     XF_REQUIRE(!cross_, "XFSetParam: cross cannot change once the stage exists");
     cross_spec = value;
@@ -1267,6 +1317,20 @@ int Worker::get_metric(const char *name, double *value) {
     uint64_t rows_kept = 0, seen = 0, kept = 0;
     if (sample_) XF_TRY(xf_negsample_stats(sample_, nullptr, &rows_kept, &seen, &kept));
     *value = (double)(n == "neg_seen" ? seen : n == "neg_kept" ? kept : rows_kept);
+  } else if (n.rfind("progress_", 0) == 0) {
+    const bool first = n.size() > 6 && n.compare(n.size() - 6, 6, "_first") == 0;
+    const std::string what = n.substr(9, n.size() - 9 - (first ? 6 : 0));
+    const xf_progress_metrics &m = first ? progress_first_ : progress_last_;
+    XF_REQUIRE(progress_have_, "XFGetMetric: %s: no epoch has been summarised (progress=1, after "
+               "XFStartTrain)", name);
+    if (what == "logloss") *value = m.logloss;
+    else if (what == "auc") *value = m.auc;
+    else if (!first && what == "auc_slack") *value = m.auc_slack;
+    else if (!first && what == "ctr") *value = m.ctr;
+    else if (!first && what == "pctr") *value = m.pctr;
+    else if (!first && what == "rows") *value = m.rows_pos + m.rows_neg;
+    else
+      return xf::set_error(XF_EINVAL, "XFGetMetric: unknown metric '%s'", name);
   } else if (n == "cross_in" || n == "cross_out") {
     uint64_t in = 0, crossed = 0;
     if (cross_) XF_TRY(xf_cross_stats(cross_, nullptr, &in, &crossed));

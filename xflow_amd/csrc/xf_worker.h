@@ -101,8 +101,18 @@ class Worker {
   // read only with fm_mode=field_aware (base + pairs <= fields).  Nothing travels with the model.
   std::string cross_spec;
   int cross_fgid_base = 0;
+  // Progressive validation (xf_progress.hip): progress = 1: every training step counts its rows'
+  // losses — formed under the weights the step is about to change — on the GPU, with no host wait
+  // inside an epoch; at the end of each epoch (replayed ones included) the counts are read, merged
+  // over the ranks and reset, and rank 0 prints one line.  A negative weighs the sampler's weight.
+  // Not with the owner-compute schedules on several workers (checked where training starts).
+  int progress = 0;
 
  private:
+  int check_progress() const;  // the refusals of progress=1, before any rendezvous
+  int progress_epoch(int epoch);  // COLLECTIVE at world > 1: read, merge, reset, summarise, print
+  xf_progress_metrics progress_last_{}, progress_first_{};
+  bool progress_have_ = false;
   int create_tables();
   int defrag_if_grown(int percent);
   int any_rank(bool mine, bool *any);
