@@ -475,6 +475,23 @@ int xf_table_div_exact(xf_table *t, int *out);
 /* out[i] = the step's x[i] / d (the product with 1.0 / (double)d, with its guard of the subnormal
  * range or, exact != 0, without it), computed on the GPU; host arrays of n floats.  For tests. */
 int xf_div_by_const_probe(const float *x, size_t n, float d, int exact, float *out);
+/* The scalar layer under every forward and step (xf_device.h), the functions as the kernels call
+ * them, computed on the GPU.  For tests (tests/test_gpu_scalar.py): each is compared with the
+ * host on all 2^32 floats.
+ *   XF_SCALAR_SIGMOID   sigmoid_ref(a)            XF_SCALAR_SQRT      sqrtf(a)
+ *   XF_SCALAR_DIV       a / b in fp32             XF_SCALAR_DIV_ROWS  div_by_rows(a, param)
+ * xf_scalar_probe: out[i] = op(a[i], b[i]); host arrays of n floats, b is read by XF_SCALAR_DIV
+ * alone (NULL otherwise), param (the row count R >= 1) by XF_SCALAR_DIV_ROWS alone.
+ * xf_scalar_sweep: every op but XF_SCALAR_DIV over whole blocks of inputs.  Block i is the 65536
+ * floats with the bit patterns (i << 16) .. (i << 16) + 65535; digests[j] (host, nblocks of them)
+ * is the wrapping sum over block first_block + j of
+ *   mix64((uint64_t)bits(a) << 32 | canon(bits(op(a))))
+ * with splitmix64's finaliser for mix64 and canon = every NaN to 0x7fc00000 (the sign and payload
+ * of a NaN are the one thing two IEEE machines may disagree on).  first_block + nblocks <= 65536. */
+enum { XF_SCALAR_SIGMOID = 0, XF_SCALAR_SQRT = 1, XF_SCALAR_DIV = 2, XF_SCALAR_DIV_ROWS = 3 };
+int xf_scalar_probe(int op, const float *a, const float *b, uint32_t param, size_t n, float *out);
+int xf_scalar_sweep(int op, uint32_t param, uint32_t first_block, uint32_t nblocks,
+                    uint64_t *digests);
 
 /* ---------------------------------------------------------------- model kernels       */
 /* All pointers are device pointers; asynchronous on `stream`. */

@@ -45,6 +45,12 @@ def lib():
     L.xo_shard_of.argtypes = [C.c_uint64, C.c_uint32]
     L.xo_sigmoid.restype = C.c_float
     L.xo_sigmoid.argtypes = [C.c_float]
+    L.xo_scalar_ref.restype = None
+    L.xo_scalar_ref.argtypes = [C.c_int, _f32p, _f32p, C.c_uint32, C.c_size_t, _f32p]
+    L.xo_scalar_sweep.restype = None
+    L.xo_scalar_sweep.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _u64p]
+    L.xo_sigmoid_fragile.restype = C.c_size_t
+    L.xo_sigmoid_fragile.argtypes = [C.c_int, C.c_int, _u32p, _i32p, C.c_size_t]
     L.xo_hashnorm.restype = C.c_float
     L.xo_hashnorm.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
     L.xo_reader_open.restype = C.c_void_p
@@ -124,6 +130,46 @@ def hash_str(s):
 
 def sigmoid(x):
     return float(lib().xo_sigmoid(C.c_float(x)))
+
+
+SCALAR_SIGMOID, SCALAR_SQRT, SCALAR_DIV, SCALAR_DIV_ROWS = range(4)
+
+
+def scalar_ref(op, a, b=None, param=0):
+    """the host's answer, element by element: xo_sigmoid(a), sqrtf(a), a / b, or the reference's
+    `a /= 1.0 * param` (fp64 division, rounded back)"""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    out = np.empty_like(a)
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        assert b.shape == a.shape
+    lib().xo_scalar_ref(op, _ptr(a, _f32p), _ptr(b, _f32p) if b is not None else None,
+                        int(param), a.size, _ptr(out, _f32p))
+    return out
+
+
+def scalar_sweep(op, param=0, first_block=0, nblocks=1 << 16, threads=1):
+    """one uint64 digest per block of 65536 consecutive float bit patterns (xo_scalar_sweep)"""
+    assert 0 <= first_block and first_block + nblocks <= 1 << 16
+    out = np.empty(nblocks, np.uint64)
+    lib().xo_scalar_sweep(op, int(param), first_block, nblocks, int(threads), _ptr(out, _u64p))
+    return out
+
+
+def sigmoid_fragile(max_ulp, threads=1, cap=1 << 16):
+    """(bits uint32[], min_ulp int32[]): every float whose sigmoid changes when pow's result moves
+    by at most max_ulp units in the last place, and the smallest move that does it"""
+    bits = np.empty(cap, np.uint32)
+    ulp = np.empty(cap, np.int32)
+    n = lib().xo_sigmoid_fragile(int(max_ulp), int(threads), _ptr(bits, _u32p), _ptr(ulp, _i32p),
+                                 cap)
+    assert n <= cap, "%d fragile inputs: more than the %d asked for" % (n, cap)
+    return bits[:n].copy(), ulp[:n].copy()
+
+
+def sweep_threads():
+    """threads for the sweeps: the CPUs this process may run on, 16 at the most"""
+    return min(16, len(os.sched_getaffinity(0)))
 
 
 def hashnorm(seed, key, j):

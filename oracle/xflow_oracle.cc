@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <mutex>
 #include <thread>
@@ -79,6 +80,114 @@ extern "C" float xo_sigmoid(float x) { /* base.h:54-63 */
     double ex = pow(2.718281828, x); /* base is NOT e */
     return ex / (1.0 + ex);
   }
+}
+
+/* --------------------------------------------- the scalar layer, one input at a time and swept
+ * What the GPU's xf_scalar_probe / xf_scalar_sweep are compared with (tests/test_gpu_scalar.py),
+ * written from the reference's statements alone: Base::sigmoid above, the host's sqrtf and fp32
+ * division, and the gradient's `float /= 1.0 * rows` — the fp64 division, rounded back
+ * (lr_worker.cc:117, fm_worker.cc:152,155). */
+static inline float xo_scalar_op(int op, float a, float b, uint32_t param) {
+  switch (op) {
+    case XO_SCALAR_SIGMOID: return xo_sigmoid(a);
+    case XO_SCALAR_SQRT: return sqrtf(a);
+    case XO_SCALAR_DIV: return a / b;
+    default: {
+      float g = a;
+      g /= 1.0 * param;
+      return g;
+    }
+  }
+}
+
+extern "C" void xo_scalar_ref(int op, const float *a, const float *b, uint32_t param, size_t n,
+                              float *out) {
+  for (size_t i = 0; i < n; ++i) out[i] = xo_scalar_op(op, a[i], b ? b[i] : 0.0f, param);
+}
+
+static inline uint64_t xo_mix64(uint64_t x);
+
+/* f(first, last) over [0, n) in pieces of 16, handed out to `threads` threads as they come free
+ * (the floats that cost something — |x| <= 30 for the sigmoid — lie in a few runs of blocks) */
+template <class F>
+static void xo_parallel_ranges(uint32_t n, int threads, F f) {
+  if (threads < 1) threads = 1;
+  std::atomic<uint32_t> next(0);
+  std::vector<std::thread> pool;
+  for (int t = 0; t < threads; ++t)
+    pool.emplace_back([&] {
+      for (;;) {
+        const uint32_t lo = next.fetch_add(16);
+        if (lo >= n) return;
+        f(lo, n - lo < 16 ? n : lo + 16);
+      }
+    });
+  for (auto &th : pool) th.join();
+}
+
+/* digests[j] = sum over the 65536 floats a of block first_block + j (bit patterns
+ * (block << 16) ..) of mix64(bits(a) << 32 | canon(bits(op(a)))), canon: any NaN -> 0x7fc00000 */
+extern "C" void xo_scalar_sweep(int op, uint32_t param, uint32_t first_block, uint32_t nblocks,
+                                int threads, uint64_t *digests) {
+  xo_parallel_ranges(nblocks, threads, [=](uint32_t lo, uint32_t hi) {
+    for (uint32_t j = lo; j < hi; ++j) {
+      const uint32_t base = (first_block + j) << 16;
+      uint64_t sum = 0;
+      for (uint32_t i = 0; i < 65536u; ++i) {
+        const uint32_t u = base + i;
+        float a, r;
+        uint32_t ru;
+        memcpy(&a, &u, 4);
+        r = xo_scalar_op(op, a, 0.0f, param);
+        memcpy(&ru, &r, 4);
+        if ((ru & 0x7FFFFFFFu) > 0x7F800000u) ru = 0x7FC00000u;
+        sum += xo_mix64(((uint64_t)u << 32) | ru);
+      }
+      digests[j] = sum;
+    }
+  });
+}
+
+/* The floats whose sigmoid depends on the last bits of pow: every x with |x| <= 30 (the others
+ * take no pow) at which moving ex = pow(2.718281828, x) by up to max_ulp units in the last place,
+ * either way, changes (float)(ex / (1 + ex)).  bits[] ascending as unsigned patterns, min_ulp[]
+ * the smallest move that changes it; returns how many there are (cap of them are stored). */
+extern "C" size_t xo_sigmoid_fragile(int max_ulp, int threads, uint32_t *bits, int32_t *min_ulp,
+                                     size_t cap) {
+  std::mutex mu;
+  std::vector<std::pair<uint32_t, int32_t> > found;
+  xo_parallel_ranges(65536u, threads, [&](uint32_t lo, uint32_t hi) {
+    std::vector<std::pair<uint32_t, int32_t> > mine;
+    for (uint64_t u64 = (uint64_t)lo << 16; u64 < (uint64_t)hi << 16; ++u64) {
+      const uint32_t u = (uint32_t)u64;
+      float x;
+      memcpy(&x, &u, 4);
+      if (!(x >= -30.0f && x <= 30.0f)) continue;
+      const double ex = pow(2.718281828, x);
+      const float p = ex / (1.0 + ex);
+      uint64_t eb;
+      memcpy(&eb, &ex, 8); /* e^-30 <= ex <= e^30: its neighbours are its bit pattern +- d */
+      for (int d = 1; d <= max_ulp; ++d) {
+        uint64_t ub = eb + (uint64_t)d, db = eb - (uint64_t)d;
+        double up, dn;
+        memcpy(&up, &ub, 8);
+        memcpy(&dn, &db, 8);
+        const float pu = up / (1.0 + up), pd = dn / (1.0 + dn);
+        if (pu != p || pd != p) {
+          mine.push_back(std::make_pair(u, (int32_t)d));
+          break;
+        }
+      }
+    }
+    std::lock_guard<std::mutex> g(mu);
+    found.insert(found.end(), mine.begin(), mine.end());
+  });
+  std::sort(found.begin(), found.end());
+  for (size_t i = 0; i < found.size() && i < cap; ++i) {
+    bits[i] = found[i].first;
+    min_ulp[i] = found[i].second;
+  }
+  return found.size();
 }
 
 /* ======================================================================= a1 */

@@ -31,6 +31,20 @@ uint32_t xo_shard_of(uint64_t key, uint32_t nshards);
 /* ---- a6: sigmoid ----------------------------------------------------------- */
 float xo_sigmoid(float x); /* src/base/base.h:54-63 */
 
+/* ---- the scalar layer: what the GPU's xf_scalar_probe / xf_scalar_sweep must equal --------- */
+enum { XO_SCALAR_SIGMOID = 0, XO_SCALAR_SQRT = 1, XO_SCALAR_DIV = 2, XO_SCALAR_DIV_ROWS = 3 };
+/* out[i] = xo_sigmoid(a[i]) | sqrtf(a[i]) | a[i] / b[i] | (float)((double)a[i] / (1.0 * param));
+ * b is read by XO_SCALAR_DIV alone */
+void xo_scalar_ref(int op, const float *a, const float *b, uint32_t param, size_t n, float *out);
+/* one digest per block of 65536 consecutive bit patterns, blocks first_block .. + nblocks, on
+ * `threads` threads: the wrapping sum of mix64(bits(a) << 32 | canon(bits(op(a)))), every NaN
+ * canonical (0x7fc00000) */
+void xo_scalar_sweep(int op, uint32_t param, uint32_t first_block, uint32_t nblocks, int threads,
+                     uint64_t *digests);
+/* every float (|x| <= 30) whose sigmoid changes when pow's result moves by <= max_ulp units in
+ * the last place: bit patterns ascending, the smallest such move beside each; returns the count */
+size_t xo_sigmoid_fragile(int max_ulp, int threads, uint32_t *bits, int32_t *min_ulp, size_t cap);
+
 /* ---- a1: block reader / parser -------------------------------------------- */
 typedef struct xo_reader xo_reader;
 /* cap_bytes == the reference's `block_size << 20` (lr_worker.cc:184) */

@@ -5,7 +5,7 @@ Runs ONLY in the build container (needs /root/reference and oracle/_ref, the sub
 the real reference that compiles from its own sources: src/io + src/base).  The outputs
 are data (inputs + expected outputs); no reference source text is stored.
 
-  python tests/golden/make_golden.py [--live]     (--live: (6) alone)
+  python tests/golden/make_golden.py [--live | --fragile]     (--live: (6) alone, --fragile: (7))
 """
 import json
 import os
@@ -85,6 +85,7 @@ def main():
             fgid=np.concatenate([b[2] for b in blocks]),
             labels=np.concatenate([b[3] for b in blocks]))
     live_vectors()
+    sigmoid_fragile()
     print("golden vectors written to", HERE)
 
 
@@ -114,8 +115,31 @@ def live_vectors():
     np.savez_compressed(os.path.join(HERE, "ref_live_vectors.npz"), **out)
 
 
+FRAGILE_1ULP = ("34000000 34c00000 35200000 35600000 35b00000 35f00000 "
+                "b3800000 b4400000 b4a00000 b4e00000 b5300000 b5700000")
+FRAGILE_2ULP = ("35900000 35d00000 36180000 36380000 36580000 "
+                "b5100000 b5500000 b5980000 b5b80000 b5d80000")
+
+
+def sigmoid_fragile():
+    """(7) the 22 floats at which Base::sigmoid depends on the last two bits of pow (the first 12:
+    on the last one) — found by the sweep of tests/test_scalar_cpu.py, which checks that the list
+    is complete —, each with the float below and above it, and the real code's answers"""
+    assert O.ref_available(), "build oracle/_ref first: make -C oracle"
+    R = O.ref()
+    bits = np.array([int(h, 16) for h in (FRAGILE_1ULP + " " + FRAGILE_2ULP).split()], np.uint32)
+    inputs = np.stack([bits - np.uint32(1), bits, bits + np.uint32(1)], axis=1)
+    host = np.array([R.ref_sigmoid(x) for x in inputs.view(np.float32).ravel()],
+                    np.float32).reshape(inputs.shape)
+    fragile1 = np.arange(len(bits)) < len(FRAGILE_1ULP.split())
+    np.savez_compressed(os.path.join(HERE, "sigmoid_fragile.npz"), bits=bits, inputs=inputs,
+                        host=host, fragile1=fragile1)
+
+
 if __name__ == "__main__":
     if sys.argv[1:] == ["--live"]:   # (6) alone
         live_vectors()
+    elif sys.argv[1:] == ["--fragile"]:   # (7) alone
+        sigmoid_fragile()
     else:
         main()

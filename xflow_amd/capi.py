@@ -21,6 +21,8 @@ INIT_ZERO, INIT_CONST, INIT_HASHNORM = 0, 1, 2
 HEAVY_SEG = 64
 FM_REFERENCE, FM_CANONICAL, FM_FIELD_AWARE = 0, 1, 2
 FM_MODES = {"reference": FM_REFERENCE, "canonical": FM_CANONICAL, "field_aware": FM_FIELD_AWARE}
+# xf_scalar_probe / xf_scalar_sweep
+SCALAR_SIGMOID, SCALAR_SQRT, SCALAR_DIV, SCALAR_DIV_ROWS = range(4)
 
 u64p = C.POINTER(C.c_uint64)
 u32p = C.POINTER(C.c_uint32)
@@ -192,6 +194,8 @@ SIGNATURES = {
     "xf_table_w_derived": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "xf_table_div_exact": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "xf_div_by_const_probe": (C.c_int, [f32p, C.c_size_t, C.c_float, C.c_int, f32p]),
+    "xf_scalar_probe": (C.c_int, [C.c_int, f32p, f32p, C.c_uint32, C.c_size_t, f32p]),
+    "xf_scalar_sweep": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, u64p]),
     "xf_lr_forward_dev": (C.c_int, [C.POINTER(DevBatch), vp, vp, vp, vp]),
     "xf_lr_grad_dev": (C.c_int, [C.POINTER(DevBatch), vp, vp, vp]),
     "xf_fm_forward_dev": (C.c_int, [C.POINTER(DevBatch), C.c_int, vp, vp, vp, vp, vp, vp]),
@@ -1287,6 +1291,31 @@ def div_by_const_probe(x, d, exact=False):
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = np.empty_like(x)
     check(lib().xf_div_by_const_probe(_p(x, f32p), x.size, d, int(bool(exact)), _p(out, f32p)))
+    return out
+
+
+def scalar_probe(op, a, b=None, param=0):
+    """a scalar function of the kernels on the GPU, element by element (xf_scalar_probe):
+    SCALAR_SIGMOID sigmoid_ref(a), SCALAR_SQRT sqrtf(a), SCALAR_DIV a / b, SCALAR_DIV_ROWS
+    div_by_rows(a, param)"""
+    require_gpu()
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    out = np.empty_like(a)
+    if b is not None:
+        b = np.ascontiguousarray(b, dtype=np.float32)
+        assert b.shape == a.shape, "one divisor per dividend"
+    check(lib().xf_scalar_probe(op, _p(a, f32p), _p(b, f32p) if b is not None else None,
+                                int(param), a.size, _p(out, f32p)))
+    return out
+
+
+def scalar_sweep(op, param=0, first_block=0, nblocks=1 << 16):
+    """the digests of blocks first_block .. first_block + nblocks of the 65536 blocks of 65536
+    floats each (xf_scalar_sweep): the wrapping sum of mix64(bits(a) << 32 | bits(op(a))) over
+    the block, every NaN result counted as 0x7fc00000"""
+    require_gpu()
+    out = np.empty(nblocks, np.uint64)
+    check(lib().xf_scalar_sweep(op, int(param), first_block, nblocks, _p(out, u64p)))
     return out
 
 
