@@ -419,6 +419,26 @@ enum {
   XF_DEFRAG_RADIX_CLUSTER = 5
 };
 int xf_table_defrag_path(xf_table *t, int *path);
+/* Table eviction — the one call that lowers a table's key count.  FTRL tables of dim 1 only (LR's
+ * w table); XF_EINVAL with a message for an SGD table, dim != 1, a negative or NaN n_below.
+ * A row is dropped iff  w == 0.0f (either sign of zero)  and  n < n_below,  compared in fp32.
+ * n is the row's accumulated sum of SQUARED gradients, in the units the step uses: the gradient
+ * of a key is the minibatch MEAN of (pctr - label) over the rows that hold it (times the value,
+ * with feature values), so one occurrence in a minibatch of R rows adds at most 1 / R^2 to n —
+ * 4e-10 at R = 50000 — and a key seen in every row of T minibatches has n <= T.  n_below = +inf
+ * drops every zero-weight row; 0 does nothing (*rows_seen = 0); a NaN n is kept; the reserved
+ * key 2^64-1 is judged like any other.  FTRL holds w at exactly 0 while |z| <= lambda1, so the
+ * dropped rows added +0 to every prediction: predictions right after the call equal those before
+ * it bit for bit.  A dropped key that comes back is a first touch: (w, n, z) = (0, 0, 0).
+ * The call settles the table first (xf_table_defrag), then marks and compacts on the GPU (two
+ * kernels and a scan, xf_evict.hip).  *rows_seen: the keys judged; *rows_dropped: those that
+ * went (either may be NULL).  Nothing dropped: row numbers and epoch as the defrag left them.
+ * Otherwise row numbers change like a defrag's — call it between steps.  Everything dropped: the
+ * table is as after xf_table_create (same capacity and hyper-parameters).  No row's value is
+ * written, so xf_table_w_derived stays what it was. */
+int xf_table_evict(xf_table *t, float n_below, uint64_t *rows_seen, uint64_t *rows_dropped);
+/* {rows of one workgroup of the eviction kernels, lanes of a wavefront}: the edges for tests */
+void xf_evict_shape(uint32_t out[2]);
 int xf_table_set_hyper(xf_table *t, float alpha, float beta, float l1, float l2, float lr);
 
 /* ps-lite-shaped host API: keys sorted & unique (the KVWorker contract), host pointers,
@@ -794,6 +814,11 @@ int xf_sharded_step(xf_sharded *st, xf_sbatch *b);
 int xf_sharded_predict(xf_sharded *st, xf_sbatch *b, float *pctr_out);
 int xf_sharded_flush(xf_sharded *st);  /* apply an outstanding stale1 Push; synchronises */
 int xf_sharded_defrag(xf_sharded *st); /* local table maintenance (flushes first) */
+/* xf_table_evict of this rank's shard of the w table (flushes first; local to the rank, no
+ * communication): LR with FTRL, on one rank or on schedule=sequential / stale1.  Refused with a
+ * message: an FM trainer, optimizer=sgd, the owner-compute schedules on several ranks.  The
+ * minibatches compiled before it rebuild their row numbers from their keys at their next step. */
+int xf_sharded_evict(xf_sharded *st, float n_below, uint64_t *seen, uint64_t *dropped);
 int xf_sharded_check(xf_sharded *st);  /* flush + the tables' sticky errors */
 int xf_sharded_set_schedule(xf_sharded *st, int schedule);
 /* the parity mode of the forward (xf_workspace_parity) for a one-rank trainer whose minibatches

@@ -177,6 +177,8 @@ SIGNATURES = {
     "xf_table_capacity": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "xf_table_reserve": (C.c_int, [vp, C.c_uint64]),
     "xf_table_defrag": (C.c_int, [vp]),
+    "xf_table_evict": (C.c_int, [vp, C.c_float, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "xf_evict_shape": (None, [C.POINTER(C.c_uint32)]),
     "xf_table_set_hyper": (C.c_int, [vp] + [C.c_float] * 5),
     "xf_table_pull": (C.c_int, [vp, u64p, C.c_size_t, f32p]),
     "xf_table_push": (C.c_int, [vp, u64p, C.c_size_t, f32p]),
@@ -243,6 +245,8 @@ SIGNATURES = {
     "xf_sharded_predict": (C.c_int, [vp, vp, f32p]),
     "xf_sharded_flush": (C.c_int, [vp]),
     "xf_sharded_defrag": (C.c_int, [vp]),
+    "xf_sharded_evict": (C.c_int, [vp, C.c_float, C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_uint64)]),
     "xf_sharded_check": (C.c_int, [vp]),
     "xf_sharded_set_schedule": (C.c_int, [vp, C.c_int]),
     "xf_sharded_set_parity": (C.c_int, [vp, C.c_int]),
@@ -900,6 +904,13 @@ def progress_shape():
     return dict(zip(("rows", "slots", "probe"), list(out)))
 
 
+def evict_shape():
+    """{rows of a workgroup, lanes of a wavefront} of the eviction kernels (xf_evict_shape)"""
+    out = (C.c_uint32 * 2)()
+    lib().xf_evict_shape(out)
+    return dict(zip(("rows", "wave"), list(out)))
+
+
 class Progress:
     """Progressive validation (xf_progress_*): counts of the ranks of the training rows' losses,
     kept on the GPU.  Attach it to a Workspace (Workspace.progress) or feed it device arrays
@@ -1380,6 +1391,14 @@ class Table:
     def defrag(self):
         check(lib().xf_table_defrag(self.h))
 
+    def evict(self, n_below):
+        """drop every row with w == 0 and n < n_below (xf_table_evict: FTRL, dim 1; inf: every
+        zero-weight row, 0: nothing) -> (rows seen, rows dropped)"""
+        seen, dropped = C.c_uint64(0), C.c_uint64(0)
+        check(lib().xf_table_evict(self.h, C.c_float(n_below), C.byref(seen),
+                                   C.byref(dropped)))
+        return seen.value, dropped.value
+
     def pull(self, keys):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
         out = np.empty(len(keys) * self.dim, dtype=np.float32)
@@ -1792,6 +1811,14 @@ class Sharded:
 
     def defrag(self):
         check(lib().xf_sharded_defrag(self.h))
+
+    def evict(self, n_below):
+        """drop this rank's zero-weight rows with n < n_below (xf_sharded_evict; local to the
+        rank) -> (seen, dropped)"""
+        seen, dropped = C.c_uint64(0), C.c_uint64(0)
+        check(lib().xf_sharded_evict(self.h, C.c_float(n_below), C.byref(seen),
+                                     C.byref(dropped)))
+        return seen.value, dropped.value
 
     def check(self):
         check(lib().xf_sharded_check(self.h))

@@ -1963,6 +1963,32 @@ extern "C" int xf_sharded_defrag(xf_sharded *st) {
   return XF_OK;
 }
 
+// drop this shard's dead rows (xf_table_evict; LR only).  Local to the rank, like the defrag: a
+// key lives on one shard, so the ranks' passes need no word of each other.  Applies an
+// outstanding stale1 Push first.  Every cache of row numbers hangs on the table's (uid, epoch) and
+// is rebuilt from keys, a dropped key re-entering as a first touch.  The owner-compute schedules
+// are refused: their minibatches keep the owners' cells, and no test here covers that rebuild.
+extern "C" int xf_sharded_evict(xf_sharded *st, float n_below, uint64_t *seen,
+                                uint64_t *dropped) {
+  XF_REQUIRE(st, "xf_sharded_evict: null trainer");
+  if (seen) *seen = 0;
+  if (dropped) *dropped = 0;
+  XF_REQUIRE(!st->tv && st->cfg.model == 0,
+             "xf_sharded_evict: only LR (model 0): the v rows of an FM key are not zero when its w "
+             "is, and the w and v tiers keep one numbering");
+  XF_REQUIRE(st->cfg.optimizer == XF_OPT_FTRL,
+             "xf_sharded_evict: only optimizer=ftrl (an SGD row keeps no n to judge it by)");
+  XF_REQUIRE(st->fused || !owner_dataflow(st->cfg.schedule),
+             "xf_sharded_evict: eviction on schedule %s is not built: use schedule=sequential or "
+             "stale1", st->cfg.schedule == XF_SCHEDULE_OWNER ? "owner" : "owner_stale1");
+  XF_TRY(xf_sharded_flush(st));
+  XF_TRY(xf_table_evict(st->tw, n_below, seen, dropped));
+  uint64_t n = 0;  // (the host-side bound on the key count follows the table down)
+  XF_TRY(xf_table_size(st->tw, &n));
+  st->seen_upper = n;
+  return XF_OK;
+}
+
 extern "C" int xf_sharded_check(xf_sharded *st) {
   XF_REQUIRE(st, "xf_sharded_check: null trainer");
   XF_TRY(xf_sharded_flush(st));

@@ -40,6 +40,7 @@
 
 #include "xf_common.h"
 #include "xf_device.h"
+#include "xf_evict.h"
 #include "xf_scratch.h"
 
 namespace {
@@ -1175,6 +1176,12 @@ k_first_rows(xf::TableDev T, const uint64_t *__restrict__ keys, size_t d) {
   }
 }
 __global__ void k_set_count(xf::TableStat *st, unsigned long long d) { st->count = d; }
+// the spare position after an eviction: the reserved key kept at `row`, or (used == 0) gone
+__global__ void k_set_spare(xf::TableDev T, unsigned int used, uint32_t row) {
+  T.stat->spare_used = used;
+  T.keys[T.cap] = xf::kEmptyKey;  // (the reserved key's own value: stored or not, the same word)
+  T.rows[T.cap] = used ? row : xf::kNoRow;
+}
 
 __global__ void k_fill_u32(uint32_t *p, size_t n, uint32_t v) {
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -1258,7 +1265,12 @@ static TierLayout tier_layout(size_t n) {
   L.bytes = L.o_cdir + al((L.ncdir + 1) * sizeof(uint32_t));
   return L;
 }
-// the second state buffer a defrag moves the rows into (the two swap roles)
+// the second state buffer a defrag moves the rows into (the two swap roles).
+// INVARIANT (both buffers): every row at or beyond the table's key count is zero.  A fresh buffer
+// is zeroed; a defrag or an eviction writes rows below the new count only; xf_table_defrag never
+// lowers the count, and xf_table_evict, which does, zeroes the rows between the new count and the
+// old one in BOTH buffers before it returns.  First-touch rows (handed out at the count, never
+// written before their first step) and the next defrag's target rely on it.
 static int alt_state(xf_table *t, size_t elems) {
   if (t->w_alt && t->alt_elems == elems) return XF_OK;
   if (t->w_alt) XF_HIP(hipFree(t->w_alt));
@@ -1695,7 +1707,8 @@ extern "C" int xf_table_defrag(xf_table *t) {
   // device and a GB-sized one takes milliseconds); what outlives the call — the new tier's keys
   // and directories — is allocated, and the state moves into the table's SECOND state buffer
   // (kept between calls: the two swap roles).  Rows at or beyond the table's key count are zero
-  // in both: a buffer only ever held rows below the count of its time, and the count only grows.
+  // in both: a buffer only ever held rows below the count of its time, and the one call that
+  // lowers the count (xf_table_evict) zeroes what it leaves behind (alt_state: the invariant).
   xf::Scratch sc;
   uint64_t *k_all = nullptr;
   uint32_t *r_all = nullptr, *r_sorted = nullptr, *bcnt = nullptr;
@@ -1804,6 +1817,137 @@ extern "C" int xf_table_defrag(xf_table *t) {
   T = N;
   ++t->epoch;  // every row number handed out before this call is stale
   t->defrag_path = path;
+  return XF_OK;
+}
+
+// Drop the dead rows of an FTRL table of dim 1: every key whose weight is zero (either sign) and
+// whose n — the sum of its squared gradients so far — is below `n_below`.  Such a row adds +0 to
+// every prediction, so the predictions right after the call are those before it, bit for bit; a
+// dropped key that comes back is a first touch (0, 0, 0).  The table is settled first
+// (xf_table_defrag: key r owns row r, the arrival index is empty), then xf_evict.hip's passes mark
+// the rows and compact the survivors' keys into the next tier and their state into the second
+// state buffer — the tail of a defrag from there on, except that the key count goes DOWN:
+// the device count is set, the rows between the new count and the old are zeroed in both state
+// buffers (alt_state: the invariant), and a table that lost everything is a created one again.
+// n_below = 0 returns at once (nothing is judged: *rows_seen = 0); +inf drops every zero-weight
+// row; a NaN n is kept.  Nothing dropped: row numbers and epoch as the defrag left them.
+extern "C" int xf_table_evict(xf_table *t, float n_below, uint64_t *rows_seen,
+                              uint64_t *rows_dropped) {
+  XF_REQUIRE(t, "xf_table_evict: null table");
+  if (rows_seen) *rows_seen = 0;
+  if (rows_dropped) *rows_dropped = 0;
+  XF_REQUIRE(t->cfg.opt_kind == XF_OPT_FTRL && t->T.nz,
+             "xf_table_evict: only FTRL tables (an SGD row keeps no n to judge it by)");
+  XF_REQUIRE(t->T.dim == 1, "xf_table_evict: only tables of dim 1 (this one: dim %d; the rows of "
+             "an FM v table are not zero when w is)", t->T.dim);
+  XF_REQUIRE(n_below >= 0.0f, "xf_table_evict: n_below must be >= 0 or +inf, not %g",
+             (double)n_below);
+  if (n_below == 0.0f) return XF_OK;
+  XF_TRY(xf_table_defrag(t));
+  XF_HIP(hipDeviceSynchronize());
+  xf::TableStat st;
+  XF_TRY(read_stat(t, &st));
+  if (st.err) return xf_table_check(t, nullptr);
+  if (rows_seen) *rows_seen = st.count;
+  if (st.count == 0) return XF_OK;
+  xf::TableDev &T = t->T;
+  const size_t spare = st.spare_used ? 1 : 0;
+  const size_t n = (size_t)st.count - spare;
+  XF_REQUIRE(n == (size_t)T.nbase && n < 0xFFFFFFF0ull,
+             "xf_table_evict: %zu keys, %llu of them settled (internal error)", n,
+             (unsigned long long)T.nbase);
+  // the reserved key's row follows the tier: one row, judged here by the same comparison
+  bool spare_keep = false;
+  if (spare) {
+    uint32_t srow = 0;
+    float sw = 0.0f;
+    float2 snz = make_float2(0.0f, 0.0f);
+    XF_HIP(hipMemcpy(&srow, T.rows + T.cap, 4, hipMemcpyDeviceToHost));
+    XF_REQUIRE(srow == n, "xf_table_evict: the reserved key's row is %u, not %zu (internal error)",
+               srow, n);
+    XF_HIP(hipMemcpy(&sw, T.w + n, 4, hipMemcpyDeviceToHost));
+    XF_HIP(hipMemcpy(&snz, T.nz + n, 8, hipMemcpyDeviceToHost));
+    spare_keep = !(sw == 0.0f && snz.x < n_below);
+  }
+  xf::Scratch sc;
+  unsigned long long *mask = nullptr;
+  uint32_t *bcnt = nullptr;
+  uint32_t kept = 0;
+  if (n) {
+    const size_t blocks = xf::evict_blocks(n);
+    XF_TRY(sc.get(&mask, xf::evict_mask_words(n)));
+    XF_TRY(sc.get(&bcnt, blocks + 1));
+    XF_TRY(xf::evict_mark_scan(T.w, T.nz, n, n_below, mask, bcnt, 0));
+    XF_HIP(hipMemcpy(&kept, bcnt + blocks, 4, hipMemcpyDeviceToHost));
+    XF_REQUIRE(kept <= n, "xf_evict: %u survivors of %zu rows (internal error)", kept, n);
+  }
+  const size_t n_new = kept, spare_new = spare_keep ? 1 : 0;
+  const size_t dropped = (n - n_new) + (spare - spare_new);
+  if (rows_dropped) *rows_dropped = dropped;
+  if (dropped == 0) return XF_OK;
+  const size_t elems = ((size_t)T.max_rows + 1) * (size_t)T.dim;
+  XF_TRY(alt_state(t, elems));
+  float *w2 = t->w_alt;
+  float2 *nz2 = t->nz_alt;
+  xf::TableDev N = T;
+  if (n_new) {
+    uint64_t *k_new = nullptr;  // (the new tier's allocation: keys, then the directories)
+    XF_TRY(tier_alloc(t, n_new, &k_new));
+    XF_TRY(xf::evict_compact(T.bkeys, T.w, T.nz, n, mask, bcnt, k_new, w2, nz2, 0));
+    tier_install(t, N, n_new, 0);
+  } else {  // no settled tier: as xf_table_create leaves these
+    N.nbase = N.ndir = N.dmult = N.ncdir = N.cmult = 0;
+    N.bkeys = nullptr;
+    N.bdir = N.cdir = nullptr;
+  }
+  if (spare_new)
+    hipLaunchKernelGGL(k_move_rows, dim3(1), dim3(kBlock), 0, 0, T.w, T.nz, T.dim,
+                       T.rows + T.cap, (size_t)1, n_new, w2, nz2);
+  XF_HIP(hipGetLastError());
+  XF_HIP(hipDeviceSynchronize());
+  // everything is built: from here on nothing fails half-way.  The rows between the new count
+  // and the old one, zero in BOTH buffers (the new one held older rows there, the old one holds
+  // the rows just judged); the count; the spare position.
+  const size_t first = n_new + spare_new, gone = (n + spare) - first;
+  float *ws[2] = {w2, T.w};
+  float2 *nzs[2] = {nz2, T.nz};
+  for (int a = 0; a < 2; ++a) {
+    XF_HIP(hipMemsetAsync(ws[a] + first, 0, gone * sizeof(float), 0));
+    XF_HIP(hipMemsetAsync(nzs[a] + first, 0, gone * sizeof(float2), 0));
+  }
+  hipLaunchKernelGGL(k_set_count, dim3(1), dim3(1), 0, 0, T.stat, (unsigned long long)first);
+  if (spare)
+    hipLaunchKernelGGL(k_set_spare, dim3(1), dim3(1), 0, 0, T, (unsigned int)spare_new,
+                       (uint32_t)n_new);
+  XF_HIP(hipGetLastError());
+  XF_HIP(hipDeviceSynchronize());
+  if (n_new) {
+    tier_swap(t);
+  } else if (t->tier) {  // the tier in use is retired (kept as the spare when it is the larger)
+    if (t->tier_bytes > t->tier_spare_bytes) {
+      if (t->tier_spare) (void)hipFree(t->tier_spare);
+      t->tier_spare = t->tier;
+      t->tier_spare_bytes = t->tier_bytes;
+    } else {
+      (void)hipFree(t->tier);
+    }
+    t->tier = nullptr;
+    t->tier_bytes = 0;
+  }
+  t->w_alt = T.w;
+  t->nz_alt = T.nz;
+  N.w = w2;
+  N.nz = nz2;
+  T = N;
+  ++t->epoch;  // every row number handed out before this call is stale
+  // what the host remembers of a table without a settled tier (note_early, table_early_keys):
+  // an emptied table is a created one again — its first minibatch may settle it at once — and
+  // one that kept only the reserved key holds a key the host API's list does not name
+  if (n_new == 0) {
+    t->early.clear();
+    t->early_over = first != 0;
+    t->rows_out = first != 0;
+  }
   return XF_OK;
 }
 

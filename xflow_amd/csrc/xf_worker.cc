@@ -231,6 +231,51 @@ int Worker::check_progress() const {
   return XF_OK;
 }
 
+// Table eviction judges the n of an FTRL row of dim 1: FM's v rows and SGD rows have no such
+// predicate, and the owner-compute schedules' minibatches are not covered (xf_sharded_evict).
+// Refused by name, before any rendezvous.
+int Worker::check_evict() const {
+  XF_REQUIRE(evict_n >= 0.0f, "XFStartTrain: evict_n must be 0 (off), a positive number or inf, "
+             "not %g", (double)evict_n);
+  XF_REQUIRE(evict_every >= 1, "XFStartTrain: evict_every must be >= 1 (epochs), not %d",
+             evict_every);
+  if (evict_n == 0.0f) return XF_OK;
+  XF_REQUIRE(model_ == 0, "XFStartTrain: evict_n=%g with model 1 (FM): only LR tables are evicted "
+             "(an FM key's v row is not zero when its w is)", (double)evict_n);
+  XF_REQUIRE(optimizer == XF_OPT_FTRL, "XFStartTrain: evict_n=%g together with optimizer=sgd: an "
+             "SGD row keeps no n to judge it by (use optimizer=ftrl)", (double)evict_n);
+  const int w = sharded_ ? world : world_from_env(world);
+  XF_REQUIRE(w <= 1 || (schedule != XF_SCHEDULE_OWNER && schedule != XF_SCHEDULE_OWNER_STALE1),
+             "XFStartTrain: evict_n=%g together with schedule=owner / owner_stale1 (world %d): "
+             "eviction is not built for the owner-compute schedules (use schedule=sequential or "
+             "stale1)", (double)evict_n, w);
+  return XF_OK;
+}
+
+// the end of an epoch, after the flush, in place of the boundary's defrag: every rank evicts its
+// shard (local); the counts summed over the ranks; one line on rank 0
+int Worker::evict_epoch(int epoch) {
+  uint64_t mine[2] = {0, 0};
+  XF_TRY(xf_sharded_evict(sharded_, evict_n, &mine[0], &mine[1]));
+  XF_TRY(xf_table_size(table_w_, &keys_seen_));  // (defrag_if_grown's inflow starts from here)
+  uint64_t sum[2] = {mine[0], mine[1]};
+  if (world > 1) {
+    std::vector<uint64_t> all(2 * (size_t)world);
+    XF_TRY(xf_group_allgather_host(group_, mine, sizeof(mine), all.data()));
+    sum[0] = sum[1] = 0;
+    for (int r = 0; r < world; ++r) {
+      sum[0] += all[2 * (size_t)r];
+      sum[1] += all[2 * (size_t)r + 1];
+    }
+  }
+  evict_seen_ += sum[0];
+  evict_dropped_ += sum[1];
+  if (rank == 0)
+    std::cout << "evict epoch " << epoch + 1 << ": rows = " << sum[0] << " dropped = " << sum[1]
+              << std::endl;
+  return XF_OK;
+}
+
 // the end of an epoch, after the flush: the epoch's counts, summed over the ranks, and reset
 int Worker::progress_epoch(int epoch) {
   if (!progress) return XF_OK;
@@ -605,6 +650,7 @@ int Worker::batch_training() {
   const double t0 = now_s();
   rows_trained_ = 0;
   blocks_gpu = blocks_host = 0;
+  evict_seen_ = evict_dropped_ = 0;
   for (xf_sbatch *b : cache_) xf_sbatch_free(b);  // a second XFStartTrain starts from the files
   cache_.clear();
   bool cached = false;
@@ -796,7 +842,12 @@ int Worker::batch_training() {
     const double tf0 = now_s();
     XF_TRY(xf_sharded_flush(sharded_));
     XF_TRY(progress_epoch(epoch));
-    if (epoch + 1 < epochs) XF_TRY(defrag_if_grown(5));
+    // (evict_n: the eviction settles the table itself; after the LAST epoch too, so that the
+    // model that is saved and scored holds no evictable row)
+    if (evict_n > 0.0f && ((epoch + 1) % evict_every == 0 || epoch + 1 == epochs))
+      XF_TRY(evict_epoch(epoch));
+    else if (epoch + 1 < epochs)
+      XF_TRY(defrag_if_grown(5));
     if (getenv("XF_TRACE_WORKER"))
       fprintf(stderr, "epoch %d: flush + table maintenance %.2f ms\n", epoch, (now_s() - tf0) * 1e3);
     if ((epoch + 1) % 30 == 0) std::cout << "epoch : " << epoch << std::endl;  // :202
@@ -1134,6 +1185,7 @@ int Worker::train() {
   XF_TRY(check_negsample());
   XF_TRY(check_progress());
   progress_have_ = false;
+  XF_TRY(check_evict());
   XF_TRY(check_cross());
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
@@ -1271,6 +1323,15 @@ int Worker::set_param(const char *name, const char *value) {
     XF_REQUIRE(!strcmp(value, "0") || !strcmp(value, "1"),
                "XFSetParam: progress must be 0 or 1, not %s", value);
     progress = atoi(value);
+  } else if (n == "evict_n") {
+    char *end = nullptr;
+    const float x = strtof(value, &end);  // ("inf" parses: every zero-weight row goes)
+    XF_REQUIRE(end != value && *end == '\0' && x >= 0.0f,
+               "XFSetParam: evict_n must be 0 (off), a positive number or inf, not '%s'", value);
+    evict_n = x;
+  } else if (n == "evict_every") {
+    XF_REQUIRE(atoi(value) >= 1, "XFSetParam: evict_every must be >= 1 (epochs), not %s", value);
+    evict_every = atoi(value);
   } else if (n == "cross") {
     XF_REQUIRE(!cross_, "XFSetParam: cross cannot change once the stage exists");
     cross_spec = value;
@@ -1339,7 +1400,9 @@ int Worker::get_metric(const char *name, double *value) {
     uint64_t seen = 0, kept = 0;
     if (admit_) XF_TRY(xf_admit_stats(admit_, &seen, &kept));
     *value = (double)(n == "admit_seen" ? seen : kept);
-  } else if (n == "train_seconds") *value = train_seconds_;
+  } else if (n == "evict_seen") *value = (double)evict_seen_;
+  else if (n == "evict_dropped") *value = (double)evict_dropped_;
+  else if (n == "train_seconds") *value = train_seconds_;
   else if (n == "examples_per_sec") *value = train_seconds_ > 0 ? rows_trained_ / train_seconds_ : 0;
   else if (n == "keys") {
     uint64_t k = 0;

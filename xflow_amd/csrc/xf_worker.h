@@ -107,8 +107,18 @@ class Worker {
   // over the ranks and reset, and rank 0 prints one line.  A negative weighs the sampler's weight.
   // Not with the owner-compute schedules on several workers (checked where training starts).
   int progress = 0;
+  // Table eviction (xf_evict.hip): evict_n = x > 0 (or inf): at the end of every evict_every-th
+  // training epoch — in place of that boundary's defrag — and after the last one, ahead of
+  // save_model and predict, every rank drops the keys of its shard whose w is 0 and whose n (the
+  // sum of squared minibatch-mean gradients) is below x.  0 = off, nothing changes.  LR with FTRL
+  // only, not with the owner-compute schedules on several workers (checked where training starts).
+  float evict_n = 0.0f;
+  int evict_every = 1;
 
  private:
+  int check_evict() const;      // the refusals of evict_n, before any rendezvous
+  int evict_epoch(int epoch);   // COLLECTIVE at world > 1: evict, sum the counts, print
+  uint64_t evict_seen_ = 0, evict_dropped_ = 0;  // totals of the run, summed over the ranks
   int check_progress() const;  // the refusals of progress=1, before any rendezvous
   int progress_epoch(int epoch);  // COLLECTIVE at world > 1: read, merge, reset, summarise, print
   xf_progress_metrics progress_last_{}, progress_first_{};
