@@ -99,6 +99,23 @@ L1 = 1.6e-3
 HYPER = dict(alpha=0.05, beta=1.0, lambda1=L1, lambda2=10.0)
 T1, T2 = 3, 2
 X_TRAIN = 5e-6        # a finite threshold inside the zero rows' n (0 .. 2.4e-5)
+# The replay stream (replay_stream(): the T1 minibatches replayed for EPOCHS = 4 epochs, 4737
+# keys), the oracle's CPU run, share of rows dropped at each eviction (tests/test_evict_cpu.py
+# asserts 10 % .. 90 %):
+#   HYPER, x = inf:      every boundary 61.7 %, 61.7 %, 61.7 %; every second boundary 20.7 %
+#   HYPER, x = X_TRAIN:  every boundary 59.8 %, 59.8 %, 59.8 %; every second boundary 18.9 %
+#   HYPER_ALL_ZERO, x = inf: 100 % at every eviction
+# The reserved key is kept under HYPER (its labels follow it) and dropped under HYPER_ALL_ZERO.
+#
+# lambda1 of the worker tests on the three-block zipf text (worker_text(): 466 keys with key 0;
+# a row of a 1 MiB block moves z by ~1.4e-5): 8e-5 leaves the rare fids at w == 0.  Shares dropped
+# at the evictions, epochs / evict_every 4/1, 4/2, 3/2:
+#   x = inf:       29.0 28.8 28.8 28.8 % | 24.5 23.7 % | 24.5 24.3 %
+#   x = X_WORKER:  26.2 25.8 25.8 25.8 % | 23.4 22.8 % | 23.4 23.2 %
+#   feature values on, 4/1, inf: 24.2 24.1 24.1 24.1 %;  two ranks, 3/1, inf: 39.8 39.7 39.7 %
+# (at 2e-5 and below 1 % go; X_WORKER = 2e-9 takes 0.9 % when n has two epochs to grow)
+L1_WORKER = 8e-5
+X_WORKER = 3e-9       # inside the zero rows' n (0 .. 6.8e-9 after one epoch, most at 1.4e-9)
 
 
 def stream():
@@ -115,3 +132,261 @@ def oracle_after_t1():
         with O.sum_mode(1):
             O.lr_update(s, O.Batch(*raw))
     return s.export()
+
+
+# ------------------------------------------------------------------ the evicting oracle
+# Every weight stays 0 under this lambda1 (|z| never reaches it): every eviction at x = inf empties
+# the table, and every replayed minibatch meets a created table again
+HYPER_ALL_ZERO = dict(HYPER, lambda1=1e3)
+EPOCHS = 4
+# drops only rows whose n is 0.  After ONE epoch of the replay stream 126 keys hold n == 0 (every
+# prediction of the first step is 0.5, so a key's losses can cancel exactly); after two epochs
+# none does: the eviction that drops nothing runs at the boundaries in AT_NONE
+X_NONE = 1e-30
+AT_NONE = [1, 2]
+
+
+class EvictingStore:
+    """O.Store(O.OPT_FTRL, 1) under `hyper`, with xf_table_evict restated on it: export, the
+    evict() filter above, a fresh Store (same hyper-parameters), import.  Steps are the oracle's
+    O.lr_update in sum_mode(1), valued steps tests/_valued_checker.py's."""
+
+    def __init__(self, hyper=None):
+        self.hyper = dict(HYPER if hyper is None else hyper)
+        self.s = self._fresh()
+        self.audit = []           # the valued restatement's sums (V.assert_exact)
+
+    def _fresh(self):
+        from oracle import pyoracle as O
+        s = O.Store(O.OPT_FTRL, 1)
+        h = self.hyper
+        s.set_ftrl(h["alpha"], h["beta"], h["lambda1"], h["lambda2"])
+        return s
+
+    def step(self, raw, values=None):
+        from oracle import pyoracle as O
+        if values is not None:
+            from tests import _valued_checker as V
+            V.lr_step(self.s, raw[0], raw[1], values, raw[2], self.audit)
+            return
+        with O.sum_mode(1):
+            O.lr_update(self.s, O.Batch(*raw))
+
+    def predict(self, raw, values=None):
+        """the forward (a Pull inserts the unseen keys, as the GPU's does)"""
+        from oracle import pyoracle as O
+        if values is not None:
+            from tests import _valued_checker as V
+            return V.lr_predict(self.s, raw[0], raw[1], values, raw[2], self.audit)
+        ob = O.Batch(*raw)
+        with O.sum_mode(1):
+            return ob.lr_loss(self.s.pull(ob.ukeys))[1]
+
+    def evict(self, x):
+        """-> (seen, dropped)"""
+        want, seen, dropped = evict(self.s.export(), x)
+        if dropped:
+            self.s = self._fresh()
+            self.s.import_(*want)
+        return seen, dropped
+
+    def export(self):
+        return self.s.export()
+
+
+class _Prepared:
+    """one rank's minibatch between its Pull and its Push"""
+
+    def __init__(self, raw, values, audit):
+        from oracle import pyoracle as O
+        self.values, self.audit = values, audit
+        if values is None:
+            self.ob = O.Batch(*raw)
+            self.ukeys = self.ob.ukeys
+        else:
+            from tests import _valued_checker as V
+            self.rp, self.ukeys, self.uidx, self.x = V._slice(raw[0], raw[1], values)
+            self.labels = raw[2]
+
+    def grad(self, pulled):
+        from oracle import pyoracle as O
+        if self.values is None:
+            with O.sum_mode(1):
+                return self.ob.lr_grad(self.ob.lr_loss(pulled)[0])
+        from tests import _valued_checker as V
+        wu = np.asarray(pulled, np.float32).reshape(len(self.ukeys))
+        loss, _ = V.forward_lr(self.rp, self.uidx, self.x, self.labels, wu, self.audit)
+        return V.gradient_w(self.rp, self.uidx, len(self.ukeys), self.x, loss, self.audit)[0]
+
+
+class Ranks:
+    """the pull / push rule of several ranks on one EvictingStore (tests/test_sharded_gloo.py's
+    _simulate): sequential — all ranks pull, then push in rank order; stale1 — the previous step's
+    pushes land after this step's pulls.  An eviction lands the outstanding pushes first, as
+    xf_sharded_evict flushes."""
+
+    def __init__(self, store, schedule):
+        assert schedule in ("sequential", "stale1")
+        self.store, self.schedule, self.outstanding = store, schedule, None
+
+    def flush(self):
+        if self.outstanding is not None:
+            for ukeys, g in self.outstanding:
+                self.store.s.push(ukeys, g)
+            self.outstanding = None
+
+    def step(self, raws, values=None):
+        """raws: one minibatch per rank (None: the rank has none this turn)"""
+        values = values or [None] * len(raws)
+        mbs = [_Prepared(r, v, self.store.audit) for r, v in zip(raws, values) if r is not None]
+        mbs = [m for m in mbs if len(m.ukeys)]
+        pulled = [self.store.s.pull(m.ukeys) for m in mbs]
+        self.flush()
+        done = [(m.ukeys, m.grad(p)) for m, p in zip(mbs, pulled)]
+        if self.schedule == "stale1":
+            self.outstanding = done
+        else:
+            for ukeys, g in done:
+                self.store.s.push(ukeys, g)
+
+    def evict(self, x):
+        self.flush()
+        return self.store.evict(x)
+
+    def export(self):
+        self.flush()
+        return self.store.export()
+
+
+def boundaries(epochs, every, last=False):
+    """the epochs (0-based) after which an eviction runs: every `every`-th boundary; last: after
+    the final epoch too (the worker's rule)"""
+    return [e for e in range(epochs)
+            if ((e + 1) % every == 0 and e + 1 < epochs) or (last and e + 1 == epochs)]
+
+
+def replay_stream(seed=43):
+    """T1 training minibatches of stream()'s shape, replayed epoch after epoch.  The reserved key
+    2^64 - 1 stands in about half the rows of every minibatch and the labels follow it (nine in
+    ten), so that it earns a weight under HYPER; key 0 stands in a few rows."""
+    rng = np.random.RandomState(seed)
+    out = []
+    for i in range(T1):
+        rowptr, keys, labels = synth(rng, 600, 12, 5000, 1.2 if i % 2 else None, True)
+        keys, labels = keys.copy(), labels.copy()
+        first = rowptr[:-1].astype(np.int64)
+        full = np.flatnonzero(np.diff(rowptr.astype(np.int64)) > 0)
+        with_spare = full[rng.rand(len(full)) < 0.5]
+        keys[first[with_spare]] = SPARE
+        has = np.zeros(len(labels), bool)
+        has[with_spare] = True
+        labels[:] = np.where(rng.rand(len(labels)) < 0.9, has, ~has).astype(np.int32)
+        with_zero = np.setdiff1d(full, with_spare)[:5]
+        keys[first[with_zero]] = 0
+        out.append((rowptr, keys, labels))
+    return out
+
+
+def replay_values(raw):
+    """a value per nonzero from {0.5, 1, 2} (products and sums stay exact)"""
+    rng = np.random.default_rng(len(raw[1]))
+    return rng.choice(np.array([0.5, 1.0, 2.0], np.float32), size=len(raw[1]))
+
+
+def replay_run(hyper, x, every, epochs=EPOCHS, valued=False, schedule=None, stream=None,
+               last=False, at=None):
+    """the evicting oracle over `epochs` epochs of the replay stream.  Evictions: at every
+    `every`-th boundary (last: after the final epoch too), none with every = 0; `at` names the
+    epochs (0-based) after which to evict instead.  schedule: None (one table, step after step)
+    or the one-rank exchange rule.
+    -> ([(kind, epoch, state, counts)], the store): ("epoch", e, export, None) after every epoch
+    and ("evict", e, export, (seen, dropped)) after every eviction"""
+    raws = replay_stream() if stream is None else stream
+    vals = [replay_values(r) for r in raws] if valued else [None] * len(raws)
+    st = EvictingStore(hyper)
+    rk = Ranks(st, schedule) if schedule else None
+    if at is None:
+        at = boundaries(epochs, every, last) if every else []
+    out = []
+    for e in range(epochs):
+        for raw, v in zip(raws, vals):
+            if rk:
+                rk.step([raw], [v])
+            else:
+                st.step(raw, v)
+        if rk:
+            rk.flush()     # (an export flushes: the state the GPU shows after the epoch)
+        out.append(("epoch", e, st.export(), None))
+        if e in at:
+            counts = rk.evict(x) if rk else st.evict(x)
+            out.append(("evict", e, st.export(), counts))
+    if valued:
+        from tests import _valued_checker as V
+        V.assert_exact(st.audit)
+    return out, st
+
+
+# ------------------------------------------------------------------ the worker
+def worker_text(tmp, two=False):
+    """the worker tests' files under `tmp`: a zipf text of just over 2 MiB (three 1 MiB blocks; two:
+    a second rank's of just over 1 MiB) and a test file"""
+    from tests._zipf_text import zipf_text
+    import os
+    texts = [zipf_text(27, (2 << 20) + (200 << 10))]
+    assert 2 << 20 < len(texts[0]) < 3 << 20
+    if two:
+        texts.append(zipf_text(26, (1 << 20) + (200 << 10)))
+    for r, text in enumerate(texts):
+        with open(os.path.join(str(tmp), "train-%05d" % r), "wb") as f:
+            f.write(text)
+    with open(os.path.join(str(tmp), "test-00000"), "wb") as f:
+        f.write(zipf_text(22, 60 << 10, 0.3))
+    return str(tmp)
+
+
+def worker_reference(d, epochs, every, x, lambda1=None, schedule="sequential", valued=False,
+                     ranks=1, cache=True):
+    """the evicting oracle doing what the worker does: the key-0 init push, then per epoch one
+    turn per 1 MiB block (a turn: one block of every rank that still has one, under the
+    schedule's rule), the flush at the end of the epoch, an eviction at every `every`-th boundary
+    and after the last epoch (every = 0: never), then the forward over the test file.
+    The worker checks the trainer (xf_sharded_check, which flushes) after the step of every block
+    it has just compiled — xf_worker.cc did so before eviction existed, see DESIGN.md "Replay
+    across evictions" — so under stale1 only the epochs that replay cache_ leave a Push
+    outstanding: the first epoch, and every epoch with cache_batches=0 (cache=False), lands its
+    Pushes after each turn.
+    -> dict: model (the state after the last eviction: what is saved), log [(epoch, seen,
+    dropped)], rows (trained), labels, pctr and metrics (of the test file), blocks (per rank),
+    states (the export after every epoch, before its eviction), store (after the forward)"""
+    import os
+    from oracle import pyoracle as O
+    from xflow_amd import capi
+    st = EvictingStore(dict(HYPER, lambda1=L1_WORKER if lambda1 is None else lambda1))
+    st.s.push(np.zeros(1, np.uint64), np.zeros(1, np.float32))
+    blocks = [list(capi.read_blocks(os.path.join(d, "train-%05d" % r), 1 << 20, values=valued))
+              for r in range(ranks)]
+    rk = Ranks(st, schedule)
+    log, rows, states = [], 0, []
+    for e in range(epochs):
+        for t in range(max(len(b) for b in blocks)):
+            mine = [b[t] if t < len(b) else None for b in blocks]
+            rk.step([None if m is None else (m[0], m[1], m[3]) for m in mine],
+                    [m[4] if valued and m is not None else None for m in mine])
+            rows += sum(len(m[3]) for m in mine if m is not None)
+            if e == 0 or not cache:
+                rk.flush()
+        rk.flush()
+        states.append(st.export())
+        if every and ((e + 1) % every == 0 or e + 1 == epochs):
+            log.append((e + 1,) + st.evict(x))
+    model = st.export()
+    labs, ps = [], []
+    for blk in capi.read_blocks(os.path.join(d, "test-00000"), 4 << 20, values=valued):
+        ps.append(st.predict((blk[0], blk[1], blk[3]), blk[4] if valued else None))
+        labs.append(blk[3])
+    if valued:
+        from tests import _valued_checker as V
+        V.assert_exact(st.audit)
+    lab, p = np.concatenate(labs), np.concatenate(ps)
+    return dict(model=model, log=log, rows=rows, labels=lab, pctr=p, metrics=O.auc_logloss(lab, p),
+                blocks=[len(b) for b in blocks], states=states, store=st)

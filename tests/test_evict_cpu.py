@@ -141,3 +141,158 @@ def test_abi_symbols_in_the_header_and_the_library():
     for cls, meth in ((capi.Table, "evict"), (capi.Sharded, "evict")):
         assert callable(getattr(cls, meth))
     assert callable(capi.evict_shape)
+
+
+# ------------------------------------------------------------------ replay across evictions
+# what gives tests/test_gpu_evict_replay.py its power: the evicting oracle alone, on the CPU
+HYPERS = {"HYPER": E.HYPER, "ALL_ZERO": E.HYPER_ALL_ZERO}
+REPLAY = [("HYPER", INF, 1), ("HYPER", INF, 2), ("HYPER", E.X_TRAIN, 1), ("HYPER", E.X_TRAIN, 2),
+          ("ALL_ZERO", INF, 1), ("ALL_ZERO", INF, 2)]
+_runs = {}
+
+
+def _replay(hname, x, every):
+    key = (hname, x, every)
+    if key not in _runs:
+        _runs[key] = E.replay_run(HYPERS[hname], x, every)[0]
+    return _runs[key]
+
+
+def _differ(a, b):
+    return any(x.shape != y.shape or not np.array_equal(E.bits(x), E.bits(y)) for x, y in zip(a, b))
+
+
+def test_replay_stream_carries_the_reserved_key_and_key_zero():
+    for rowptr, keys, labels in E.replay_stream():
+        assert len(labels) == 600 and len(np.unique(keys)) > 500
+        first = rowptr[:-1].astype(np.int64)[np.diff(rowptr.astype(np.int64)) > 0]
+        has = keys[first] == E.SPARE
+        assert 0.4 < has.mean() < 0.6 and (keys == E.SPARE).sum() == has.sum()
+        assert 1 <= (keys == 0).sum() <= 5
+        lab = labels[np.diff(rowptr.astype(np.int64)) > 0]
+        assert (lab[has] == 1).mean() > 0.8 and (lab[~has] == 1).mean() < 0.2
+
+
+@pytest.mark.parametrize("hname,x,every", REPLAY)
+def test_replayed_epochs_meet_evictions_that_bite(hname, x, every):
+    out = _replay(hname, x, every)
+    epoch_keys = np.unique(np.concatenate([r[1] for r in E.replay_stream()]))
+    evictions = [i for i, o in enumerate(out) if o[0] == "evict"]
+    assert [out[i][1] for i in evictions] == E.boundaries(E.EPOCHS, every) and evictions
+    assert len(E.boundaries(E.EPOCHS, every)) == {1: 3, 2: 1}[every]
+    for i in evictions:
+        (_, e, pre, _), (_, _, post, (seen, dropped)) = out[i - 1], out[i]
+        assert out[i - 1][0] == "epoch" and seen == len(pre[0]) == len(epoch_keys)
+        share = dropped / seen
+        print("%s x = %g every %d, after epoch %d: %d of %d dropped (%.1f %%)" % (
+            hname, x, every, e + 1, dropped, seen, 100 * share))
+        if hname == "ALL_ZERO":
+            assert share == 1.0 and len(post[0]) == 0
+        else:
+            assert 0.1 <= share <= 0.9
+        gone = np.setdiff1d(pre[0], post[0])
+        assert len(gone) == dropped and e + 1 < E.EPOCHS
+        assert np.isin(gone, epoch_keys).all()          # the next epoch touches every one again
+        # the reserved key meets both fates
+        assert (E.SPARE in post[0]) == (hname == "HYPER") and E.SPARE in pre[0]
+        if hname == "HYPER":
+            assert post[1][-1] != 0
+    if hname == "ALL_ZERO":
+        for o in out:
+            assert not E.bits(o[2][1]).any(), o[:2]     # every weight is +0
+    # a run that ignored re-entry would end elsewhere: the state without any eviction, as it is
+    # and filtered, is another one
+    final = out[-1][2]
+    plain = _replay(hname, 0.0, 0)[-1][2]
+    assert out[-1][0] == "epoch" and np.array_equal(final[0], plain[0])
+    assert _differ(final, plain)
+    if hname == "HYPER":
+        assert _differ(E.evict(final, x)[0], E.evict(plain, x)[0])
+    for o in out:
+        if o[0] == "epoch":
+            assert _differ(o[2], _replay(hname, 0.0, 0)[o[1]][2]) == (
+                o[1] > E.boundaries(E.EPOCHS, every)[0])
+
+
+def test_the_schedules_and_the_values_of_the_replay_bite_too():
+    """the one-rank exchange rules and the valued steps, x = inf at every boundary"""
+    for kw in (dict(schedule="sequential"), dict(schedule="stale1"), dict(valued=True)):
+        out = E.replay_run(E.HYPER, INF, 1, **kw)[0]
+        plain = E.replay_run(E.HYPER, 0.0, 0, **kw)[0]
+        counts = [o[3] for o in out if o[0] == "evict"]
+        assert len(counts) == 3 and all(0.1 <= d / s <= 0.9 for s, d in counts), (kw, counts)
+        assert _differ(out[-1][2], plain[-1][2]), kw
+    seq = E.replay_run(E.HYPER, INF, 1, schedule="sequential")[0]
+    one = _replay("HYPER", INF, 1)
+    for a, b in zip(seq, one):        # one rank, sequential: the plain step after step
+        E.same_state(a[2], b[2])
+    assert _differ(E.replay_run(E.HYPER, INF, 1, schedule="stale1")[0][-1][2], one[-1][2])
+
+
+def test_a_threshold_that_drops_nothing():
+    """x = X_NONE takes only rows whose n is 0: some after one epoch, none after two"""
+    assert E.replay_run(E.HYPER, E.X_NONE, 1)[0][1][3][1] > 0
+    out = E.replay_run(E.HYPER, E.X_NONE, 0, at=E.AT_NONE)[0]
+    plain = _replay("HYPER", 0.0, 0)
+    counts = [o[3] for o in out if o[0] == "evict"]
+    assert counts == [(len(plain[0][2][0]), 0)] * 2
+    E.same_state(out[-1][2], plain[-1][2])
+
+
+# ---- the worker tests' text
+WORKER = [(4, 1), (4, 2), (3, 2)]
+
+
+@pytest.fixture(scope="module")
+def text(tmp_path_factory):
+    return E.worker_text(tmp_path_factory.mktemp("evict_text"), two=True)
+
+
+@pytest.mark.parametrize("x", [INF, E.X_WORKER])
+@pytest.mark.parametrize("epochs,every", WORKER)
+def test_lambda1_of_the_worker_text_keeps_the_band(text, epochs, every, x):
+    r = E.worker_reference(text, epochs, every, x)
+    assert r["blocks"] == [3]
+    want = [e + 1 for e in range(epochs) if (e + 1) % every == 0 or e + 1 == epochs]
+    assert [e for e, _, _ in r["log"]] == want
+    for e, seen, dropped in r["log"]:
+        print("lambda1 = %g x = %g epochs %d every %d, epoch %d: %d of %d dropped (%.1f %%)" % (
+            E.L1_WORKER, x, epochs, every, e, dropped, seen, 100.0 * dropped / seen))
+        assert 0.1 <= dropped / seen <= 0.9
+    assert E.evict(r["model"], x)[2] == 0
+    plain = E.worker_reference(text, epochs, 0, 0.0)
+    assert plain["log"] == [] and plain["rows"] == r["rows"]
+    assert _differ(r["model"], E.evict(plain["model"], x)[0])
+    if x != INF:      # the finite threshold leaves zero rows the infinite one takes
+        inf = E.worker_reference(text, epochs, every, INF)
+        assert all(a[2] < b[2] for a, b in zip(r["log"], inf["log"]))
+
+
+def test_worker_text_with_values_and_on_two_ranks_keeps_the_band(text):
+    runs = [E.worker_reference(text, 4, 1, INF, valued=True)]
+    runs += [E.worker_reference(text, 3, 1, INF, schedule=s, ranks=2)
+             for s in ("sequential", "stale1")]
+    assert runs[1]["blocks"] == [3, 2]
+    for r in runs:
+        assert all(0.1 <= d / s <= 0.9 for _, s, d in r["log"]), r["log"]
+    plain = E.worker_reference(text, 3, 0, 0.0, schedule="stale1", ranks=2)
+    assert _differ(runs[2]["model"], E.evict(plain["model"], INF)[0])
+    # the schedules part ways in the epochs that replay (the first one flushes after every turn)
+    assert _differ(runs[1]["model"], runs[2]["model"])
+    assert not _differ(runs[1]["states"][0], runs[2]["states"][0])
+
+
+@pytest.mark.parametrize("epochs", [3, 4])
+def test_epoch_by_epoch_without_eviction_is_the_oracle_train_call(text, epochs):
+    """the worker reference steps the blocks epoch by epoch; without eviction that is one
+    O.train(..., epochs=N) call"""
+    from oracle import pyoracle as O
+    r = E.worker_reference(text, epochs, 0, 0.0)
+    s = O.Store(O.OPT_FTRL, 1)
+    s.set_ftrl(E.HYPER["alpha"], E.HYPER["beta"], E.L1_WORKER, E.HYPER["lambda2"])
+    with O.sum_mode(1):
+        rows = O.train(0, s, None, os.path.join(text, "train-00000"), epochs, 1 << 20)
+        lab, p = O.predict(0, s, None, os.path.join(text, "test-00000"))
+    assert rows == r["rows"]
+    assert np.array_equal(lab, r["labels"]) and p.tobytes() == r["pctr"].tobytes()
+    E.same_state(s.export(), r["store"].export())

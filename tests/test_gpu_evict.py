@@ -316,13 +316,18 @@ def _two_rank(rank, world, port, schedule, outdir, q):
         st = capi.Sharded(g, model="lr", optimizer="ftrl", capacity=1 << 14, schedule=schedule,
                           seed=7, **E.HYPER)
         raw = _rank_stream(rank)
+        out = {}
+
+        def stage(name):
+            for nm, a in zip("kwnz", st.w.export()):
+                out[name + "_" + nm] = a
         alive = []
         for i in range(E.T1):
             alive.append(st.compile(*raw[i]))
             st.step(alive[-1])
         st.check()
         hb = st.compile(*raw[E.T1])
-        out = {"p0": st.predict(hb)}
+        out["p0"] = st.predict(hb)
         g.barrier()                       # (every rank's Pulls of the predict have been served)
         for nm, a in zip("kwnz", st.w.export()):
             out["before_" + nm] = a
@@ -336,6 +341,18 @@ def _two_rank(rank, world, port, schedule, outdir, q):
         st.step(alive[0])                 # a minibatch compiled before the eviction, replayed
         st.check()
         out["end_k"] = st.w.export()[0]
+        stage("end")
+        # all the held minibatches replayed as a second epoch, a second eviction, a third epoch
+        for b in alive:
+            st.step(b)
+        st.check()
+        stage("epoch2")
+        out["counts2"] = np.array(st.evict(float("inf")), np.uint64)
+        stage("evicted2")
+        for b in alive:
+            st.step(b)
+        st.check()
+        stage("epoch3")
         np.savez(os.path.join(outdir, "rank%d.npz" % rank), **out)
         g.barrier()
         st.close()
@@ -343,6 +360,42 @@ def _two_rank(rank, world, port, schedule, outdir, q):
         q.put((rank, None))
     except Exception:
         q.put((rank, traceback.format_exc()))
+
+
+def _two_rank_oracle(schedule):
+    """what _two_rank does, on the evicting oracle under the schedule's pull / push rule: a step is
+    one minibatch of either rank; a predict flushes and pulls (inserts) its keys
+    -> {stage: state}, the two evictions' (seen, dropped)"""
+    raws = [_rank_stream(r) for r in range(2)]
+    rk = E.Ranks(E.EvictingStore(E.HYPER), schedule)
+    stages = {}
+
+    def turn(i):
+        rk.step([raws[0][i], raws[1][i]])
+
+    def predict():
+        rk.flush()
+        for r in range(2):
+            rk.store.s.pull(np.unique(raws[r][E.T1][1]))
+    for i in range(E.T1):
+        turn(i)
+    predict()
+    stages["before"] = rk.export()
+    c1 = rk.evict(INF)
+    stages["after"] = rk.export()
+    predict()
+    turn(E.T1 + 1)
+    turn(0)
+    stages["end"] = rk.export()
+    for i in range(E.T1):
+        turn(i)
+    stages["epoch2"] = rk.export()
+    c2 = rk.evict(INF)
+    stages["evicted2"] = rk.export()
+    for i in range(E.T1):
+        turn(i)
+    stages["epoch3"] = rk.export()
+    return stages, c1, c2
 
 
 @pytest.mark.parametrize("schedule", ["sequential", "stale1"])
@@ -366,6 +419,19 @@ def test_two_ranks_evict_their_shards(tmp_path, schedule):
         assert (int(p["counts"][0]), int(p["counts"][1])) == (s1, d1) and d1 > 0, r
         assert len(p["p0"]) == 300 and p["p0"].tobytes() == p["p1"].tobytes(), r
         assert len(p["end_k"]) > len(p["after_k"])
+    # every stage against the evicting oracle under the schedule's rule: the held minibatches
+    # replayed as a second epoch, a second eviction, a third epoch
+    stages, c1, c2 = _two_rank_oracle(schedule)
+    assert c1 == (seen, dropped)
+    for name in ("before", "after", "end", "epoch2", "evicted2", "epoch3"):
+        E.same_state(cat(name), stages[name], (schedule, name))
+    assert tuple(sum(int(p["counts2"][i]) for p in parts) for i in range(2)) == c2
+    assert 0 < c2[1] < c2[0]
+    # every dropped key of the replayed minibatches came back with the third epoch
+    gone = np.setdiff1d(stages["epoch2"][0], stages["evicted2"][0])
+    held = np.unique(np.concatenate([raw[1] for r in range(2) for raw in _rank_stream(r)[:E.T1]]))
+    back = gone[np.isin(gone, held)]
+    assert len(back) > 100 and np.isin(back, stages["epoch3"][0]).all()
 
 
 def _owner_refused(port, q):
@@ -491,7 +557,21 @@ def test_worker_evict_every_and_the_final_eviction(data, capfd):
     # evicts at every boundary but the first, whose dropped keys come back as first touches too
     every, _, mdl_b = _worker(data, "every1", epochs=3, evict_every=1, evict_n="inf")
     assert every.metric("rows_trained") == ev.metric("rows_trained")
-    assert E.evict(_model(data, mdl_b)[1], INF)[2] == 0
+    m_b = _model(data, mdl_b)[1]
+    assert E.evict(m_b, INF)[2] == 0
+    # both runs against the evicting oracle stepping the sample's one block epoch by epoch
+    lines_b = [ln for ln in capfd.readouterr().out.split("\n") if ln.startswith("evict epoch ")]
+    for x, saved, got_lines, k in ((ev, m, lines, 2), (every, m_b, lines_b, 1)):
+        ref = E.worker_reference(str(data), 3, k, INF, lambda1=E.L1)
+        assert ref["blocks"] == [1]
+        E.same_state(saved, ref["model"], k)
+        ll, auc, tp, fp = ref["metrics"]
+        assert (np.float32(x.metric("logloss_ref")), np.float32(x.metric("auc"))) == \
+            (np.float32(ll), np.float32(auc))
+        assert (x.metric("tp"), x.metric("fp"), x.metric("rows_trained")) == (tp, fp, ref["rows"])
+        assert x.metric("evict_seen") == sum(s for _, s, _ in ref["log"])
+        assert x.metric("evict_dropped") == sum(d for _, _, d in ref["log"])
+        assert got_lines == ["evict epoch %d: rows = %d dropped = %d" % l for l in ref["log"]]
 
 
 def test_worker_refusals(data):
