@@ -1077,6 +1077,107 @@ int xf_sharded_progress_read(xf_sharded *st, uint64_t *counts, uint64_t *other, 
                              int merged);
 int xf_sharded_last_loss(xf_sharded *st, xf_sbatch *b, float *loss, size_t R);
 
+/* ---------------------------------------------------------------- sliced progressive validation */
+/* Progressive validation's figures per value of ONE field (per site, advertiser, slot ...; the
+ * FTRL paper's metrics by slice; not in the reference): where is the model miscalibrated, which
+ * slice carries the loss.  A stage names every row's slice, a device table adds per slice.  The
+ * device only adds integers, so its result depends on nothing but the rows' losses, labels and
+ * ids and is compared with ==; every floating-point figure is formed on the host.
+ * Slice id.  id[r] = the key of the lowest-position nonzero of row r whose fgid == F;
+ * XF_SLICE_NONE = UINT64_MAX for a row without one.  A real key equal to that value is counted
+ * with `none` (one key in 2^64).  A row whose offsets descend or leave the arrays counts as empty,
+ * as in the other stages.  The id depends on nothing else: not the ingest path, the launch shape
+ * or the block boundaries.
+ * xf_slices_extract_dev: device arrays (d_rowptr row-relative u32, R + 1; d_keys, d_fgid NNZ), one
+ * launch on `stream` (none with R = 0), no wait; *d_id_out: R ids in a device array owned by the
+ * object, valid until its next extract.  The inputs pass through unchanged.  xf_slices_extract: the
+ * reader's host arrays and a row slice, uploaded (rowptr rebased to u32) as xf_cross_apply does —
+ * one implementation, the device one.
+ * Counters.  XF_SLICE_WORDS = 7 64-bit words a slice: n[2], qsum[2], llsum[2] (class 0 = label 0
+ * first) and other.  With rank = xf_progress_rank(loss), cls = (label != 0), q = |loss|:
+ *   rank == XF_PROGRESS_RANKS (NaN, q > 1): other += 1, nothing else
+ *   otherwise: n[cls] += 1; qsum[cls] += (uint32)(q * 2^31) — an fp32 multiply by a power of two
+ *   and a truncating conversion, exact; llsum[cls] += ll_fix[rank]
+ *   ll_fix[rank] = (uint32) llrint(term(rank) * 2^24), term the row term xf_progress_summary gives
+ *   that rank (one definition, shared).  The library builds the XF_PROGRESS_RANKS words once per
+ *   object and uploads them (1 MB); xf_slices_terms exports them (host code).
+ * Table.  Open-addressed, 2^b entries of (key, 7 words) = 64 bytes, b in 2 .. 26, empty =
+ * UINT64_MAX.  Home slot xf_slices_home(key, b) = mix64(key) >> (64 - b), mix64 as for admission
+ * (one definition for host and device; 0 for b outside 2 .. 26); linear probing with wrap, probe
+ * limit min(2^b, 128).  One `none` entry and one `overflow` entry sit beside the table: a row whose
+ * key finds neither itself nor an empty slot within the limit is counted in `overflow`.  Always:
+ * the sum of every entry, `none` and `overflow` equals the counters of the whole stream, and a
+ * resident key's counters are exactly that key's.  Per-slice figures are complete exactly when
+ * `overflow` is all zero.  The table does not grow and is not rehashed.
+ * xf_slices_accumulate_dev: R rows of device arrays, one launch on `stream` (none with R = 0), no
+ * wait.  xf_slices_read: compacts the occupied entries on the device in the order of the stream of
+ * the last accumulate and copies out up to `cap` of them — 8 words each: the key, then the seven —
+ * sorted by key ascending, with *n = the occupied entries and none[7] / overflow[7] (either may be
+ * NULL); one wait.  entries == NULL: only *n, none and overflow (reset must be 0).  *n > cap:
+ * XF_EINVAL, nothing reset.  reset != 0: the table is emptied after the copy (a second wait).
+ * xf_slices_launches: the accumulate launches since the library was loaded.  xf_slices_shape:
+ * {rows of an accumulate workgroup, entries and probes of its LDS table, the global probe limit's
+ * cap, rows of an extract workgroup}, for the tests that aim at the edges.
+ * Summary (host, no GPU), per slice in fp64, w the weight of a negative as in xf_progress_summary:
+ *   rows    = n1 + w n0
+ *   ctr     = n1 / rows
+ *   pctr    = ((n1 2^31 - qsum1) + w qsum0) / 2^31 / rows     (n1 2^31 - qsum1 in exact integers)
+ *   logloss = (llsum1 + w llsum0) / 2^24 / rows
+ *   other   = other (rows, unweighted: they have no class)
+ * logloss lies within logloss_bound = progress's bound + 2^-25 (the rounding of a fixed-point
+ * term) of the fp64 mean of -log1p(-q) over the slice's rows outside the saturated bucket; pctr
+ * within pctr_bound = 2^-31 (the truncation, a row) of the weighted mean of the rows' p.  No rows:
+ * every mean is NaN; the call succeeds.  Per-slice AUC is out of scope.
+ * Tap.  xf_workspace_slices(ws, s) attaches a slices object to a workspace (NULL: off, the
+ * default; the caller keeps s alive); xf_workspace_slice_ids(ws, d_id, R) names the ids of the
+ * NEXT training step's rows (a device array the caller keeps alive until that step has run; row r
+ * of the minibatch as it was compiled).  The step accumulates right after progressive
+ * validation's accumulate, on the same unweighted losses, and forgets the ids; a step without ids
+ * accumulates nothing, as does one whose R differs from the ids' (XF_EINVAL naming both).  Needs a
+ * progress attached (XF_EINVAL otherwise, at the step).  With nothing attached a step is launch
+ * for launch what it was; with one attached its tables and outputs are bit for bit the same.
+ * xf_sharded_slices(st, enable, F, b): the trainer owns one (created at 1, freed at 0); needs
+ * xf_sharded_progress on, and inherits its refusals: XF_EINVAL on a several-rank trainer on
+ * XF_SCHEDULE_OWNER / _OWNER_STALE1.  xf_sbatch_set_slices(b, d_id, R) copies the ids of this
+ * rank's R rows, in the order of the trainer's stream, into memory the minibatch owns, so a cached
+ * minibatch replays with its ids (NULL: none); a step on a minibatch without ids counts no slice.
+ * Every step path hands the tap its labels in the minibatch's row order, the order of the ids.
+ * Several ranks: each rank counts its own rows.  xf_sharded_slices_read: flushes, then as
+ * xf_slices_read on this rank's table; merged != 0: COLLECTIVE, every rank's compacted entries to
+ * every rank (xf_group_allgather_host), merged by key — the same list on every rank, which may be
+ * longer than one table — with none and overflow summed; reset empties this rank's table. */
+#define XF_SLICE_NONE 0xFFFFFFFFFFFFFFFFull
+#define XF_SLICE_WORDS 7
+typedef struct xf_slices xf_slices;
+typedef struct {
+  double rows, other, ctr, pctr, logloss, logloss_bound, pctr_bound;
+} xf_slice_metrics;
+uint64_t xf_slices_home(uint64_t key, int log2_slots);
+int xf_slices_terms(uint32_t *out);
+int xf_slices_check(int64_t field, int64_t log2_slots);
+int xf_slices_summary(const uint64_t *words, float neg_weight, xf_slice_metrics *out);
+int xf_slices_create(xf_slices **out, int32_t field, int log2_slots);
+int xf_slices_destroy(xf_slices *s);
+int xf_slices_params(const xf_slices *s, int32_t *field, int *log2_slots);
+int xf_slices_extract_dev(xf_slices *s, const uint64_t *d_keys, const int32_t *d_fgid,
+                          const uint32_t *d_rowptr, uint32_t R, uint32_t NNZ, void *stream,
+                          const uint64_t **d_id_out);
+int xf_slices_extract(xf_slices *s, const uint64_t *rowptr, const uint64_t *keys,
+                      const int32_t *fgid, size_t row_begin, size_t row_end, void *stream,
+                      const uint64_t **d_id_out, uint32_t *R_out);
+int xf_slices_accumulate_dev(xf_slices *s, const float *d_loss, const int32_t *d_labels,
+                             const uint64_t *d_id, uint32_t R, void *stream);
+int xf_slices_read(xf_slices *s, uint64_t *entries, uint64_t cap, uint64_t *n, uint64_t *none,
+                   uint64_t *overflow, int reset);
+uint64_t xf_slices_launches(void);
+void xf_slices_shape(uint32_t out[5]);
+int xf_workspace_slices(xf_workspace *ws, xf_slices *s);
+int xf_workspace_slice_ids(xf_workspace *ws, const uint64_t *d_id, uint32_t R);
+int xf_sharded_slices(xf_sharded *st, int enable, int32_t field, int log2_slots);
+int xf_sbatch_set_slices(xf_sbatch *b, const uint64_t *d_id, uint32_t R);
+int xf_sharded_slices_read(xf_sharded *st, uint64_t *entries, uint64_t cap, uint64_t *n,
+                           uint64_t *none, uint64_t *overflow, int reset, int merged);
+
 /* ---------------------------------------------------------------- feature crosses      */
 /* Crossed features as a GPU stage ahead of the key build (not in the reference).  Like admission
  * and negative subsampling it works on a minibatch's CSR arrays and its result goes to any *_dev
@@ -1207,7 +1308,22 @@ int XFDestroy(void **h);
  *        saturated / other; a negative weighs 1 / neg_keep; not with schedule=owner / owner_stale1
  *        on several workers).  XFGetMetric: progress_logloss progress_auc progress_auc_slack
  *        progress_ctr progress_pctr progress_rows (the last epoch) progress_logloss_first
- *        progress_auc_first (epoch 0: the held-out figure) */
+ *        progress_auc_first (epoch 0: the held-out figure)
+ *        progress_by(F, a field id in 0 .. 2^31 - 1; default off: sliced progressive validation,
+ *        xf_slices_* — with progress=1, every TRAINING block's rows are named by the key of their
+ *        first nonzero of field F, after negative subsampling and before the cross; the ids travel
+ *        with the compiled minibatch, so replayed epochs count too; after the "progress epoch" line
+ *        rank 0 prints "progress slices epoch E: field = F slices = S rows = ... none_rows = ...
+ *        overflow_rows = ..." — weighted rows; a note when overflow is not empty — and the
+ *        progress_top heaviest slices by weighted rows, ties by key, each as "  key = 0x... rows =
+ *        ... ctr = ... pctr = ... logloss = ..."; core_num 1, key_build=gpu, parity=exact, not
+ *        with ingest=gpu (use ingest=gpu_fields), progress's own refusals; nothing is saved with
+ *        the model) progress_slots(b in 2 .. 26, default 16: every worker's table has 2^b entries
+ *        of 64 bytes) progress_top(N >= 0, default 10) progress_slices_out(PATH: rank 0 appends one
+ *        tab-separated line per slice and epoch, by key: epoch, key (0x...), n0, n1, other, ctr,
+ *        pctr, logloss).  XFGetMetric (the last epoch): slices slice_rows slice_none_rows
+ *        slice_overflow_rows (weighted rows; slice_rows = entries + none + overflow =
+ *        progress_rows) */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

@@ -313,6 +313,27 @@ SIGNATURES = {
     "xf_sharded_progress": (C.c_int, [vp, C.c_int]),
     "xf_sharded_progress_read": (C.c_int, [vp, u64p, u64p, C.c_int, C.c_int]),
     "xf_sharded_last_loss": (C.c_int, [vp, vp, f32p, C.c_size_t]),
+    "xf_slices_home": (C.c_uint64, [C.c_uint64, C.c_int]),
+    "xf_slices_terms": (C.c_int, [C.POINTER(C.c_uint32)]),
+    "xf_slices_check": (C.c_int, [C.c_int64, C.c_int64]),
+    "xf_slices_summary": (C.c_int, [u64p, C.c_float, vp]),
+    "xf_slices_create": (C.c_int, [C.POINTER(vp), C.c_int32, C.c_int]),
+    "xf_slices_destroy": (C.c_int, [vp]),
+    "xf_slices_params": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int)]),
+    "xf_slices_extract_dev": (C.c_int, [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp,
+                                        C.POINTER(vp)]),
+    "xf_slices_extract": (C.c_int, [vp, u64p, u64p, i32p, C.c_size_t, C.c_size_t, vp,
+                                    C.POINTER(vp), C.POINTER(C.c_uint32)]),
+    "xf_slices_accumulate_dev": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp]),
+    "xf_slices_read": (C.c_int, [vp, u64p, C.c_uint64, u64p, u64p, u64p, C.c_int]),
+    "xf_slices_launches": (C.c_uint64, []),
+    "xf_slices_shape": (None, [C.POINTER(C.c_uint32)]),
+    "xf_workspace_slices": (C.c_int, [vp, vp]),
+    "xf_workspace_slice_ids": (C.c_int, [vp, vp, C.c_uint32]),
+    "xf_sharded_slices": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int]),
+    "xf_sbatch_set_slices": (C.c_int, [vp, vp, C.c_uint32]),
+    "xf_sharded_slices_read": (C.c_int, [vp, u64p, C.c_uint64, u64p, u64p, u64p, C.c_int,
+                                         C.c_int]),
     "xf_cross_key": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "xf_cross_parse": (C.c_int, [C.c_char_p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
     "xf_cross_create": (C.c_int, [C.POINTER(vp), i32p, i32p, C.c_int, C.c_int32]),
@@ -948,6 +969,149 @@ class Progress:
         return progress_summary(counts, other, neg_weight)
 
 
+SLICE_NONE = 2**64 - 1
+SLICE_WORDS = 7
+SLICE_NAMES = ("n0", "n1", "qsum0", "qsum1", "llsum0", "llsum1", "other")
+
+
+class SliceMetrics(C.Structure):
+    _fields_ = [(n, C.c_double) for n in
+                ("rows", "other", "ctr", "pctr", "logloss", "logloss_bound", "pctr_bound")]
+
+
+def slices_home(key, log2_slots):
+    """the home slot of a slice's key in a table of 2^log2_slots entries (xf_slices_home; host
+    code, the kernel's own definition)"""
+    return int(lib().xf_slices_home(int(key) & (2**64 - 1), int(log2_slots)))
+
+
+def slices_terms():
+    """the fixed-point row terms ll_fix[rank], uint32 [PROGRESS_RANKS] (xf_slices_terms)"""
+    out = np.empty(PROGRESS_RANKS, np.uint32)
+    check(lib().xf_slices_terms(out.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out
+
+
+def slices_check(field, log2_slots):
+    """the parameter check of xf_slices_create without a device (raises XFError)"""
+    check(lib().xf_slices_check(int(field), int(log2_slots)))
+
+
+def slices_summary(words, neg_weight=1.0):
+    """xf_slices_summary (host code): a slice's seven words -> a dict of the metrics' fields"""
+    words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+    assert words.size == SLICE_WORDS
+    m = SliceMetrics()
+    check(lib().xf_slices_summary(_p(words, u64p), float(neg_weight), C.byref(m)))
+    return {n: getattr(m, n) for n, _ in SliceMetrics._fields_}
+
+
+def slices_launches():
+    return int(lib().xf_slices_launches())
+
+
+def slices_shape():
+    """{rows of an accumulate workgroup, entries and probes of its LDS table, the cap of the
+    global probe limit, rows of an extract workgroup}"""
+    out = (C.c_uint32 * 5)()
+    lib().xf_slices_shape(out)
+    return dict(zip(("rows", "slots", "probe", "global_probe", "extract_rows"), list(out)))
+
+
+def _slices_result(entries, n, none, overflow):
+    e = entries[:n]
+    return e[:, 0].copy(), e[:, 1:].copy(), none, overflow
+
+
+class Slices:
+    """Sliced progressive validation (xf_slices_*): progressive validation's counters per value
+    of field F, in a device table of 2^log2_slots entries.  extract() names the rows' slices,
+    accumulate() adds; attach it to a Workspace (Workspace.slices / slice_ids); read() returns
+    (keys ascending, words [n, 7], none [7], overflow [7])."""
+
+    home = staticmethod(slices_home)
+
+    def __init__(self, field, log2_slots=16):
+        require_gpu()
+        self.h = vp()
+        check(lib().xf_slices_create(C.byref(self.h), int(field), int(log2_slots)))
+        self.field, self.log2_slots = int(field), int(log2_slots)
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().xf_slices_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def params(self):
+        f, b = C.c_int32(), C.c_int()
+        check(lib().xf_slices_params(self.h, C.byref(f), C.byref(b)))
+        return f.value, b.value
+
+    def extract_dev(self, d_keys, d_fgid, d_rowptr, R, NNZ, stream=None):
+        """device pointers in (ints); the device pointer of the R ids out (owned by the object,
+        valid until its next extract, written in the order of `stream`)"""
+        out = vp()
+        check(lib().xf_slices_extract_dev(self.h, d_keys, d_fgid, d_rowptr, int(R), int(NNZ),
+                                          stream, C.byref(out)))
+        return out.value
+
+    def extract_host_dev(self, rowptr, keys, fgid, row_begin=0, row_end=None, stream=None):
+        """host arrays and a row slice in (uploaded); (device pointer of the ids, R) out"""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        fgid = np.ascontiguousarray(fgid, dtype=np.int32)
+        assert len(rowptr) >= 1 and len(fgid) == len(keys), "one field id per key"
+        row_end = len(rowptr) - 1 if row_end is None else row_end
+        if len(keys) == 0:
+            keys, fgid = np.zeros(1, np.uint64), np.zeros(1, np.int32)
+        out, R = vp(), C.c_uint32()
+        check(lib().xf_slices_extract(self.h, _p(rowptr, u64p), _p(keys, u64p), _p(fgid, i32p),
+                                      row_begin, row_end, stream, C.byref(out), C.byref(R)))
+        return out.value, R.value
+
+    def extract(self, rowptr, keys, fgid, row_begin=0, row_end=None):
+        """the ids of rows [row_begin, row_end) as a uint64 array (downloaded)"""
+        d, R = self.extract_host_dev(rowptr, keys, fgid, row_begin, row_end)
+        return self.download_ids(d, R)
+
+    @staticmethod
+    def download_ids(d_id, R):
+        check(lib().xf_stream_sync(None))
+        ids = np.zeros(R, np.uint64)
+        if R:
+            check(lib().xf_copy_to_host(ids.ctypes.data, d_id, ids.nbytes))
+        return ids
+
+    def accumulate(self, d_loss, d_labels, d_id, R, stream=None):
+        """device pointers (ints): R losses (f32), labels (i32) and ids (u64); one launch, no
+        wait"""
+        check(lib().xf_slices_accumulate_dev(self.h, d_loss, d_labels, d_id, int(R), stream))
+
+    def count(self):
+        """the occupied entries (a read that copies none of them)"""
+        n = C.c_uint64()
+        check(lib().xf_slices_read(self.h, None, 0, C.byref(n), None, None, 0))
+        return n.value
+
+    def read(self, reset=False):
+        cap = 1 << self.log2_slots if self.log2_slots <= 16 else max(self.count(), 1)
+        entries = np.zeros((cap, SLICE_WORDS + 1), np.uint64)
+        none, overflow = np.zeros(SLICE_WORDS, np.uint64), np.zeros(SLICE_WORDS, np.uint64)
+        n = C.c_uint64()
+        check(lib().xf_slices_read(self.h, _p(entries, u64p), cap, C.byref(n), _p(none, u64p),
+                                   _p(overflow, u64p), 1 if reset else 0))
+        return _slices_result(entries, n.value, none, overflow)
+
+
+def slice_ids(rowptr, keys, fgid, field, row_begin=0, row_end=None):
+    """the slice ids of the rows of host arrays for field `field`, computed on the GPU (a
+    throw-away Slices object's extract)"""
+    return Slices(field, 2).extract(rowptr, keys, fgid, row_begin, row_end)
+
+
 class Cross:
     """Feature crosses (xf_cross_*): apply() returns a minibatch with, behind every row's own
     nonzeros, one nonzero per listed pair of fields and per (member of the first, member of the
@@ -1504,6 +1668,17 @@ class Workspace:
         check(lib().xf_workspace_progress(self.h, p.h if p is not None else None))
         self._progress = p   # (the workspace holds a pointer to it)
 
+    def slices(self, s):
+        """attach a Slices (None: off, the default): a training step that was given its rows' ids
+        (slice_ids) adds them to the slices right after the progress has counted them"""
+        check(lib().xf_workspace_slices(self.h, s.h if s is not None else None))
+        self._slices = s
+
+    def slice_ids(self, d_id, R):
+        """the ids (a device pointer the caller keeps alive until the step has run) of the NEXT
+        training step's R rows; None: that step counts no slice"""
+        check(lib().xf_workspace_slice_ids(self.h, d_id, int(R)))
+
     def fetch(self, U, R):
         wu = np.empty(U, np.float32)
         loss = np.empty(R, np.float32)
@@ -1731,6 +1906,31 @@ class Sharded:
         check(lib().xf_sharded_progress_read(self.h, _p(counts, u64p), _p(other, u64p),
                                              1 if reset else 0, 1 if merged else 0))
         return counts, other
+
+    def set_slices(self, enable, field=0, log2_slots=16):
+        """sliced progressive validation on the trainer's training steps (xf_sharded_slices);
+        needs set_progress(True)"""
+        check(lib().xf_sharded_slices(self.h, 1 if enable else 0, int(field), int(log2_slots)))
+        self._slices_b = int(log2_slots)
+
+    def batch_slices(self, b, d_id, R):
+        """the ids of minibatch b's rows (xf_sbatch_set_slices: copied, in the order of
+        stream()); None: the minibatch counts no slice"""
+        check(lib().xf_sbatch_set_slices(b.h, d_id, int(R)))
+
+    def slices_read(self, reset=False, merged=False):
+        """(keys ascending, words [n, 7], none, overflow) of this rank; merged=True: COLLECTIVE,
+        the ranks' entries merged by key"""
+        n = C.c_uint64()
+        check(lib().xf_sharded_slices_read(self.h, None, 0, C.byref(n), None, None, 0,
+                                           1 if merged else 0))
+        cap = max(n.value, 1)
+        entries = np.zeros((cap, SLICE_WORDS + 1), np.uint64)
+        none, overflow = np.zeros(SLICE_WORDS, np.uint64), np.zeros(SLICE_WORDS, np.uint64)
+        check(lib().xf_sharded_slices_read(self.h, _p(entries, u64p), cap, C.byref(n),
+                                           _p(none, u64p), _p(overflow, u64p),
+                                           1 if reset else 0, 1 if merged else 0))
+        return _slices_result(entries, n.value, none, overflow)
 
     def last_loss(self, b):
         """the (weighted) losses the last step of minibatch b left (xf_sharded_last_loss)"""

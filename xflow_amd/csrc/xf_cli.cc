@@ -36,7 +36,10 @@ int main(int argc, char *argv[]) {
                  "[cross_fgid_base=N with fm_mode=field_aware]\n"
               << "progressive validation (per epoch: logloss and AUC of every training row under "
                  "the weights it met before it was trained on, counted on the GPU): append "
-                 "progress=1\n";
+                 "progress=1\n"
+              << "... and per value of one field (which site, advertiser or slot is miscalibrated "
+                 "or carries the loss): append progress_by=F [progress_slots=16 progress_top=10 "
+                 "progress_slices_out=PATH]\n";
     return 2;
   }
   if (const char *role = getenv("DMLC_ROLE")) {  // main.cc:22-26: ps::IsServer / scheduler

@@ -35,6 +35,7 @@
 #include "xf_fm_canonical.h"
 #include "xf_negsample.h"
 #include "xf_progress.h"
+#include "xf_slices.h"
 #include "xf_scratch.h"
 #include "xf_wave.h"
 
@@ -1608,6 +1609,12 @@ struct xf_workspace {
   // progressive validation (xf_workspace_progress; null: off): a training step counts its losses'
   // ranks after the forward has written them and before the weight above touches them (ws_tap)
   xf_progress *progress = nullptr;
+  // sliced progressive validation (xf_workspace_slices; null: off) and the slice ids of the next
+  // training step's rows (xf_workspace_slice_ids; null: that step counts no slices): ws_tap
+  // accumulates right after the progress and forgets the ids
+  xf_slices *slices = nullptr;
+  const uint64_t *slice_ids = nullptr;
+  uint32_t slice_R = 0;
   // the cells lr_step last ran over (compared, never dereferenced): a minibatch stepped twice in
   // a row has its entries where the step before left them, and nothing is fetched for it
   const xf_cells *last_cells = nullptr;
@@ -1858,11 +1865,37 @@ extern "C" int xf_workspace_progress(xf_workspace *ws, xf_progress *p) {
   return XF_OK;
 }
 
+extern "C" int xf_workspace_slices(xf_workspace *ws, xf_slices *s) {
+  XF_REQUIRE(ws, "xf_workspace_slices: null workspace");
+  ws->slices = s;
+  ws->slice_ids = nullptr;
+  return XF_OK;
+}
+
+extern "C" int xf_workspace_slice_ids(xf_workspace *ws, const uint64_t *d_id, uint32_t R) {
+  XF_REQUIRE(ws, "xf_workspace_slice_ids: null workspace");
+  XF_REQUIRE(!d_id || (ws->slices && ws->progress),
+             "xf_workspace_slice_ids: slice ids need a slices object and a progress attached "
+             "(xf_workspace_slices, xf_workspace_progress): the slices are counted where "
+             "progressive validation taps the losses");
+  ws->slice_ids = d_id;
+  ws->slice_R = d_id ? R : 0;
+  return XF_OK;
+}
+
 // between a training step's forward and whatever reads its losses: progressive validation counts
 // them as the forward left them, then the negatives take their weight (no launch for either when
 // nothing is attached and the weight is 1)
 static int ws_tap(xf_workspace *ws, const int32_t *labels, uint32_t R, hipStream_t s) {
   if (ws->progress) XF_TRY(xf::progress_accumulate(ws->progress, ws->loss, labels, R, s));
+  if (ws->progress && ws->slices && ws->slice_ids) {
+    const uint64_t *ids = ws->slice_ids;
+    ws->slice_ids = nullptr;  // (they name this step's rows only)
+    XF_REQUIRE(ws->slice_R == R,
+               "a training step of %u rows with the slice ids of %u rows (xf_workspace_slice_ids)",
+               R, ws->slice_R);
+    XF_TRY(xf::slices_accumulate(ws->slices, ws->loss, labels, ids, R, s));
+  }
   return xf::weigh_negatives(ws->loss, labels, R, ws->neg_weight, s);
 }
 // the LR steps on cells store the weighted loss from the finalize kernel — unless a progress is

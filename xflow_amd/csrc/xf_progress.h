@@ -37,6 +37,10 @@ XF_ADMIT_HD uint32_t progress_word(float loss, int32_t label) {
 }
 constexpr uint32_t kProgressWords = 2u * XF_PROGRESS_RANKS + 2u;
 
+// host only (xf_progress_host.cc): the row term the summary gives a row of that rank, rank in
+// 0 .. 2C — the one definition, also behind the sliced counters' fixed-point terms (xf_slices.h)
+double progress_term(uint32_t rank);
+
 }  // namespace xf
 
 struct xf_progress;

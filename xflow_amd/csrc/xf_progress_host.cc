@@ -33,6 +33,12 @@ double bucket_m(uint32_t rank) {
 
 }  // namespace
 
+// the row term of a bucket: -log1p(-m) below C, -ln(m) from C on (m: the bucket's representative)
+double xf::progress_term(uint32_t rank) {
+  const double m = bucket_m(rank);
+  return rank < C ? -log1p(-m) : -log(m);
+}
+
 extern "C" uint32_t xf_progress_rank(float loss) { return xf::progress_rank(loss); }
 
 extern "C" int xf_progress_summary(const uint64_t *counts, const uint64_t *other, float neg_weight,
@@ -48,7 +54,7 @@ extern "C" int xf_progress_summary(const uint64_t *counts, const uint64_t *other
   for (uint32_t r = 0; r < RANKS; ++r) {
     if (!pos[r] && !neg[r]) continue;
     const double m = bucket_m(r);
-    const double term = r < C ? -log1p(-m) : -log(m);
+    const double term = xf::progress_term(r);
     const double q = r < C ? m : 1.0 - m;  // the error mass; p = q for a negative, 1 - q for a positive
     const double pq = r < C ? 1.0 - m : m;
     P += pos[r];

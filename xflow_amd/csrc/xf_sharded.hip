@@ -53,6 +53,7 @@
 #include "xf_fm_canonical.h"
 #include "xf_negsample.h"
 #include "xf_progress.h"
+#include "xf_slices.h"
 #include "xf_scratch.h"
 
 namespace xf {
@@ -218,6 +219,10 @@ struct xf_sbatch {
   uint32_t o_total = 0;                      // rows of all workers
   uint32_t o_rows_all = 0;                   // the same, LR (rows1 on the host)
   Dev<float> lv, lv_rep, lv_recv, vsum_recv;
+  // sliced progressive validation: the slice ids of this worker's rows (xf_sbatch_set_slices), the
+  // minibatch's own copy, so that a cached minibatch replays with its ids
+  Dev<uint64_t> slice_ids;
+  bool has_slices = false;
 };
 
 struct xf_sharded {
@@ -234,6 +239,7 @@ struct xf_sharded {
   int fm_fields = 0;                       // (what xf_sharded_set_fm_fields last set)
   float neg_weight = 1.0f;                 // (what xf_sharded_set_neg_weight last set)
   xf_progress *progress = nullptr;         // progressive validation (xf_sharded_progress); null: off
+  xf_slices *slices = nullptr;             // its slices (xf_sharded_slices); null: off
   uint64_t seen_upper = 0;     // world 1: host-side upper bound on the keys in the table
   Dev<double> partial;         // LR forward scratch
   // the owner-compute compile's staging: the worker's nonzeros grouped by owner (sent from
@@ -395,8 +401,11 @@ int front_pull(xf_sharded *st, xf_sbatch *b, StepBuf &B, hipStream_t s) {
 
 // between the forward and the gradient of a training step: progressive validation counts the
 // losses as the forward left them, then the negatives take their weight
-int front_tap(xf_sharded *st, float *loss, const int32_t *labels, uint32_t R, hipStream_t s) {
+int front_tap(xf_sharded *st, const xf_sbatch *b, float *loss, const int32_t *labels, uint32_t R,
+              hipStream_t s) {
   if (st->progress) XF_TRY(xf::progress_accumulate(st->progress, loss, labels, R, s));
+  if (st->progress && st->slices && b->has_slices)  // (a minibatch without ids counts no slices)
+    XF_TRY(xf::slices_accumulate(st->slices, loss, labels, b->slice_ids.p, R, s));
   return xf::weigh_negatives(loss, labels, R, st->neg_weight, s);
 }
 
@@ -419,7 +428,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
   if (!fm && hb->valued) {
     // valued LR: the w half of the canonical step (xf_valued.hip), no cells
     XF_TRY(xf::val_lr_forward(&v, hb->d_xval, B.wu.p, B.loss.p, d_pctr, s));
-    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
+    if (want_grad) XF_TRY(front_tap(st, b, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -430,7 +439,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     XF_TRY(B.S.reserve((size_t)b->R * k));
     XF_TRY(xf::fmc_forward(&v, k, B.wu.p, B.vu.p, B.S.p, B.loss.p, d_pctr,
                            hb->valued ? hb->d_xval : nullptr, s));
-    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
+    if (want_grad) XF_TRY(front_tap(st, b, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -443,7 +452,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     const int F = st->fm_fields, kf = k / F;  // (k: the v rows' width, fields x kf)
     XF_TRY(xf::ffm_forward(&v, kf, F, B.wu.p, B.vu.p, hb->d_xfg, B.loss.p, d_pctr,
                            hb->valued ? hb->d_xval : nullptr, s));
-    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
+    if (want_grad) XF_TRY(front_tap(st, b, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -457,7 +466,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     XF_TRY(st->partial.reserve(xf::cells_partial_doubles(b->cells)));
     XF_TRY(xf::cells_lr_forward(b->cells, B.wu.p, b->b->view.labels, st->partial.p, B.loss.p,
                                 d_pctr, s));
-    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
+    if (want_grad) XF_TRY(front_tap(st, b, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -471,7 +480,7 @@ int front_compute(xf_sharded *st, xf_sbatch *b, StepBuf &B, float *d_pctr, bool 
     } else {
       XF_TRY(xf_fm_forward_dev(&b->b->view, k, B.wu.p, B.vu.p, B.loss.p, d_pctr, B.vsum.p, s));
     }
-    if (want_grad) XF_TRY(front_tap(st, B.loss.p, v.labels, b->R, s));
+    if (want_grad) XF_TRY(front_tap(st, b, B.loss.p, v.labels, b->R, s));
     XF_MARK(kEvForward + 1);
     if (want_grad) {
       XF_TRY(B.g.reserve(b->U));
@@ -1416,6 +1425,7 @@ extern "C" int xf_sharded_destroy(xf_sharded *st) {
   if (st->h_counts) (void)hipHostFree(st->h_counts);
   if (st->ws) xf_workspace_destroy(st->ws);
   if (st->progress) xf_progress_destroy(st->progress);
+  if (st->slices) xf_slices_destroy(st->slices);
   if (st->tw) xf_table_destroy(st->tw);
   if (st->tv) xf_table_destroy(st->tv);
   if (st->main) (void)hipStreamDestroy(st->main);
@@ -1857,6 +1867,8 @@ extern "C" int xf_sharded_step(xf_sharded *st, xf_sbatch *b) {
   XF_REQUIRE(st && b, "xf_sharded_step: null argument");
   XF_ALIVE(st);
   if (st->fused) {
+    if (st->slices)  // (the ids of this step's rows, or none: the workspace forgets them after it)
+      XF_TRY(xf_workspace_slice_ids(st->ws, b->has_slices ? b->slice_ids.p : nullptr, b->R));
     if (st->cfg.model == 0) return xf_lr_step(st->tw, b->b, st->ws, st->main);
     return xf_fm_step(st->tw, st->tv, b->b, st->ws, st->main);
   }
@@ -2111,6 +2123,8 @@ extern "C" int xf_sharded_progress(xf_sharded *st, int enable) {
   if (enable && !st->progress) {
     XF_TRY(xf_progress_create(&st->progress));
   } else if (!enable && st->progress) {
+    XF_REQUIRE(!st->slices, "xf_sharded_progress: sliced progressive validation is on "
+               "(xf_sharded_slices): switch that off first");
     XF_TRY(xf_sharded_flush(st));
     xf_progress_destroy(st->progress);
     st->progress = nullptr;
@@ -2138,6 +2152,108 @@ extern "C" int xf_sharded_progress_read(xf_sharded *st, uint64_t *counts, uint64
     for (int r = 0; r < st->world; ++r) sum += all[(size_t)r * n + i];
     (i < nc ? counts[i] : other[i - nc]) = sum;
   }
+  return XF_OK;
+}
+
+// sliced progressive validation: beside the progress, tapped at the same two places
+extern "C" int xf_sharded_slices(xf_sharded *st, int enable, int32_t field, int log2_slots) {
+  XF_REQUIRE(st, "xf_sharded_slices: null trainer");
+  XF_ALIVE(st);
+  if (enable) {
+    XF_TRY(xf::slices_check_params("xf_sharded_slices", field, log2_slots));
+    XF_REQUIRE(st->fused || !owner_dataflow(st->cfg.schedule),
+               "xf_sharded_slices: sliced progressive validation on schedule %s: the owners' "
+               "finalize kernels form the loss where no tap reads it (use schedule sequential or "
+               "stale1)", schedule_name(st->cfg.schedule));
+    XF_REQUIRE(st->progress, "xf_sharded_slices: sliced progressive validation needs progressive "
+               "validation on (xf_sharded_progress): the slices are counted where it taps the losses");
+    XF_REQUIRE(!st->slices, "xf_sharded_slices: already on (switch it off first)");
+    XF_TRY(xf_slices_create(&st->slices, field, log2_slots));
+  } else if (st->slices) {
+    XF_TRY(xf_sharded_flush(st));
+    if (st->fused) XF_TRY(xf_workspace_slices(st->ws, nullptr));
+    xf_slices_destroy(st->slices);
+    st->slices = nullptr;
+  }
+  if (st->fused) XF_TRY(xf_workspace_slices(st->ws, st->slices));
+  return XF_OK;
+}
+
+extern "C" int xf_sbatch_set_slices(xf_sbatch *b, const uint64_t *d_id, uint32_t R) {
+  XF_REQUIRE(b, "xf_sbatch_set_slices: null batch");
+  XF_REQUIRE(!b->oc, "xf_sbatch_set_slices: a minibatch of the owner-compute dataflow: its losses "
+             "are formed at the owners, where no tap reads them");
+  b->has_slices = false;
+  if (!d_id) return XF_OK;
+  XF_REQUIRE(R == b->R, "xf_sbatch_set_slices: %u slice ids for a minibatch of %u rows", R, b->R);
+  if (R == 0) return XF_OK;
+  XF_TRY(b->slice_ids.reserve(R));
+  XF_HIP(hipMemcpyAsync(b->slice_ids.p, d_id, (size_t)R * 8, hipMemcpyDeviceToDevice,
+                        b->owner ? b->owner->main : nullptr));
+  b->has_slices = true;
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_slices_read(xf_sharded *st, uint64_t *entries, uint64_t cap, uint64_t *n,
+                                      uint64_t *none, uint64_t *overflow, int reset, int merged) {
+  XF_REQUIRE(st && n, "xf_sharded_slices_read: null argument");
+  XF_REQUIRE(st->slices, "xf_sharded_slices_read: sliced progressive validation is off "
+             "(xf_sharded_slices)");
+  XF_TRY(xf_sharded_flush(st));
+  if (!merged || !st->g || st->world <= 1)
+    return xf_slices_read(st->slices, entries, cap, n, none, overflow, reset);
+  XF_REQUIRE(entries || !reset,
+             "xf_sharded_slices_read: a read without entries only counts them and cannot reset");
+  // COLLECTIVE: every rank's compacted entries to every rank, merged by key
+  constexpr size_t E = XF_SLICE_WORDS + 1;
+  uint64_t mine_n = 0;
+  XF_TRY(xf_slices_read(st->slices, nullptr, 0, &mine_n, nullptr, nullptr, 0));
+  std::vector<uint64_t> counts((size_t)st->world);
+  XF_TRY(xf_group_allgather_host(st->g, &mine_n, 8, counts.data()));
+  const uint64_t most = *std::max_element(counts.begin(), counts.end());
+  const size_t per = ((size_t)most + 2) * E;  // a rank's entries (padded), its none, its overflow
+  std::vector<uint64_t> mine(per, 0), all(per * (size_t)st->world);
+  uint64_t got = 0;
+  XF_TRY(xf_slices_read(st->slices, mine.data(), mine_n, &got, mine.data() + (size_t)most * E + 1,
+                        mine.data() + ((size_t)most + 1) * E + 1, 0));
+  XF_REQUIRE(got == mine_n, "xf_sharded_slices_read: the table changed between two reads");
+  XF_TRY(xf_group_allgather_host(st->g, mine.data(), per * 8, all.data()));
+  struct Entry {
+    uint64_t w[E];
+  };
+  std::vector<Entry> merged_e;
+  uint64_t sum_none[XF_SLICE_WORDS] = {0}, sum_over[XF_SLICE_WORDS] = {0};
+  for (int r = 0; r < st->world; ++r) {
+    const uint64_t *base = all.data() + per * (size_t)r;
+    for (uint64_t i = 0; i < counts[(size_t)r]; ++i) {
+      Entry e;
+      std::copy(base + i * E, base + (i + 1) * E, e.w);
+      merged_e.push_back(e);
+    }
+    for (size_t w = 0; w < XF_SLICE_WORDS; ++w) {
+      sum_none[w] += base[(size_t)most * E + 1 + w];
+      sum_over[w] += base[((size_t)most + 1) * E + 1 + w];
+    }
+  }
+  std::stable_sort(merged_e.begin(), merged_e.end(),
+                   [](const Entry &a, const Entry &b) { return a.w[0] < b.w[0]; });
+  size_t m = 0;
+  for (size_t i = 0; i < merged_e.size(); ++i) {
+    if (m && merged_e[m - 1].w[0] == merged_e[i].w[0]) {
+      for (size_t w = 1; w < E; ++w) merged_e[m - 1].w[w] += merged_e[i].w[w];
+    } else {
+      merged_e[m++] = merged_e[i];
+    }
+  }
+  *n = m;
+  if (none) std::copy(sum_none, sum_none + XF_SLICE_WORDS, none);
+  if (overflow) std::copy(sum_over, sum_over + XF_SLICE_WORDS, overflow);
+  if (!entries) return XF_OK;
+  XF_REQUIRE(m <= cap,
+             "xf_sharded_slices_read: %zu merged entries do not fit an array of %llu; nothing was "
+             "reset", m, (unsigned long long)cap);
+  if (m) memcpy(entries, merged_e.data(), m * sizeof(Entry));
+  if (reset) XF_TRY(xf_slices_read(st->slices, mine.data(), mine_n, &got, nullptr, nullptr, 1));
   return XF_OK;
 }
 

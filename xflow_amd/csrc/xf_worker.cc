@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include "xf_worker.h"
+#include "xf_slices.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -54,6 +55,7 @@ Worker::~Worker() {
   if (admit_) xf_admit_destroy(admit_);
   if (sample_) xf_negsample_destroy(sample_);
   if (cross_) xf_cross_destroy(cross_);
+  if (slicer_) xf_slices_destroy(slicer_);
   if (sharded_) xf_sharded_destroy(sharded_);  // owns the tables
   if (group_) xf_group_destroy(group_);
 }
@@ -110,6 +112,10 @@ int Worker::create_tables() {
   if (fm_mode == XF_FM_FIELD_AWARE) XF_TRY(xf_sharded_set_fm_fields(sharded_, fields));
   if (fm_mode != XF_FM_REFERENCE) XF_TRY(xf_sharded_set_fm_mode(sharded_, fm_mode));
   if (progress) XF_TRY(xf_sharded_progress(sharded_, 1));
+  if (progress_by_set) {
+    XF_TRY(xf_sharded_slices(sharded_, 1, (int32_t)progress_by, progress_slots));
+    if (!slicer_) XF_TRY(xf_slices_create(&slicer_, (int32_t)progress_by, xf::kSlicesMinLog2));
+  }
   XF_TRY(xf_sharded_tables(sharded_, &table_w_, &table_v_));
   // One update() and one predict of a two-row minibatch on a private single-shard trainer: the
   // first launch of a kernel loads its code object and the builders size their scratch on first
@@ -135,6 +141,16 @@ int Worker::create_tables() {
     if (rc == XF_OK && neg_keep < 1.0f) rc = xf_sharded_set_neg_weight(warm, 1.0f / neg_keep);
     if (rc == XF_OK && progress) rc = xf_sharded_progress(warm, 1);  // (its kernel's first launch)
     if (rc == XF_OK) rc = compile_rows(warm, &b, 0, rp, keys, fg, vals, lab, 0, 2, 1);
+    if (rc == XF_OK && progress_by_set) {  // (the two slices kernels' first launches)
+      const int32_t sf[4] = {(int32_t)progress_by, 0, 0, (int32_t)progress_by};
+      const uint64_t *ids = nullptr;
+      uint32_t R = 0;
+      void *stream = nullptr;
+      rc = xf_sharded_slices(warm, 1, (int32_t)progress_by, xf::kSlicesMinLog2);
+      if (rc == XF_OK) rc = xf_sharded_stream(warm, &stream);
+      if (rc == XF_OK) rc = xf_slices_extract(slicer_, rp, keys, sf, 0, 2, stream, &ids, &R);
+      if (rc == XF_OK) rc = xf_sbatch_set_slices(b, ids, R);
+    }
     if (rc == XF_OK) rc = xf_sharded_step(warm, b);
     if (rc == XF_OK) rc = xf_sharded_predict(warm, b, p);
     if (b) xf_sbatch_free(b);
@@ -276,6 +292,94 @@ int Worker::evict_epoch(int epoch) {
   return XF_OK;
 }
 
+// Sliced progressive validation names a training block's rows on the GPU ahead of the key build,
+// from the nonzeros' field ids: core_num > 1 slices a block after it was read, the host key build
+// and the reference-order forward take host arrays, ingest=gpu hands out no fgid, and the counters
+// sit where progressive validation taps the losses.  All refused by name, before any rendezvous.
+int Worker::check_slices() const {
+  if (!progress_by_set) return XF_OK;
+  XF_REQUIRE(progress_by >= 0 && progress_by <= 0x7fffffffll,
+             "XFStartTrain: progress_by must be a field id in 0 .. 2147483647, not %lld",
+             progress_by);
+  XF_REQUIRE(progress_slots >= xf::kSlicesMinLog2 && progress_slots <= xf::kSlicesMaxLog2,
+             "XFStartTrain: progress_slots must be in %d .. %d (the slice table has 2^b entries), "
+             "not %d", xf::kSlicesMinLog2, xf::kSlicesMaxLog2, progress_slots);
+  XF_REQUIRE(progress_top >= 0, "XFStartTrain: progress_top must be >= 0, not %d", progress_top);
+  XF_REQUIRE(progress == 1, "XFStartTrain: progress_by=%lld together with progress=0: the slices "
+             "are counted where progressive validation taps the losses (use progress=1)",
+             progress_by);
+  XF_REQUIRE(!ingest_gpu, "XFStartTrain: progress_by=%lld together with ingest=gpu: the GPU "
+             "tokeniser hands out no fgid (use ingest=gpu_fields)", progress_by);
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: progress_by=%lld needs core_num=1, not core_num=%d",
+             progress_by, core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: progress_by=%lld together with key_build=host: the "
+             "rows are named on the GPU (use key_build=gpu)", progress_by);
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: progress_by=%lld together with "
+             "parity=reference_order: that mode builds its keys on the host", progress_by);
+  return XF_OK;
+}
+
+// the end of an epoch, after the progress line: the epoch's slices, merged over the ranks, and reset
+int Worker::slices_epoch(int epoch) {
+  if (!progress_by_set) return XF_OK;
+  constexpr size_t E = XF_SLICE_WORDS + 1;
+  const int merged = world > 1;
+  uint64_t n = 0;
+  XF_TRY(xf_sharded_slices_read(sharded_, nullptr, 0, &n, nullptr, nullptr, 0, merged));
+  std::vector<uint64_t> entries(std::max<uint64_t>(n, 1) * E);
+  uint64_t none[XF_SLICE_WORDS], overflow[XF_SLICE_WORDS];
+  XF_TRY(xf_sharded_slices_read(sharded_, entries.data(), std::max<uint64_t>(n, 1), &n, none,
+                                overflow, 1, merged));
+  float weight = 1.0f;
+  if (sample_) XF_TRY(xf_negsample_weight(sample_, &weight));
+  struct Row {
+    uint64_t key;
+    const uint64_t *w;
+    xf_slice_metrics m;
+  };
+  std::vector<Row> rows((size_t)n);
+  double total = 0.0;
+  for (size_t i = 0; i < (size_t)n; ++i) {
+    rows[i].key = entries[i * E];
+    rows[i].w = &entries[i * E + 1];
+    XF_TRY(xf_slices_summary(rows[i].w, weight, &rows[i].m));
+    total += rows[i].m.rows;
+  }
+  xf_slice_metrics mn, mo;
+  XF_TRY(xf_slices_summary(none, weight, &mn));
+  XF_TRY(xf_slices_summary(overflow, weight, &mo));
+  slices_last_[0] = (double)n;
+  slices_last_[1] = total + mn.rows + mo.rows;
+  slices_last_[2] = mn.rows;
+  slices_last_[3] = mo.rows;
+  slices_have_ = true;
+  if (rank != 0) return XF_OK;
+  const bool incomplete = mo.rows != 0 || mo.other != 0;
+  printf("progress slices epoch %d: field = %lld slices = %llu rows = %.12g none_rows = %.12g "
+         "overflow_rows = %.12g%s\n", epoch, progress_by, (unsigned long long)n, slices_last_[1],
+         mn.rows, mo.rows,
+         incomplete ? " (the table is full: per-slice figures are incomplete, raise progress_slots)"
+                    : "");
+  if (!progress_slices_out.empty()) {  // one line per slice, by key
+    FILE *f = fopen(progress_slices_out.c_str(), "a");
+    XF_REQUIRE(f, "progress_slices_out: cannot append to %s", progress_slices_out.c_str());
+    for (const Row &r : rows)
+      fprintf(f, "%d\t0x%016llx\t%llu\t%llu\t%llu\t%.17g\t%.17g\t%.17g\n", epoch,
+              (unsigned long long)r.key, (unsigned long long)r.w[0], (unsigned long long)r.w[1],
+              (unsigned long long)r.w[6], r.m.ctr, r.m.pctr, r.m.logloss);
+    fclose(f);
+  }
+  // the heaviest slices: weighted rows descending, ties by key ascending (the entries are by key)
+  std::stable_sort(rows.begin(), rows.end(),
+                   [](const Row &a, const Row &b) { return a.m.rows > b.m.rows; });
+  for (size_t i = 0; i < rows.size() && i < (size_t)progress_top; ++i)
+    printf("  key = 0x%016llx rows = %.12g ctr = %.6f pctr = %.6f logloss = %.6f\n",
+           (unsigned long long)rows[i].key, rows[i].m.rows, rows[i].m.ctr, rows[i].m.pctr,
+           rows[i].m.logloss);
+  fflush(stdout);
+  return XF_OK;
+}
+
 // the end of an epoch, after the flush: the epoch's counts, summed over the ranks, and reset
 int Worker::progress_epoch(int epoch) {
   if (!progress) return XF_OK;
@@ -335,7 +439,7 @@ int Worker::sample_dev(size_t first_row, const uint64_t **d_keys, const int32_t 
   void *stream = nullptr;
   XF_TRY(xf_sharded_stream(sharded_, &stream));
   return xf_negsample_apply_dev(sample_, sample_stream_, ordinal_ + first_row, *d_keys,
-                                fm_mode == XF_FM_FIELD_AWARE || cross_ ? *d_fgid : nullptr,
+                                fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? *d_fgid : nullptr,
                                 feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
                                 stream, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ);
 }
@@ -408,6 +512,15 @@ int Worker::compile_staged_dev(xf_sbatch **b, int update, const uint64_t *d_keys
                                const int32_t *d_fgid, const float *d_vals,
                                const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
                                uint32_t NNZ, int keep) {
+  // (training blocks only: the rows' slices, named before the cross adds its nonzeros; neither
+  // the cross nor admission drops or reorders rows, so the ids fit the minibatch compiled below)
+  const uint64_t *ids = nullptr;
+  const uint32_t id_rows = R;
+  if (slicer_ && update && R) {
+    void *stream = nullptr;
+    XF_TRY(xf_sharded_stream(sharded_, &stream));
+    XF_TRY(xf_slices_extract_dev(slicer_, d_keys, d_fgid, d_rowptr, R, NNZ, stream, &ids));
+  }
   if (cross_ && R) {
     void *stream = nullptr;
     XF_TRY(xf_sharded_stream(sharded_, &stream));
@@ -420,9 +533,12 @@ int Worker::compile_staged_dev(xf_sbatch **b, int update, const uint64_t *d_keys
     d_vals = fv;
   }
   if (admit_)
-    return compile_admitted_dev(b, update, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ,
-                                keep);
-  return compile_dev_arrays(b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
+    XF_TRY(compile_admitted_dev(b, update, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ,
+                                keep));
+  else
+    XF_TRY(compile_dev_arrays(b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep));
+  if (ids && *b) XF_TRY(xf_sbatch_set_slices(*b, ids, id_rows));
+  return XF_OK;
 }
 
 // rows [start, end) of host arrays through the cross: uploaded by the stage, then as above
@@ -454,7 +570,7 @@ int Worker::compile_sampled(xf_sbatch **b, const uint64_t *rowptr, const uint64_
   const uint32_t *fr = nullptr;
   uint32_t R = 0, NNZ = 0;
   XF_TRY(xf_negsample_apply(sample_, sample_stream_, ordinal_ + start, rowptr, keys,
-                            fm_mode == XF_FM_FIELD_AWARE || cross_ ? fgid : nullptr,
+                            fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? fgid : nullptr,
                             feature_values ? vals : nullptr, labels, start, end, stream, &fk, &ff,
                             &fv, &fr, &fl, &R, &NNZ));
   return compile_sampled_dev(b, fk, ff, fv, fr, fl, R, NNZ, keep);
@@ -471,6 +587,31 @@ int Worker::compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep) {
 int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
                          const uint64_t *keys, const int32_t *fgid, const float *vals,
                          const int32_t *labels, size_t start, size_t end, int keep) {
+  // (sliced progressive validation: training rows of this rank's own.  Under negative subsampling
+  // the block is on the device when its rows are named — compile_staged_dev; otherwise here)
+  if (slicer_ && !sample_ && update && trainer == sharded_ && rowptr && end > start)
+    return compile_sliced(b, rowptr, keys, fgid, vals, labels, start, end, keep);
+  return compile_rows_unsliced(trainer, b, update, rowptr, keys, fgid, vals, labels, start, end,
+                               keep);
+}
+
+int Worker::compile_sliced(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                           const int32_t *fgid, const float *vals, const int32_t *labels,
+                           size_t start, size_t end, int keep) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const uint64_t *ids = nullptr;
+  uint32_t R = 0;
+  XF_TRY(xf_slices_extract(slicer_, rowptr, keys, fgid, start, end, stream, &ids, &R));
+  XF_TRY(compile_rows_unsliced(sharded_, b, 1, rowptr, keys, fgid, vals, labels, start, end, keep));
+  if (*b) XF_TRY(xf_sbatch_set_slices(*b, ids, R));
+  return XF_OK;
+}
+
+int Worker::compile_rows_unsliced(xf_sharded *trainer, xf_sbatch **b, int update,
+                                  const uint64_t *rowptr, const uint64_t *keys, const int32_t *fgid,
+                                  const float *vals, const int32_t *labels, size_t start,
+                                  size_t end, int keep) {
   // (training blocks only — predict passes update 0 — and only rows of this rank's own)
   if (sample_ && update && trainer == sharded_ && rowptr && end > start)
     return compile_sampled(b, rowptr, keys, fgid, vals, labels, start, end, keep);
@@ -547,7 +688,7 @@ int Worker::compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr,
 // field-aware FM, the third field with feature values; neither: the tokeniser of ingest = gpu
 int Worker::set_ingest_fields(xf_ingest *g) {
   return xf_ingest_set_fields(g, ingest_fields && (fm_mode == XF_FM_FIELD_AWARE ||
-                                                   !cross_spec.empty()),
+                                                   !cross_spec.empty() || progress_by_set),
                               ingest_fields && feature_values);
 }
 
@@ -842,6 +983,7 @@ int Worker::batch_training() {
     const double tf0 = now_s();
     XF_TRY(xf_sharded_flush(sharded_));
     XF_TRY(progress_epoch(epoch));
+    XF_TRY(slices_epoch(epoch));
     // (evict_n: the eviction settles the table itself; after the LAST epoch too, so that the
     // model that is saved and scored holds no evictable row)
     if (evict_n > 0.0f && ((epoch + 1) % evict_every == 0 || epoch + 1 == epochs))
@@ -1185,6 +1327,8 @@ int Worker::train() {
   XF_TRY(check_negsample());
   XF_TRY(check_progress());
   progress_have_ = false;
+  XF_TRY(check_slices());
+  slices_have_ = false;
   XF_TRY(check_evict());
   XF_TRY(check_cross());
   XF_TRY(create_tables());
@@ -1323,6 +1467,21 @@ int Worker::set_param(const char *name, const char *value) {
     XF_REQUIRE(!strcmp(value, "0") || !strcmp(value, "1"),
                "XFSetParam: progress must be 0 or 1, not %s", value);
     progress = atoi(value);
+  } else if (n == "progress_by") {
+    XF_REQUIRE(!sharded_, "XFSetParam: progress_by cannot change after training started");
+    char *end = nullptr;
+    const long long f = strtoll(value, &end, 10);
+    XF_REQUIRE(end != value && *end == '\0', "XFSetParam: progress_by must be a field id, not '%s'",
+               value);
+    progress_by = f;
+    progress_by_set = true;
+  } else if (n == "progress_slots") {
+    XF_REQUIRE(!sharded_, "XFSetParam: progress_slots cannot change after training started");
+    progress_slots = atoi(value);
+  } else if (n == "progress_top") {
+    progress_top = atoi(value);
+  } else if (n == "progress_slices_out") {
+    progress_slices_out = value;
   } else if (n == "evict_n") {
     char *end = nullptr;
     const float x = strtof(value, &end);  // ("inf" parses: every zero-weight row goes)
@@ -1378,6 +1537,11 @@ int Worker::get_metric(const char *name, double *value) {
     uint64_t rows_kept = 0, seen = 0, kept = 0;
     if (sample_) XF_TRY(xf_negsample_stats(sample_, nullptr, &rows_kept, &seen, &kept));
     *value = (double)(n == "neg_seen" ? seen : n == "neg_kept" ? kept : rows_kept);
+  } else if (n == "slices" || n == "slice_rows" || n == "slice_none_rows" ||
+             n == "slice_overflow_rows") {
+    XF_REQUIRE(slices_have_, "XFGetMetric: %s: no epoch has been summarised (progress_by=F, after "
+               "XFStartTrain)", name);
+    *value = slices_last_[n == "slices" ? 0 : n == "slice_rows" ? 1 : n == "slice_none_rows" ? 2 : 3];
   } else if (n.rfind("progress_", 0) == 0) {
     const bool first = n.size() > 6 && n.compare(n.size() - 6, 6, "_first") == 0;
     const std::string what = n.substr(9, n.size() - 9 - (first ? 6 : 0));

@@ -107,6 +107,19 @@ class Worker {
   // over the ranks and reset, and rank 0 prints one line.  A negative weighs the sampler's weight.
   // Not with the owner-compute schedules on several workers (checked where training starts).
   int progress = 0;
+  // Sliced progressive validation (xf_slices.hip): progress_by = F (with progress = 1): every
+  // TRAINING block's rows are named by the key of their first nonzero of field F — after negative
+  // subsampling, which drops rows, and before the cross, so a slice is a value of an input field —
+  // the ids travel with the compiled minibatch (replayed with it), and the trainer counts per
+  // slice beside the progress.  At the end of each epoch rank 0 prints a summary line and the
+  // progress_top slices by weighted rows, and appends a TSV line per slice to progress_slices_out.
+  // core_num 1, key_build=gpu, parity=exact, not ingest=gpu (checked where training starts).
+  // Nothing travels with the model.
+  bool progress_by_set = false;
+  long long progress_by = -1;
+  int progress_slots = 16;
+  int progress_top = 10;
+  std::string progress_slices_out;
   // Table eviction (xf_evict.hip): evict_n = x > 0 (or inf): at the end of every evict_every-th
   // training epoch — in place of that boundary's defrag — and after the last one, ahead of
   // save_model and predict, every rank drops the keys of its shard whose w is 0 and whose n (the
@@ -123,6 +136,21 @@ class Worker {
   int progress_epoch(int epoch);  // COLLECTIVE at world > 1: read, merge, reset, summarise, print
   xf_progress_metrics progress_last_{}, progress_first_{};
   bool progress_have_ = false;
+  int check_slices() const;  // the refusals of progress_by, before any rendezvous
+  int slices_epoch(int epoch);  // COLLECTIVE at world > 1: read, merge, reset, summarise, print
+  // the stage that names the rows' slices (its own table is never fed: the trainer owns the
+  // counters, xf_sharded_slices); created with the tables
+  xf_slices *slicer_ = nullptr;
+  double slices_last_[4] = {0, 0, 0, 0};  // slices, rows, none rows, overflow rows of the last epoch
+  bool slices_have_ = false;
+  // rows [start, end) of host arrays with the feature on: the ids from the stage's own upload,
+  // then the compile the block would have taken, then the ids onto the minibatch
+  int compile_sliced(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                     const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
+                     size_t end, int keep);
+  int compile_rows_unsliced(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
+                            const uint64_t *keys, const int32_t *fgid, const float *vals,
+                            const int32_t *labels, size_t start, size_t end, int keep);
   int create_tables();
   int defrag_if_grown(int percent);
   int any_rank(bool mine, bool *any);
