@@ -1178,6 +1178,88 @@ int xf_sbatch_set_slices(xf_sbatch *b, const uint64_t *d_id, uint32_t R);
 int xf_sharded_slices_read(xf_sharded *st, uint64_t *entries, uint64_t cap, uint64_t *n,
                            uint64_t *none, uint64_t *overflow, int reset, int merged);
 
+/* ---------------------------------------------------------------- held-out validation  */
+/* A fixed, hash-chosen share of the training rows taken out of training, and a forward-only pass
+ * that counts their losses (not in the reference): a held-out figure per epoch that needs no second
+ * file.  Progressive validation is held out in the first epoch only; this is held out in every one.
+ * Split.  share: a float in [0, 1); seed; a 64-bit stream id per split; a 64-bit ordinal per row.
+ *   T = (uint64) floor((double)share * 2^32)
+ *   h(ordinal) = mix64(mix64(seed ^ stream ^ XF_HOLDOUT_SALT) + ordinal), mix64 as for admission
+ *     (64-bit wrapping); the salt makes the decision independent of xf_negsample_keep's on the same
+ *     seed and stream
+ *   a row is HELD iff (h >> 32) < T
+ * and on nothing else: not the label, the keys, the block boundaries, the ingest path or the launch
+ * shape.  xf_holdout_held is that decision as host code (0 or 1; 0 for a share outside [0, 1)),
+ * from the one definition the kernels use.
+ * One split = one minibatch: row i of the input has ordinal first_ordinal + i; the rows go, in
+ * order (stable), into two compacted minibatches, *train and *held, each with its own row-relative
+ * u32 rowptr (R + 1 offsets), its labels, keys and fgid / vals (NULL when not given).  R = 0,
+ * NNZ = 0 and rows without nonzeros are ordinary inputs; a part without rows has R = 0 and the one
+ * zero offset.  A row whose offsets descend or leave the arrays counts as empty, as in the other
+ * stages; nothing is read or written out of bounds.  XF_EINVAL when the rows' lengths sum past NNZ
+ * (rows that overlap).
+ * xf_holdout_split_dev: device arrays.  The parts are device arrays owned by the object, valid
+ * until its next split, written in the order of `stream`; both parts share one set of arrays, the
+ * held part at a 256-byte boundary behind the train part.  One wait for the stream, for the counts
+ * (none with R = 0).
+ * xf_holdout_split: the reader's host arrays and a row slice: uploads the slice (rowptr rebased to
+ * u32) and runs the same kernels — one implementation, the device one.
+ * xf_holdout_stats, summed over the splits: rows seen, rows held, nonzeros held.  The object
+ * allocates on the device only in its first split.  xf_holdout_shape: {rows of a tile, output
+ * nonzeros of a copy chunk, the alignment of the held part in elements}, for the tests.
+ * Early stop (host, no GPU).  xf_holdout_should_stop walks logloss[0 .. n), one value per validated
+ * epoch: an epoch improves iff L < best - delta (strict; the first value that is not NaN and below
+ * +inf improves); a NaN neither improves nor counts as an epoch without improvement.  *best (may be
+ * NULL): the index of the best epoch, -1 for none.  Returns 1 iff patience > 0, at least `patience`
+ * epochs since the best one did not improve, and logloss[n - 1] is not NaN; else 0 (also for
+ * n <= 0, a NULL curve, or a delta that is negative or NaN).
+ * Validate.  xf_lr_validate / xf_fm_validate: exactly the forward of xf_lr_predict / xf_fm_predict
+ * on every path those support — the same launches in the same order, the pulls insert unseen keys
+ * at first-touch state — but instead of copying pctr out they accumulate the losses the forward
+ * left (loss = sigmoid - label, one fp32 subtraction), unweighted, into `p`: one
+ * xf_progress_accumulate_dev launch, no host wait beyond those predict has.  Predict itself keeps
+ * every bit and launch and never accumulates.
+ * xf_sharded_holdout(st, enable): the trainer owns a SECOND xf_progress, apart from the one of
+ * xf_sharded_progress (created at 1, freed at 0).  XF_EINVAL on a several-rank trainer on
+ * XF_SCHEDULE_OWNER / _OWNER_STALE1 (the loss is formed inside the owners' finalize kernels), and
+ * xf_sharded_set_schedule to one of those two while it is on.
+ * xf_sharded_validate(st, b): xf_sharded_predict's forward of minibatch b, counted into that
+ * progress.  COLLECTIVE like predict — ranks without rows call it with an empty minibatch — and it
+ * flushes first.  xf_sharded_holdout_read: as xf_sharded_progress_read, of the second progress. */
+#define XF_HOLDOUT_SALT 0x6a09e667f3bcc909ull /* (the fraction bits of sqrt 2) */
+typedef struct xf_holdout xf_holdout;
+typedef struct {
+  const uint64_t *d_keys;
+  const int32_t *d_fgid;
+  const float *d_vals;
+  const uint32_t *d_rowptr;
+  const int32_t *d_labels;
+  uint32_t R, NNZ;
+} xf_holdout_part;
+int xf_holdout_create(xf_holdout **out, float share, uint64_t seed);
+int xf_holdout_destroy(xf_holdout *s);
+int xf_holdout_params(const xf_holdout *s, float *share, uint64_t *seed);
+int xf_holdout_held(uint64_t seed, uint64_t stream, uint64_t ordinal, float share);
+int xf_holdout_split_dev(xf_holdout *s, uint64_t stream_id, uint64_t first_ordinal,
+                         const uint64_t *d_keys, const int32_t *d_fgid, const float *d_vals,
+                         const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
+                         uint32_t NNZ, void *stream, xf_holdout_part *train,
+                         xf_holdout_part *held);
+int xf_holdout_split(xf_holdout *s, uint64_t stream_id, uint64_t first_ordinal,
+                     const uint64_t *rowptr, const uint64_t *keys, const int32_t *fgid,
+                     const float *vals, const int32_t *labels, size_t row_begin, size_t row_end,
+                     void *stream, xf_holdout_part *train, xf_holdout_part *held);
+int xf_holdout_stats(const xf_holdout *s, uint64_t *rows_seen, uint64_t *rows_held,
+                     uint64_t *nnz_held);
+void xf_holdout_shape(uint32_t out[3]);
+int xf_holdout_should_stop(const double *logloss, int n, int patience, double delta, int *best);
+int xf_lr_validate(xf_table *w, xf_batch *b, xf_workspace *ws, xf_progress *p);
+int xf_fm_validate(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws, xf_progress *p);
+int xf_sharded_holdout(xf_sharded *st, int enable);
+int xf_sharded_validate(xf_sharded *st, xf_sbatch *b);
+int xf_sharded_holdout_read(xf_sharded *st, uint64_t *counts, uint64_t *other, int reset,
+                            int merged);
+
 /* ---------------------------------------------------------------- feature crosses      */
 /* Crossed features as a GPU stage ahead of the key build (not in the reference).  Like admission
  * and negative subsampling it works on a minibatch's CSR arrays and its result goes to any *_dev
@@ -1323,7 +1405,27 @@ int XFDestroy(void **h);
  *        tab-separated line per slice and epoch, by key: epoch, key (0x...), n0, n1, other, ctr,
  *        pctr, logloss).  XFGetMetric (the last epoch): slices slice_rows slice_none_rows
  *        slice_overflow_rows (weighted rows; slice_rows = entries + none + overflow =
- *        progress_rows) */
+ *        progress_rows)
+ *        holdout(r in [0, 1), default 0 = off: held-out validation, xf_holdout_* — every TRAINING
+ *        block is split first, on the GPU: a row is held iff xf_holdout_held(seed, rank, the row's
+ *        index in this rank's training file, r) — no epoch in the stream: the same rows in every
+ *        epoch — and only the train part is trained on.  With neg_keep < 1 the sampler then
+ *        numbers the rows of the TRAIN part (a second running count): neg_keep's ordinal changes
+ *        only when both are on.  The held part goes through the cross and through admission
+ *        without being counted, after the block's train part, is compiled once and kept in HBM
+ *        whatever cache_batches says.  After the flush of every holdout_every-th epoch and of the
+ *        last one the held minibatches are scored with xf_sharded_validate, the counts are summed
+ *        over the workers and rank 0 prints "holdout epoch E: rows = ... logloss = ... (+- bound)
+ *        auc = ... (+- slack) ctr = ... pctr = ..." (E counts from 0, as progress's; unweighted).
+ *        core_num 1, key_build=gpu, parity=exact, not with schedule=owner / owner_stale1 on several
+ *        workers; nothing is saved with the model) holdout_every(E >= 1, default 1)
+ *        early_stop(P >= 0, default 0 = off; needs holdout: training ends after P validated epochs
+ *        without an improvement by xf_holdout_should_stop's rule; rank 0 prints "early stop after
+ *        epoch E: best epoch B logloss = ..."; that epoch counts as the last one — eviction's
+ *        after-the-last-epoch pass, save and predict follow) early_stop_delta(d >= 0, default 0).
+ *        XFGetMetric: holdout_rows holdout_logloss holdout_auc holdout_auc_slack holdout_ctr
+ *        holdout_pctr (the last validated epoch) holdout_logloss_first holdout_best_epoch
+ *        holdout_best_logloss epochs_run; rows_trained excludes held rows */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

@@ -313,6 +313,23 @@ SIGNATURES = {
     "xf_sharded_progress": (C.c_int, [vp, C.c_int]),
     "xf_sharded_progress_read": (C.c_int, [vp, u64p, u64p, C.c_int, C.c_int]),
     "xf_sharded_last_loss": (C.c_int, [vp, vp, f32p, C.c_size_t]),
+    "xf_holdout_create": (C.c_int, [C.POINTER(vp), C.c_float, C.c_uint64]),
+    "xf_holdout_destroy": (C.c_int, [vp]),
+    "xf_holdout_params": (C.c_int, [vp, C.POINTER(C.c_float), u64p]),
+    "xf_holdout_held": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_float]),
+    "xf_holdout_split_dev": (C.c_int, [vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp,
+                                       C.c_uint32, C.c_uint32, vp, vp, vp]),
+    "xf_holdout_split": (C.c_int, [vp, C.c_uint64, C.c_uint64, u64p, u64p, i32p, f32p, i32p,
+                                   C.c_size_t, C.c_size_t, vp, vp, vp]),
+    "xf_holdout_stats": (C.c_int, [vp, u64p, u64p, u64p]),
+    "xf_holdout_shape": (None, [C.POINTER(C.c_uint32)]),
+    "xf_holdout_should_stop": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double,
+                                         C.POINTER(C.c_int)]),
+    "xf_lr_validate": (C.c_int, [vp, vp, vp, vp]),
+    "xf_fm_validate": (C.c_int, [vp, vp, vp, vp, vp]),
+    "xf_sharded_holdout": (C.c_int, [vp, C.c_int]),
+    "xf_sharded_validate": (C.c_int, [vp, vp]),
+    "xf_sharded_holdout_read": (C.c_int, [vp, u64p, u64p, C.c_int, C.c_int]),
     "xf_slices_home": (C.c_uint64, [C.c_uint64, C.c_int]),
     "xf_slices_terms": (C.c_int, [C.POINTER(C.c_uint32)]),
     "xf_slices_check": (C.c_int, [C.c_int64, C.c_int64]),
@@ -867,6 +884,126 @@ class NegSample:
         """(rows seen, rows kept, negatives seen, negatives kept), summed over the applies"""
         v = [C.c_uint64() for _ in range(4)]
         check(lib().xf_negsample_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
+def holdout_held(seed, stream, ordinal, share):
+    """whether the row of this ordinal is held out of training (xf_holdout_held; host code, the
+    kernels' own definition)"""
+    return bool(lib().xf_holdout_held(int(seed) & (2**64 - 1), int(stream) & (2**64 - 1),
+                                      int(ordinal) & (2**64 - 1), float(share)))
+
+
+def holdout_should_stop(logloss, patience, delta=0.0):
+    """xf_holdout_should_stop (host code) on one held-out logloss per validated epoch ->
+    (stop, index of the best epoch or -1)"""
+    a = np.ascontiguousarray(logloss, dtype=np.float64)
+    best = C.c_int(-1)
+    stop = lib().xf_holdout_should_stop(a.ctypes.data_as(C.POINTER(C.c_double)) if len(a) else None,
+                                        len(a), int(patience), float(delta), C.byref(best))
+    return bool(stop), best.value
+
+
+def holdout_shape():
+    """{tile (rows of a workgroup), chunk (output nonzeros of a copy workgroup), align (elements
+    the held part is aligned to)} of the split kernels"""
+    out = (C.c_uint32 * 3)()
+    lib().xf_holdout_shape(out)
+    return {"tile": out[0], "chunk": out[1], "align": out[2]}
+
+
+class HoldoutPart(C.Structure):
+    _fields_ = [("d_keys", vp), ("d_fgid", vp), ("d_vals", vp), ("d_rowptr", vp),
+                ("d_labels", vp), ("R", C.c_uint32), ("NNZ", C.c_uint32)]
+
+    def dev(self):
+        return AdmitDev(self.d_keys, self.d_rowptr, self.d_labels, self.R, self.NNZ, self.d_fgid,
+                        self.d_vals)
+
+
+class Holdout:
+    """Held-out validation's row split (xf_holdout_*): split() sends a hash-chosen share of a
+    minibatch's rows — decided by a hash of (seed, stream, the row's ordinal) alone — into a held
+    minibatch and the rest, in order, into a train minibatch.  Stateless but for the statistics."""
+
+    def __init__(self, share, seed=0):
+        self.h = vp()
+        self.share, self.seed = float(np.float32(share)), seed
+        check(lib().xf_holdout_create(C.byref(self.h), share, seed))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().xf_holdout_destroy(self.h)
+            self.h = None
+
+    def params(self):
+        share, seed = C.c_float(), C.c_uint64()
+        check(lib().xf_holdout_params(self.h, C.byref(share), C.byref(seed)))
+        return share.value, seed.value
+
+    def split_dev(self, stream_id, first_ordinal, rowptr, keys, labels, fgid=None, values=None,
+                  stream=None):
+        """host arrays in (uploaded as they are), (train, held) as two AdmitDev out (device
+        pointers owned by the object, valid until its next split)"""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert len(rowptr) >= 1 and int(rowptr[-1]) - int(rowptr[0]) <= len(keys)
+        R = len(rowptr) - 1
+        args = []
+        for a, dt, pt in ((fgid, np.int32, i32p), (values, np.float32, f32p)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=dt)
+                assert len(a) == len(keys), "one entry per key"
+                a = a if len(a) else np.zeros(1, dt)
+            args.append((a, pt))
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        assert len(labels) == R, "one label per row"
+        labels = labels if R else np.zeros(1, np.int32)
+        if len(keys) == 0:
+            keys = np.zeros(1, np.uint64)
+        ptr = [(_p(a, pt) if a is not None else None) for a, pt in args]
+        train, held = HoldoutPart(), HoldoutPart()
+        check(lib().xf_holdout_split(self.h, int(stream_id), int(first_ordinal) & (2**64 - 1),
+                                     _p(rowptr, u64p), _p(keys, u64p), ptr[0], ptr[1],
+                                     _p(labels, i32p), 0, R, stream, C.byref(train),
+                                     C.byref(held)))
+        return train.dev(), held.dev()
+
+    def part_dev(self, stream_id, first_ordinal, d_keys, d_rowptr, d_labels, R, NNZ, d_fgid=None,
+                 d_vals=None, stream=None):
+        """xf_holdout_split_dev: device pointers in (ints), (train, held) as two AdmitDev"""
+        train, held = HoldoutPart(), HoldoutPart()
+        check(lib().xf_holdout_split_dev(self.h, int(stream_id), int(first_ordinal) & (2**64 - 1),
+                                         d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ,
+                                         stream, C.byref(train), C.byref(held)))
+        return train.dev(), held.dev()
+
+    @staticmethod
+    def download(d, fgid=False, values=False):
+        """the host arrays of one part: (rowptr uint32, keys, labels) and then, for each of fgid /
+        values asked for, its array in that order"""
+        check(lib().xf_stream_sync(None))
+        out = [(np.zeros(d.R + 1, np.uint32), d.d_rowptr), (np.zeros(d.NNZ, np.uint64), d.d_keys),
+               (np.zeros(d.R, np.int32), d.d_labels)]
+        if fgid:
+            out.append((np.zeros(d.NNZ, np.int32), d.d_fgid))
+        if values:
+            out.append((np.zeros(d.NNZ, np.float32), d.d_vals))
+        for a, ptr in out:
+            if a.nbytes:
+                check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
+        return tuple(a for a, _ in out)
+
+    def split(self, stream_id, first_ordinal, rowptr, keys, labels, fgid=None, values=None):
+        """(train, held), each the downloaded host arrays of that part (download())"""
+        t, h = self.split_dev(stream_id, first_ordinal, rowptr, keys, labels, fgid, values)
+        return (self.download(t, fgid is not None, values is not None),
+                self.download(h, fgid is not None, values is not None))
+
+    def stats(self):
+        """(rows seen, rows held, nonzeros held), summed over the splits"""
+        v = [C.c_uint64() for _ in range(3)]
+        check(lib().xf_holdout_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
 
@@ -1722,6 +1859,16 @@ def fm_predict(wt, vt, batch, ws):
     return out
 
 
+def lr_validate(table, batch, ws, progress):
+    """xf_lr_predict's forward; the rows' losses counted into `progress` (a Progress) instead of
+    pctr copied out"""
+    check(lib().xf_lr_validate(table.h, batch.h, ws.h, progress.h))
+
+
+def fm_validate(wt, vt, batch, ws, progress):
+    check(lib().xf_fm_validate(wt.h, vt.h, batch.h, ws.h, progress.h))
+
+
 def stream_sync(stream=None):
     check(lib().xf_stream_sync(stream))
 
@@ -1905,6 +2052,23 @@ class Sharded:
         other = np.empty(2, np.uint64)
         check(lib().xf_sharded_progress_read(self.h, _p(counts, u64p), _p(other, u64p),
                                              1 if reset else 0, 1 if merged else 0))
+        return counts, other
+
+    def set_holdout(self, enable):
+        """held-out validation (xf_sharded_holdout): a second progress, counted by validate()
+        alone; several ranks: schedules 'sequential' and 'stale1' only"""
+        check(lib().xf_sharded_holdout(self.h, 1 if enable else 0))
+
+    def validate(self, b):
+        """predict's forward of minibatch b, its losses counted (xf_sharded_validate; COLLECTIVE)"""
+        check(lib().xf_sharded_validate(self.h, b.h))
+
+    def holdout_read(self, reset=False, merged=False):
+        """(counts, other) of this rank's validates; merged=True: COLLECTIVE, the ranks' sum"""
+        counts = np.empty((2, PROGRESS_RANKS), np.uint64)
+        other = np.empty(2, np.uint64)
+        check(lib().xf_sharded_holdout_read(self.h, _p(counts, u64p), _p(other, u64p),
+                                            1 if reset else 0, 1 if merged else 0))
         return counts, other
 
     def set_slices(self, enable, field=0, log2_slots=16):

@@ -34,6 +34,10 @@ int main(int argc, char *argv[]) {
               << "feature crosses (a nonzero per listed pair of fields and per pair of their "
                  "members, formed on the GPU; predict needs the same spec): append cross=2*3,16*17 "
                  "[cross_fgid_base=N with fm_mode=field_aware]\n"
+              << "held-out validation (a hash-chosen share r of the training rows is never trained "
+                 "on and scored after every E-th epoch; stop after P validated epochs without "
+                 "improvement): append holdout=r [holdout_every=E early_stop=P "
+                 "early_stop_delta=d]\n"
               << "progressive validation (per epoch: logloss and AUC of every training row under "
                  "the weights it met before it was trained on, counted on the GPU): append "
                  "progress=1\n"

@@ -1904,6 +1904,16 @@ static float ws_finalize_weight(const xf_workspace *ws) {
   return ws->progress ? 1.0f : ws->neg_weight;
 }
 
+// what a forward-only pass does with the R rows its forward left in ws->pctr and ws->loss (on the
+// null stream): predict copies pctr out (tap == nullptr), validate counts the losses into `tap`
+// — one launch, no wait (xf_lr_validate, xf_fm_validate)
+static int score_out(xf_workspace *ws, const int32_t *labels, uint32_t R, float *pctr_out,
+                     xf_progress *tap) {
+  if (tap) return xf::progress_accumulate(tap, ws->loss, labels, R, nullptr);
+  if (R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)R * 4, hipMemcpyDeviceToHost));
+  return XF_OK;
+}
+
 extern "C" int xf_workspace_capture(xf_workspace *ws, int enable) {
   XF_REQUIRE(ws, "xf_workspace_capture: null workspace");
   XF_REQUIRE(!enable || ws->fm_mode != XF_FM_FIELD_AWARE,
@@ -2000,10 +2010,8 @@ static int lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream,
 
 // feature values: the step / predict of a valued minibatch (below, with the canonical FM's)
 static int lr_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream);
-static int lr_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out);
 // ... and of a valued LOCAL minibatch: the valued cell kernels (xf_cells_valued.hip)
 static int lr_local_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream);
-static int lr_local_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out);
 
 extern "C" int xf_lr_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stream) {
   XF_REQUIRE(w && b && ws, "xf_lr_step: null argument");
@@ -2305,7 +2313,7 @@ static int fm_canonical_step(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
 
 // forward only: pulls (and so inserts) the keys, as the reference-mode predict does
 static int fm_canonical_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
-                                float *pctr_out) {
+                                float *pctr_out, xf_progress *tap) {
   XF_TRY(fmc_check_batch(b, "xf_fm_predict"));
   const int k = xf::table_dim(vt);
   XF_TRY(xf_batch_upload(b, nullptr));
@@ -2318,7 +2326,7 @@ static int fm_canonical_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_works
   XF_TRY(xf_table_gather_dev(vt, ws->slots2, v.U, ws->fmc_vu, nullptr));
   XF_TRY(xf::fmc_forward(&v, k, ws->wu, ws->fmc_vu, ws->fmc_S, ws->loss, ws->pctr,
                          b->valued ? b->d_xval : nullptr, nullptr));
-  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(score_out(ws, v.labels, b->R, pctr_out, tap));
   XF_TRY(xf_table_check(w, nullptr));
   return xf_table_check(vt, nullptr);
 }
@@ -2416,7 +2424,7 @@ static int fm_field_aware_step(xf_table *w, xf_table *vt, xf_batch *b, xf_worksp
 
 // forward only: pulls (and so inserts) the keys, as the other forms' predict does
 static int fm_field_aware_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
-                                  float *pctr_out) {
+                                  float *pctr_out, xf_progress *tap) {
   int k = 0;
   XF_TRY(ffm_check(vt, b, ws, "xf_fm_predict", &k));
   const int F = ws->fm_fields;
@@ -2431,7 +2439,7 @@ static int fm_field_aware_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_wor
   XF_TRY(xf_table_gather_dev(vt, ws->slots2, v.U, ws->fmc_vu, nullptr));
   XF_TRY(xf::ffm_forward(&v, k, F, ws->wu, ws->fmc_vu, b->d_xfg, ws->loss, ws->pctr,
                          b->valued ? b->d_xval : nullptr, nullptr));
-  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(score_out(ws, v.labels, b->R, pctr_out, tap));
   XF_TRY(xf_table_check(w, nullptr));
   return xf_table_check(vt, nullptr);
 }
@@ -2477,14 +2485,15 @@ static int lr_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void *stre
   return XF_OK;
 }
 
-static int lr_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out) {
+static int lr_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out,
+                             xf_progress *tap) {
   XF_TRY(valued_check(ws, "xf_lr_predict"));
   XF_TRY(xf_batch_upload(b, nullptr));
   XF_TRY(ws_reserve(ws, b->U, 0, b->R, false));
   const xf_dev_batch &v = b->view;
   XF_TRY(xf_table_pull_dev(w, v.ukeys, v.U, ws->slots, ws->wu, nullptr));
   XF_TRY(xf::val_lr_forward(&v, b->d_xval, ws->wu, ws->loss, ws->pctr, nullptr));
-  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(score_out(ws, v.labels, b->R, pctr_out, tap));
   return xf_table_check(w, nullptr);
 }
 
@@ -2514,14 +2523,15 @@ static int lr_local_valued_step(xf_table *w, xf_batch *b, xf_workspace *ws, void
   return XF_OK;
 }
 
-static int lr_local_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out) {
+static int lr_local_valued_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out,
+                                   xf_progress *tap) {
   XF_TRY(valued_check(ws, "xf_lr_predict"));
   XF_TRY(xf::ensure_cells(b, w, nullptr));
   XF_TRY(ws_reserve(ws, 0, 0, b->R));
   XF_TRY(ws_reserve_cells(ws, b->cells, false));
   XF_TRY(xf::cells_lr_forward_valued(b->cells, xf::table_dev(w).w, b->raw_labels, ws->partial,
                                      ws->loss, ws->pctr, nullptr));
-  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(score_out(ws, b->raw_labels, b->R, pctr_out, tap));
   return xf_table_check(w, nullptr);
 }
 
@@ -2800,11 +2810,12 @@ int fm_owner_push_pulled(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *w
 
 // forward only: calculate_pctr (lr_worker.cc:25-71).  The pull inserts unseen keys, as the
 // reference's test-time Pull does (ftrl.h:56).
-extern "C" int xf_lr_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out) {
-  XF_REQUIRE(w && b && ws && pctr_out, "xf_lr_predict: null argument");
+// (one body for predict and validate: the forward on the device, then score_out)
+static int lr_score(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out,
+                    xf_progress *tap) {
   XF_REQUIRE(xf::table_dim(w) == 1, "xf_lr_predict: the w table must have dim 1");
-  if (b->valued) return lr_valued_predict(w, b, ws, pctr_out);
-  if (b->local_valued) return lr_local_valued_predict(w, b, ws, pctr_out);
+  if (b->valued) return lr_valued_predict(w, b, ws, pctr_out, tap);
+  if (b->local_valued) return lr_local_valued_predict(w, b, ws, pctr_out, tap);
   XF_TRY(xf::ensure_cells(b, w, nullptr));
   XF_TRY(ws_reserve(ws, b->U, 0, b->R));
   XF_TRY(ws_reserve_cells(ws, b->cells, false));
@@ -2814,17 +2825,27 @@ extern "C" int xf_lr_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *
   else
     XF_TRY(xf::cells_lr_forward(b->cells, xf::table_dev(w).w, labels, ws->partial, ws->loss,
                                 ws->pctr, nullptr));
-  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(score_out(ws, labels, b->R, pctr_out, tap));
   return xf_table_check(w, nullptr);
 }
 
-extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
-                             float *pctr_out) {
-  XF_REQUIRE(w && vt && b && ws && pctr_out, "xf_fm_predict: null argument");
+extern "C" int xf_lr_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *pctr_out) {
+  XF_REQUIRE(w && b && ws && pctr_out, "xf_lr_predict: null argument");
+  return lr_score(w, b, ws, pctr_out, nullptr);
+}
+
+extern "C" int xf_lr_validate(xf_table *w, xf_batch *b, xf_workspace *ws, xf_progress *p) {
+  XF_REQUIRE(w && b && ws && p, "xf_lr_validate: null argument");
+  return lr_score(w, b, ws, nullptr, p);
+}
+
+static int fm_score(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws, float *pctr_out,
+                    xf_progress *tap) {
   XF_TRY(no_local_valued(b, "xf_fm_predict"));
   XF_REQUIRE(!b->local, "xf_fm_predict: needs a minibatch with a key list (xf_batch_compile*)");
-  if (ws->fm_mode == XF_FM_FIELD_AWARE) return fm_field_aware_predict(w, vt, b, ws, pctr_out);
-  if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_predict(w, vt, b, ws, pctr_out);
+  if (ws->fm_mode == XF_FM_FIELD_AWARE)
+    return fm_field_aware_predict(w, vt, b, ws, pctr_out, tap);
+  if (ws->fm_mode == XF_FM_CANONICAL) return fm_canonical_predict(w, vt, b, ws, pctr_out, tap);
   XF_REQUIRE(!b->valued,
              "xf_fm_predict: a minibatch with feature values (feature_values) needs fm_mode = "
              "canonical (xf_workspace_fm_mode)");
@@ -2847,7 +2868,7 @@ extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
                          dim3(kBlock), 0, S(nullptr), v.rowptr, b->d_fm_ridx, (const FmKey *)rec,
                          v.labels, v.R, ws->loss, ws->pctr, ws->vsum);
       XF_HIP(hipGetLastError());
-      XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+      XF_TRY(score_out(ws, v.labels, b->R, pctr_out, tap));
     }
     XF_TRY(xf_table_check(w, nullptr));
     return xf_table_check(vt, nullptr);
@@ -2862,9 +2883,21 @@ extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
                                   nullptr));
   else
     XF_TRY(xf_fm_forward_dev(&v, k, ws->wu, ws->vu, ws->loss, ws->pctr, ws->vsum, nullptr));
-  if (b->R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)b->R * 4, hipMemcpyDeviceToHost));
+  XF_TRY(score_out(ws, v.labels, b->R, pctr_out, tap));
   XF_TRY(xf_table_check(w, nullptr));
   return xf_table_check(vt, nullptr);
+}
+
+extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
+                             float *pctr_out) {
+  XF_REQUIRE(w && vt && b && ws && pctr_out, "xf_fm_predict: null argument");
+  return fm_score(w, vt, b, ws, pctr_out, nullptr);
+}
+
+extern "C" int xf_fm_validate(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
+                              xf_progress *p) {
+  XF_REQUIRE(w && vt && b && ws && p, "xf_fm_validate: null argument");
+  return fm_score(w, vt, b, ws, nullptr, p);
 }
 
 // parity hook: intermediates of the last step

@@ -239,6 +239,7 @@ struct xf_sharded {
   int fm_fields = 0;                       // (what xf_sharded_set_fm_fields last set)
   float neg_weight = 1.0f;                 // (what xf_sharded_set_neg_weight last set)
   xf_progress *progress = nullptr;         // progressive validation (xf_sharded_progress); null: off
+  xf_progress *holdout = nullptr;          // held-out validation (xf_sharded_holdout); null: off
   xf_slices *slices = nullptr;             // its slices (xf_sharded_slices); null: off
   uint64_t seen_upper = 0;     // world 1: host-side upper bound on the keys in the table
   Dev<double> partial;         // LR forward scratch
@@ -1425,6 +1426,7 @@ extern "C" int xf_sharded_destroy(xf_sharded *st) {
   if (st->h_counts) (void)hipHostFree(st->h_counts);
   if (st->ws) xf_workspace_destroy(st->ws);
   if (st->progress) xf_progress_destroy(st->progress);
+  if (st->holdout) xf_progress_destroy(st->holdout);
   if (st->slices) xf_slices_destroy(st->slices);
   if (st->tw) xf_table_destroy(st->tw);
   if (st->tv) xf_table_destroy(st->tv);
@@ -1964,6 +1966,33 @@ extern "C" int xf_sharded_predict(xf_sharded *st, xf_sbatch *b, float *pctr_out)
   return XF_OK;
 }
 
+// held-out validation: xf_sharded_predict's forward, its losses counted instead of its pctr copied
+// out.  COLLECTIVE like predict: ranks without held rows call it with an empty minibatch.
+extern "C" int xf_sharded_validate(xf_sharded *st, xf_sbatch *b) {
+  XF_REQUIRE(st && b, "xf_sharded_validate: null argument");
+  XF_ALIVE(st);
+  XF_REQUIRE(st->holdout, "xf_sharded_validate: held-out validation is off (xf_sharded_holdout)");
+  if (st->fused) {
+    XF_TRY(wait_stream(st, st->main));
+    if (st->cfg.model == 0) return xf_lr_validate(st->tw, b->b, st->ws, st->holdout);
+    return xf_fm_validate(st->tw, st->tv, b->b, st->ws, st->holdout);
+  }
+  XF_TRY(xf_sharded_flush(st));
+  st->rec = false;  // a forward-only pass records no step profile
+  XF_REQUIRE(!owner_dataflow(st->cfg.schedule) && !b->oc,
+             "xf_sharded_validate: held-out validation on schedule %s: the owners' finalize "
+             "kernels form the loss where no tap reads it (use schedule sequential or stale1)",
+             schedule_name(st->cfg.schedule));
+  XF_TRY(form_check(st, b, "xf_sharded_validate"));
+  StepBuf &B = b->buf[b->flip];
+  Dev<float> pctr;  // (the forward of predict, launch for launch: it forms pctr as well)
+  XF_TRY(pctr.reserve(b->R));
+  XF_TRY(front_pull(st, b, B, st->main));
+  XF_TRY(front_compute(st, b, B, pctr.p, false, st->main));
+  XF_TRY(xf::progress_accumulate(st->holdout, B.loss.p, b->b->view.labels, b->R, st->main));
+  return wait_stream(st, st->main);  // (predict's wait: pctr goes out of scope)
+}
+
 // renumber this shard's state rows in key order (table maintenance between steps; local to the
 // rank).  Applies an outstanding stale1 Push first: row numbers held by a step in flight would
 // go stale.
@@ -2076,6 +2105,10 @@ extern "C" int xf_sharded_set_schedule(xf_sharded *st, int schedule) {
              "xf_sharded_set_schedule: schedule %s with progressive validation on "
              "(xf_sharded_progress): the owners' finalize kernels form the loss where no tap reads it",
              schedule_name(schedule));
+  XF_REQUIRE(!owner_dataflow(schedule) || st->fused || !st->holdout,
+             "xf_sharded_set_schedule: schedule %s with held-out validation on "
+             "(xf_sharded_holdout): the owners' finalize kernels form the loss where no tap reads it",
+             schedule_name(schedule));
   XF_TRY(xf_sharded_flush(st));
   st->cfg.schedule = schedule;
   return XF_OK;
@@ -2133,13 +2166,41 @@ extern "C" int xf_sharded_progress(xf_sharded *st, int enable) {
   return XF_OK;
 }
 
+static int read_counts(xf_sharded *st, xf_progress *p, uint64_t *counts, uint64_t *other,
+                       int reset, int merged);  // (below: shared with xf_sharded_holdout_read)
+
 extern "C" int xf_sharded_progress_read(xf_sharded *st, uint64_t *counts, uint64_t *other,
                                         int reset, int merged) {
   XF_REQUIRE(st && counts && other, "xf_sharded_progress_read: null argument");
   XF_REQUIRE(st->progress, "xf_sharded_progress_read: progressive validation is off "
              "(xf_sharded_progress)");
+  return read_counts(st, st->progress, counts, other, reset, merged);
+}
+
+// held-out validation: a second progress, counted by xf_sharded_validate alone — no training step
+// taps it, so the fused step's workspace never sees it
+extern "C" int xf_sharded_holdout(xf_sharded *st, int enable) {
+  XF_REQUIRE(st, "xf_sharded_holdout: null trainer");
+  XF_ALIVE(st);
+  XF_REQUIRE(!enable || st->fused || !owner_dataflow(st->cfg.schedule),
+             "xf_sharded_holdout: held-out validation on schedule %s: the owners' finalize "
+             "kernels form the loss where no tap reads it (use schedule sequential or stale1)",
+             schedule_name(st->cfg.schedule));
+  if (enable && !st->holdout) {
+    XF_TRY(xf_progress_create(&st->holdout));
+  } else if (!enable && st->holdout) {
+    XF_TRY(xf_sharded_flush(st));
+    xf_progress_destroy(st->holdout);
+    st->holdout = nullptr;
+  }
+  return XF_OK;
+}
+
+// this rank's counts of `p` after a flush; merged: COLLECTIVE, the ranks' counts summed
+static int read_counts(xf_sharded *st, xf_progress *p, uint64_t *counts, uint64_t *other,
+                       int reset, int merged) {
   XF_TRY(xf_sharded_flush(st));
-  XF_TRY(xf_progress_read(st->progress, counts, other, reset));
+  XF_TRY(xf_progress_read(p, counts, other, reset));
   if (!merged || !st->g || st->world <= 1) return XF_OK;
   const size_t nc = 2 * (size_t)XF_PROGRESS_RANKS, n = nc + 2;
   std::vector<uint64_t> mine(n), all(n * (size_t)st->world);
@@ -2153,6 +2214,14 @@ extern "C" int xf_sharded_progress_read(xf_sharded *st, uint64_t *counts, uint64
     (i < nc ? counts[i] : other[i - nc]) = sum;
   }
   return XF_OK;
+}
+
+extern "C" int xf_sharded_holdout_read(xf_sharded *st, uint64_t *counts, uint64_t *other,
+                                       int reset, int merged) {
+  XF_REQUIRE(st && counts && other, "xf_sharded_holdout_read: null argument");
+  XF_REQUIRE(st->holdout, "xf_sharded_holdout_read: held-out validation is off "
+             "(xf_sharded_holdout)");
+  return read_counts(st, st->holdout, counts, other, reset, merged);
 }
 
 // sliced progressive validation: beside the progress, tapped at the same two places

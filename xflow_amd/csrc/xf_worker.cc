@@ -52,6 +52,8 @@ Worker::~Worker() {
   for (xf_ingest *g : ingest_)
     if (g) xf_ingest_destroy(g);
   for (xf_sbatch *b : cache_) xf_sbatch_free(b);
+  for (xf_sbatch *b : held_) xf_sbatch_free(b);
+  if (split_) xf_holdout_destroy(split_);
   if (admit_) xf_admit_destroy(admit_);
   if (sample_) xf_negsample_destroy(sample_);
   if (cross_) xf_cross_destroy(cross_);
@@ -77,6 +79,7 @@ int Worker::create_tables() {
   if (sharded_) {
     XF_TRY(create_admit());
     XF_TRY(create_negsample());
+    XF_TRY(create_holdout());
     return create_cross();
   }
   int w = world;
@@ -159,6 +162,7 @@ int Worker::create_tables() {
   }
   XF_TRY(create_admit());
   XF_TRY(create_negsample());
+  XF_TRY(create_holdout());
   return create_cross();
 }
 
@@ -438,10 +442,175 @@ int Worker::sample_dev(size_t first_row, const uint64_t **d_keys, const int32_t 
                        uint32_t *R, uint32_t *NNZ) {
   void *stream = nullptr;
   XF_TRY(xf_sharded_stream(sharded_, &stream));
-  return xf_negsample_apply_dev(sample_, sample_stream_, ordinal_ + first_row, *d_keys,
+  // (with holdout on the sampler numbers the rows of the TRAIN part: split_dev's running count)
+  return xf_negsample_apply_dev(sample_, sample_stream_,
+                                split_ ? train_block_first_ : ordinal_ + first_row, *d_keys,
                                 fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? *d_fgid : nullptr,
                                 feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
                                 stream, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ);
+}
+
+// Held-out validation splits a training block on the GPU ahead of every other stage: core_num > 1
+// slices a block after it was read (a row would have no file-wide index), the host key build and
+// the reference-order forward take host arrays, and on several workers the owner-compute schedules
+// form the loss inside the owners' finalize kernels.  All refused by name, before any rendezvous.
+int Worker::check_holdout() const {
+  XF_REQUIRE(holdout >= 0.0f && holdout < 1.0f,
+             "XFStartTrain: holdout must be in [0, 1) (the share of the training rows that is held "
+             "out; 0 = off), not %g", (double)holdout);
+  XF_REQUIRE(holdout_every >= 1, "XFStartTrain: holdout_every must be >= 1 (epochs), not %d",
+             holdout_every);
+  XF_REQUIRE(early_stop >= 0, "XFStartTrain: early_stop must be >= 0 (validated epochs without "
+             "improvement; 0 = off), not %d", early_stop);
+  XF_REQUIRE(early_stop_delta >= 0.0, "XFStartTrain: early_stop_delta must be >= 0, not %g",
+             early_stop_delta);
+  XF_REQUIRE(early_stop == 0 || holdout > 0.0f, "XFStartTrain: early_stop=%d without holdout: "
+             "the rule reads the held-out logloss (use holdout=r)", early_stop);
+  if (holdout == 0.0f) return XF_OK;
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: holdout=%g needs core_num=1, not core_num=%d",
+             (double)holdout, core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: holdout=%g together with key_build=host: the split "
+             "minibatch is born on the GPU (use key_build=gpu)", (double)holdout);
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: holdout=%g together with "
+             "parity=reference_order: that mode builds its keys on the host", (double)holdout);
+  const int w = sharded_ ? world : world_from_env(world);
+  XF_REQUIRE(w <= 1 || (schedule != XF_SCHEDULE_OWNER && schedule != XF_SCHEDULE_OWNER_STALE1),
+             "XFStartTrain: holdout=%g together with schedule=owner / owner_stale1 (world %d): the "
+             "owners' finalize kernels form the loss where no tap reads it (use schedule=sequential "
+             "or stale1)", (double)holdout, w);
+  return XF_OK;
+}
+
+int Worker::create_holdout() {
+  XF_TRY(check_holdout());
+  if (holdout == 0.0f || split_) return XF_OK;
+  XF_TRY(xf_holdout_create(&split_, holdout, seed));
+  XF_TRY(xf_sharded_holdout(sharded_, 1));
+  // the split's first launches, on two rows of a private object: start-up work like the two-row
+  // update of create_tables (the worker's own object keeps its statistics clean)
+  xf_holdout *warm = nullptr;
+  XF_TRY(xf_holdout_create(&warm, holdout, seed));
+  static const uint64_t rp[3] = {0, 2, 4}, keys[4] = {11, 12, 12, 13};
+  static const int32_t lab[2] = {0, 1};
+  void *stream = nullptr;
+  int rc = xf_sharded_stream(sharded_, &stream);
+  xf_holdout_part tr, he;
+  if (rc == XF_OK)
+    rc = xf_holdout_split(warm, 0, 0, rp, keys, nullptr, nullptr, lab, 0, 2, stream, &tr, &he);
+  if (rc == XF_OK) rc = xf_stream_sync(stream);
+  xf_holdout_destroy(warm);
+  return rc;
+}
+
+// the held part of a training block: through the cross and through admission with update = 0
+// (filtered, not counted, as test rows are), compiled with keep = 1 onto the held list — AFTER the
+// block's train part has been compiled, so the filter has counted the block's train rows when it
+// looks at the held ones (on a file of one block: the filter the test file will meet).  Only while
+// the first epoch runs: an epoch that reads the text again drops it.  Without rows: no minibatch
+// on one worker, the empty minibatch in a group.
+int Worker::keep_held(const xf_holdout_part &held) {
+  if (held_complete_ || (held.R == 0 && world <= 1)) return XF_OK;
+  xf_sbatch *hb = nullptr;
+  if (!held.d_rowptr && !admit_) {  // (a turn without rows of this rank's own)
+    XF_TRY(compile_no_rows(sharded_, &hb, 1));
+  } else {
+    XF_TRY(compile_staged_dev(&hb, 0, held.d_keys, held.d_fgid, held.d_vals, held.d_rowptr,
+                              held.d_labels, held.R, held.NNZ, 1));
+  }
+  if (hb) held_.push_back(hb);
+  return XF_OK;
+}
+
+int Worker::split_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
+                      const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
+                      uint32_t *R, uint32_t *NNZ) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  xf_holdout_part tr, he;
+  XF_TRY(xf_holdout_split_dev(split_, (uint64_t)(uint32_t)rank, ordinal_ + first_row, *d_keys,
+                              fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? *d_fgid : nullptr,
+                              feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
+                              stream, &tr, &he));
+  pending_held_ = he;  // (the caller compiles the train part, then keep_held(pending_held_))
+  train_block_first_ = train_ordinal_;
+  train_ordinal_ += tr.R;
+  *d_keys = tr.d_keys;
+  *d_fgid = tr.d_fgid;
+  *d_vals = tr.d_vals;
+  *d_rowptr = tr.d_rowptr;
+  *d_labels = tr.d_labels;
+  *R = tr.R;
+  *NNZ = tr.NNZ;
+  return XF_OK;
+}
+
+// rows [start, end) of host arrays: uploaded by the split; the train part then takes the stages a
+// sampled block takes (a train part without rows is a block without rows)
+int Worker::compile_split(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                          const int32_t *fgid, const float *vals, const int32_t *labels,
+                          size_t start, size_t end, int keep) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  xf_holdout_part tr, he;
+  XF_TRY(xf_holdout_split(split_, (uint64_t)(uint32_t)rank, ordinal_ + start, rowptr, keys,
+                          fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? fgid : nullptr,
+                          feature_values ? vals : nullptr, labels, start, end, stream, &tr, &he));
+  train_block_first_ = train_ordinal_;
+  train_ordinal_ += tr.R;
+  const uint64_t *dk = tr.d_keys;
+  const int32_t *dfg = tr.d_fgid, *dl = tr.d_labels;
+  const float *dv = tr.d_vals;
+  const uint32_t *drp = tr.d_rowptr;
+  uint32_t R = tr.R, NNZ = tr.NNZ;
+  if (sample_) XF_TRY(sample_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ));
+  XF_TRY(compile_sampled_dev(b, dk, dfg, dv, drp, dl, R, NNZ, keep));
+  return keep_held(he);
+}
+
+// the end of an epoch, after the flush and before table maintenance: every holdout_every-th epoch
+// and after the last one the held list is scored forward-only, the counts are summed over the
+// ranks and reset, and rank 0 prints one line; then the early-stop rule, from the merged counts —
+// every rank decides alike
+int Worker::holdout_epoch(int epoch, bool last, bool *stop) {
+  *stop = false;
+  if (!split_) return XF_OK;
+  held_complete_ = true;
+  if ((epoch + 1) % holdout_every != 0 && !last) return XF_OK;
+  for (xf_sbatch *hb : held_) XF_TRY(xf_sharded_validate(sharded_, hb));
+  XF_TRY(xf_sharded_check(sharded_));
+  std::vector<uint64_t> counts(2 * (size_t)XF_PROGRESS_RANKS);
+  uint64_t other[2] = {0, 0};
+  XF_TRY(xf_sharded_holdout_read(sharded_, counts.data(), other, 1, world > 1));
+  XF_TRY(xf_progress_summary(counts.data(), other, 1.0f, &holdout_last_));  // (never weighted)
+  if (holdout_curve_.empty()) holdout_first_ = holdout_last_;
+  holdout_curve_.push_back(holdout_last_.logloss);
+  holdout_epochs_.push_back(epoch);
+  const xf_progress_metrics &m = holdout_last_;
+  if (rank == 0) {
+    char line[512];
+    int at = snprintf(line, sizeof(line),
+                      "holdout epoch %d: rows = %.12g logloss = %.6f (+- %.1e) auc = %.6f (+- %.1e) "
+                      "ctr = %.6f pctr = %.6f", epoch, m.rows_pos + m.rows_neg, m.logloss,
+                      m.logloss_bound, m.auc, m.auc_slack, m.ctr, m.pctr);
+    if (m.saturated != 0 && at < (int)sizeof(line))
+      at += snprintf(line + at, sizeof(line) - at, " saturated = %.17g", m.saturated);
+    if (m.other != 0 && at < (int)sizeof(line))
+      snprintf(line + at, sizeof(line) - at, " other = %.17g", m.other);
+    std::cout << line << std::endl;
+  }
+  int best = -1;
+  const int s = xf_holdout_should_stop(holdout_curve_.data(), (int)holdout_curve_.size(),
+                                       early_stop, early_stop_delta, &best);
+  if (s && !last) {
+    *stop = true;
+    if (rank == 0) {
+      char line[256];
+      snprintf(line, sizeof(line), "early stop after epoch %d: best epoch %d logloss = %.6f", epoch,
+               best >= 0 ? holdout_epochs_[best] : -1, best >= 0 ? holdout_curve_[best] : NAN);
+      std::cout << line << std::endl;
+    }
+  }
+  return XF_OK;
 }
 
 int Worker::compile_sampled_dev(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
@@ -589,6 +758,18 @@ int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const u
                          const int32_t *labels, size_t start, size_t end, int keep) {
   // (sliced progressive validation: training rows of this rank's own.  Under negative subsampling
   // the block is on the device when its rows are named — compile_staged_dev; otherwise here)
+  // (held-out validation: a training block of this rank's own is split first, on the device; in
+  // a group a turn without rows still adds the empty minibatch to the held list, so that every
+  // rank validates equally often)
+  if (split_ && update && trainer == sharded_) {
+    if (rowptr && end > start)
+      return compile_split(b, rowptr, keys, fgid, vals, labels, start, end, keep);
+    if (world > 1) {  // (the train part first, as compile_split does)
+      XF_TRY(compile_rows_unsliced(trainer, b, update, rowptr, keys, fgid, vals, labels, start, end,
+                                   keep));
+      return keep_held(xf_holdout_part{});
+    }
+  }
   if (slicer_ && !sample_ && update && trainer == sharded_ && rowptr && end > start)
     return compile_sliced(b, rowptr, keys, fgid, vals, labels, start, end, keep);
   return compile_rows_unsliced(trainer, b, update, rowptr, keys, fgid, vals, labels, start, end,
@@ -794,6 +975,12 @@ int Worker::batch_training() {
   evict_seen_ = evict_dropped_ = 0;
   for (xf_sbatch *b : cache_) xf_sbatch_free(b);  // a second XFStartTrain starts from the files
   cache_.clear();
+  for (xf_sbatch *b : held_) xf_sbatch_free(b);
+  held_.clear();
+  held_complete_ = false;
+  holdout_curve_.clear();
+  holdout_epochs_.clear();
+  epochs_run_ = 0;
   bool cached = false;
   // compiled minibatches are kept in HBM for the epochs that replay them — with one epoch
   // there is none: the batches are one-shot (no key-sorted copy, their blobs go back to the pool)
@@ -816,7 +1003,7 @@ int Worker::batch_training() {
       // file): the host reader below yields zero rows for such a file and the rank still joins
       // every collective with empty minibatches
       // (negative subsampling: this epoch's stream of decisions, the file's rows numbered from 0)
-      ordinal_ = 0;
+      ordinal_ = train_ordinal_ = 0;
       sample_stream_ = (uint64_t)epoch << 32 | (uint32_t)rank;
       bool took = false;
       if (gpu_ingest_applies()) XF_TRY(text_epoch(epoch, keep, &took));
@@ -933,7 +1120,7 @@ int Worker::batch_training() {
           }
           uint32_t kept_rows = 0;  // (under negative subsampling: the kept rows)
           if (b) xf_sbatch_dims(b, &kept_rows, nullptr, nullptr, nullptr);
-          rows_trained_ += sample_ ? (long)kept_rows : (long)(end - start);
+          rows_trained_ += sample_ || split_ ? (long)kept_rows : (long)(end - start);
           if (keep && b) cache_.push_back(b);
           else if (b)
             xf_sbatch_free(b);
@@ -984,15 +1171,21 @@ int Worker::batch_training() {
     XF_TRY(xf_sharded_flush(sharded_));
     XF_TRY(progress_epoch(epoch));
     XF_TRY(slices_epoch(epoch));
+    // (holdout: the held list scored; an early stop makes this epoch the last one)
+    bool stopped = false;
+    XF_TRY(holdout_epoch(epoch, epoch + 1 == epochs, &stopped));
+    const bool last = stopped || epoch + 1 == epochs;
     // (evict_n: the eviction settles the table itself; after the LAST epoch too, so that the
     // model that is saved and scored holds no evictable row)
-    if (evict_n > 0.0f && ((epoch + 1) % evict_every == 0 || epoch + 1 == epochs))
+    if (evict_n > 0.0f && ((epoch + 1) % evict_every == 0 || last))
       XF_TRY(evict_epoch(epoch));
-    else if (epoch + 1 < epochs)
+    else if (!last)
       XF_TRY(defrag_if_grown(5));
+    epochs_run_ = epoch + 1;
     if (getenv("XF_TRACE_WORKER"))
       fprintf(stderr, "epoch %d: flush + table maintenance %.2f ms\n", epoch, (now_s() - tf0) * 1e3);
     if ((epoch + 1) % 30 == 0) std::cout << "epoch : " << epoch << std::endl;  // :202
+    if (stopped) break;
   }
   XF_TRY(xf_sharded_flush(sharded_));
   train_seconds_ = now_s() - t0;
@@ -1126,9 +1319,11 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
         const float *dv = nullptr;
         rc = xf_ingest_fields(ingest_[k], &dfg, &dv);
         rows = R;
-        if (rc == XF_OK && sample_) {
-          rc = sample_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ);
+        if (rc == XF_OK && split_) rc = split_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ);
+        if (rc == XF_OK && (sample_ || split_)) {
+          if (sample_) rc = sample_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ);
           if (rc == XF_OK) rc = compile_sampled_dev(&b, dk, dfg, dv, drp, dl, R, NNZ, keep);
+          if (rc == XF_OK && split_) rc = keep_held(pending_held_);
         } else if (rc == XF_OK)
           rc = compile_staged_dev(&b, 1, dk, dfg, dv, drp, dl, R, NNZ, keep);
         on_gpu = true;
@@ -1163,7 +1358,7 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
     }
     uint32_t kept_rows = 0;  // (under negative subsampling: the kept rows)
     if (b) xf_sbatch_dims(b, &kept_rows, nullptr, nullptr, nullptr);
-    rows_trained_ += sample_ ? (long)kept_rows : (long)rows;
+    rows_trained_ += sample_ || split_ ? (long)kept_rows : (long)rows;
     ordinal_ += rows;
     if (keep && b) cache_.push_back(b);
     else if (b)
@@ -1325,6 +1520,7 @@ int Worker::train() {
   }
   XF_TRY(check_admit());  // before any rendezvous of a group
   XF_TRY(check_negsample());
+  XF_TRY(check_holdout());
   XF_TRY(check_progress());
   progress_have_ = false;
   XF_TRY(check_slices());
@@ -1462,6 +1658,15 @@ int Worker::set_param(const char *name, const char *value) {
   } else if (n == "neg_keep") {
     XF_REQUIRE(!sample_, "XFSetParam: neg_keep cannot change once the sampler exists");
     neg_keep = strtof(value, nullptr);
+  } else if (n == "holdout") {
+    XF_REQUIRE(!split_, "XFSetParam: holdout cannot change once the split stage exists");
+    holdout = strtof(value, nullptr);
+  } else if (n == "holdout_every") {
+    holdout_every = atoi(value);
+  } else if (n == "early_stop") {
+    early_stop = atoi(value);
+  } else if (n == "early_stop_delta") {
+    early_stop_delta = strtod(value, nullptr);
   } else if (n == "progress") {
     XF_REQUIRE(!sharded_, "XFSetParam: progress cannot change after training started");
     XF_REQUIRE(!strcmp(value, "0") || !strcmp(value, "1"),
@@ -1542,6 +1747,26 @@ int Worker::get_metric(const char *name, double *value) {
     XF_REQUIRE(slices_have_, "XFGetMetric: %s: no epoch has been summarised (progress_by=F, after "
                "XFStartTrain)", name);
     *value = slices_last_[n == "slices" ? 0 : n == "slice_rows" ? 1 : n == "slice_none_rows" ? 2 : 3];
+  } else if (n == "epochs_run") {
+    *value = (double)epochs_run_;
+  } else if (n.rfind("holdout_", 0) == 0) {
+    XF_REQUIRE(!holdout_curve_.empty(), "XFGetMetric: %s: no epoch has been validated (holdout=r, "
+               "after XFStartTrain)", name);
+    const xf_progress_metrics &m = holdout_last_;
+    int best = -1;
+    xf_holdout_should_stop(holdout_curve_.data(), (int)holdout_curve_.size(), 0, early_stop_delta,
+                           &best);
+    if (n == "holdout_rows") *value = m.rows_pos + m.rows_neg;
+    else if (n == "holdout_logloss") *value = m.logloss;
+    else if (n == "holdout_auc") *value = m.auc;
+    else if (n == "holdout_auc_slack") *value = m.auc_slack;
+    else if (n == "holdout_ctr") *value = m.ctr;
+    else if (n == "holdout_pctr") *value = m.pctr;
+    else if (n == "holdout_logloss_first") *value = holdout_first_.logloss;
+    else if (n == "holdout_best_epoch") *value = best >= 0 ? (double)holdout_epochs_[best] : -1.0;
+    else if (n == "holdout_best_logloss") *value = best >= 0 ? holdout_curve_[best] : NAN;
+    else
+      return xf::set_error(XF_EINVAL, "XFGetMetric: unknown metric '%s'", name);
   } else if (n.rfind("progress_", 0) == 0) {
     const bool first = n.size() > 6 && n.compare(n.size() - 6, 6, "_first") == 0;
     const std::string what = n.substr(9, n.size() - 9 - (first ? 6 : 0));

@@ -127,8 +127,51 @@ class Worker {
   // only, not with the owner-compute schedules on several workers (checked where training starts).
   float evict_n = 0.0f;
   int evict_every = 1;
+  // Held-out validation (xf_holdout.hip): holdout = r in (0, 1): every TRAINING block is split
+  // first — a row is held iff xf_holdout_held(seed, rank, the row's index in this rank's training
+  // file, r): no epoch in the stream, so the SAME rows are held in every epoch — and only the train
+  // part goes on to negative subsampling (which then numbers the rows of the train part: a second
+  // running count), slices, cross, admission, compile and step.  The held part goes through the
+  // cross and through admission with update = 0 (filtered, not counted, as test rows are), is
+  // compiled with keep = 1 and stays in HBM for the whole run, whatever cache_batches says; an
+  // epoch that reads the text again drops it.  After the flush of every holdout_every-th epoch
+  // and of the last one the held list is scored forward-only (xf_sharded_validate), the counts are
+  // merged over the ranks and rank 0 prints one line.  early_stop = P > 0: training ends after P
+  // validated epochs without an improvement of the held-out logloss by more than early_stop_delta
+  // (xf_holdout_should_stop); that epoch counts as the last one.  0 = off, nothing is created.
+  // core_num 1, key_build=gpu, parity=exact, not with the owner-compute schedules on several
+  // workers (checked where training starts).  Nothing travels with the model.
+  float holdout = 0.0f;
+  int holdout_every = 1;
+  int early_stop = 0;
+  double early_stop_delta = 0.0;
 
  private:
+  int check_holdout() const;  // the refusals of holdout / early_stop, before any rendezvous
+  int create_holdout();
+  // COLLECTIVE at world > 1: validate the held list, read, merge, reset, summarise, print; *stop:
+  // the early-stop rule says this epoch is the last one
+  int holdout_epoch(int epoch, bool last, bool *stop);
+  xf_holdout *split_ = nullptr;     // holdout > 0: the split stage, created with the tables
+  std::vector<xf_sbatch *> held_;   // the held parts of the first epoch's blocks, kept in HBM
+  bool held_complete_ = false;      // the first epoch has ended: later splits drop the held part
+  uint64_t train_ordinal_ = 0;      // rows of the train part so far in this epoch ...
+  uint64_t train_block_first_ = 0;  // ... and before the block at hand: the sampler's first ordinal
+  std::vector<double> holdout_curve_;  // the held-out logloss of every validated epoch ...
+  std::vector<int> holdout_epochs_;    // ... and which epoch that was
+  xf_progress_metrics holdout_last_{}, holdout_first_{};
+  int epochs_run_ = 0;
+  // split a training block (device arrays): the train part in the arguments, the held part in
+  // pending_held_
+  int split_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
+                const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
+                uint32_t *R, uint32_t *NNZ);
+  int keep_held(const xf_holdout_part &held);
+  xf_holdout_part pending_held_{};  // split_dev's held part, until the train part is compiled
+  // ... or rows [start, end) of host arrays; then the train part's stages and compile
+  int compile_split(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                    const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
+                    size_t end, int keep);
   int check_evict() const;      // the refusals of evict_n, before any rendezvous
   int evict_epoch(int epoch);   // COLLECTIVE at world > 1: evict, sum the counts, print
   uint64_t evict_seen_ = 0, evict_dropped_ = 0;  // totals of the run, summed over the ranks
