@@ -278,6 +278,17 @@ int xf_batch_compile_local_valued(xf_batch **out, xf_table *t, const uint64_t *r
  * windows, chunks, forward workgroups per window, gradient work items, 0 (reserved), chunks
  * cut into several work items, size of the index space */
 int xf_batch_cells_info(const xf_batch *b, uint32_t *out);
+/* the forward's own row windows over the key-sorted copy of a kept minibatch (DESIGN.md 3,
+ * "forward windows"): out[0..6) = rows per forward window, forward windows, forward workgroups
+ * per window, 1 when they differ from xf_batch_cells_info's (else they are those), 1 when the
+ * copy has been built, 1 when the batch's last forward ran on them (a chain of segments and a
+ * resumed forward do not) */
+int xf_batch_fwd_info(const xf_batch *b, uint32_t *out);
+/* the rule that picks the forward windows, by itself (no GPU): out[0..4) = forward windows, rows
+ * per forward window, forward workgroups per window, the gradient's windows, of a minibatch of R
+ * rows and NNZ nonzeros over M index positions under xf_tune("fwd_windows") = tune; flags: 1 a
+ * kept minibatch (it has a key-sorted copy), 2 row-id cells, 4 valued cells */
+int xf_fwd_windows_rule(uint32_t R, uint64_t NNZ, uint64_t M, int flags, int tune, uint32_t *out);
 /* copy a device-built batch's arrays into its host views (xf_batch_host etc. do it on demand) */
 int xf_batch_download(xf_batch *b);
 int xf_batch_free(xf_batch *b);
@@ -307,7 +318,8 @@ int xf_batch_tiles(const xf_batch *b, uint32_t *ntiles, const uint32_t **tile_pt
  * (1 the general kernel, 2 / 3 the dense kernel with byte-masked / whole-line stores),
  * "owner_pass" (1 the general loop, 2 / 3 the merged phases, 4 a phase per worker),
  * "valued_lr" (a valued LR minibatch of a one-rank trainer: 1 the generic build + the tile
- * kernels, 2 the local build + the valued cell kernels) —
+ * kernels, 2 the local build + the valued cell kernels), "fwd_windows" (the row windows of a
+ * kept minibatch's key-sorted copy: 1 the gradient's, 2 .. 32 that many) —
  * xflow_amd/csrc/xf_common.h.  An unknown name, or a value a switch does not take, is XF_EINVAL
  * (a library built with -DXF_EXPERIMENTS also has the experiments' numeric "exp_knob"). */
 int xf_tune(const char *name, double value);
@@ -805,6 +817,7 @@ int xf_sbatch_dims(const xf_sbatch *b, uint32_t *R, uint32_t *NNZ, uint32_t *U,
  * table's rows (a minibatch with a key list that was not stepped yet, any FM minibatch) — which
  * build a compile took, for tests and tools */
 int xf_sbatch_cells_info(const xf_sbatch *b, uint32_t *out);
+int xf_sbatch_fwd_info(const xf_sbatch *b, uint32_t *out); /* xf_batch_fwd_info, likewise */
 /* 1 when the minibatch came from the FM build against the tables' settled tiers
  * (xf_batch_compile_fm: one shard, every key settled), else 0; < 0: error */
 int xf_sbatch_fm_keyed(const xf_sbatch *b);

@@ -152,6 +152,9 @@ SIGNATURES = {
                                                     C.c_uint32, C.c_uint32, C.c_int, vp]),
     "xf_batch_cells_info": (C.c_int, [vp, u32p]),
     "xf_sbatch_cells_info": (C.c_int, [vp, u32p]),
+    "xf_batch_fwd_info": (C.c_int, [vp, u32p]),
+    "xf_sbatch_fwd_info": (C.c_int, [vp, u32p]),
+    "xf_fwd_windows_rule": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_int, u32p]),
     "xf_source_hash": (C.c_char_p, []),
     "xf_workspace_capture": (C.c_int, [vp, C.c_int]),
     "xf_workspace_parity": (C.c_int, [vp, C.c_int]),
@@ -1571,10 +1574,31 @@ class LocalBatch:
     def cells_info(self):
         return cells_info(self)
 
+    def fwd_info(self):
+        return fwd_info(self)
+
     def upload(self, stream=None):
         return self
 
     __del__ = Batch.__del__
+
+
+FWD_INFO = ["W_f", "nwin_f", "G_f", "split", "copy_ready", "used"]
+
+
+def fwd_info(batch):
+    """the forward's own row windows over the batch's key-sorted copy (xf_batch_fwd_info)"""
+    out = (C.c_uint32 * 6)()
+    check(lib().xf_batch_fwd_info(batch.h, out))
+    return dict(zip(FWD_INFO, list(out)))
+
+
+def fwd_windows_rule(R, NNZ, M, kept=True, w_fixed=False, valued=False, tune=0):
+    """the rule that picks them, by itself (no GPU): nwin_f, W_f, G_f and the gradient's nwin"""
+    out = (C.c_uint32 * 4)()
+    flags = (1 if kept else 0) | (2 if w_fixed else 0) | (4 if valued else 0)
+    check(lib().xf_fwd_windows_rule(R, NNZ, M, flags, int(tune), out))
+    return dict(zip(["nwin_f", "W_f", "G_f", "nwin"], list(out)))
 
 
 def cells_info(batch):
@@ -1973,6 +1997,12 @@ class ShardedBatch:
         check(lib().xf_sbatch_cells_info(self.h, out))
         names = ["W", "nwin", "nchunk", "G", "nitems", "segments", "nsplit_chunks", "M"]
         return dict(zip(names, list(out)))
+
+    def local_fwd_info(self):
+        """fwd_info() of the same cells"""
+        out = (C.c_uint32 * 6)()
+        check(lib().xf_sbatch_fwd_info(self.h, out))
+        return dict(zip(FWD_INFO, list(out)))
 
     def __del__(self):
         try:

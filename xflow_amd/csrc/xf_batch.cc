@@ -10,6 +10,7 @@
 // The result depends only on the input rows, so a compiled batch can be cached across
 // epochs (the reference re-parses and re-sorts every epoch, lr_worker.cc:184).
 #include "xf_batch.h"
+#include "xf_cells.h"
 #include "xf_cross.h"
 #include "xf_scratch.h"
 #include "xf_tiling.h"
@@ -228,8 +229,54 @@ void blob_pool_limit(int blobs) {
 }
 }  // namespace xf
 
+// The forward geometry of a kept minibatch's key-sorted copy (xf_cells.h, DESIGN 3 "forward
+// windows").  The forward's partial row sums are (forward workgroups) x (rows per window) x 8
+// bytes, written once and read once: with ~256 workgroups whatever the windows they fall only
+// with more, smaller windows — which the gradient's cells cannot have (k_lr_grad_dense keeps the
+// bounds of at most four windows), the forward's own copy can.  Off (the result is nwin):
+//   no copy to regroup; row-id cells of the owner dataflow (their windows are the workers');
+//   valued cells (one value array serves both passes); a later segment of a chain; a minibatch
+//   of more than four gradient windows (not measured); forward windows of fewer than kFwdRowsMin
+//   rows (a small minibatch: its partial sums are a few MB, not measured either); forward cells
+//   of fewer than kFwdCellMin entries on average — a forward block of 1024 entries then spans
+//   more cells than the 32 its tag bits tell apart and searches cellptr (a 10^8-key table).
+// A forced count (tune >= 2) drops the last three.
 namespace xf {
-static int g_path[kPathCount] = {0, 0, 0, 0, 0, 0};
+uint32_t cells_fwd_windows(uint32_t R, uint64_t NNZ, uint64_t M, uint32_t nwin,
+                           bool key_sorted_copy, bool w_fixed, bool valued, uint32_t chunk0,
+                           int tune) {
+  if (tune == 1 || !key_sorted_copy || w_fixed || valued || chunk0 != 0 || NNZ == 0) return nwin;
+  const uint32_t n = tune >= 2 ? (uint32_t)tune : kFwdWinDefault;
+  if (n < 2 || n > kFwdWinMax || n == nwin) return nwin;
+  const uint32_t W_f = std::max<uint32_t>(1, (uint32_t)(((uint64_t)R + n - 1) / n));
+  const uint64_t nchunk = std::max<uint64_t>(1, (M + kChunk - 1) / kChunk);
+  if (W_f > kWinMax || nchunk * n >= 0x7FFFFFFFull) return nwin;
+  if (tune >= 2) return n;
+  if (nwin > 4 || n < nwin || W_f < kFwdRowsMin) return nwin;
+  if (NNZ < (uint64_t)kFwdCellMin * nchunk * n) return nwin;
+  return n;
+}
+}  // namespace xf
+
+// the rule by itself (no GPU): out[0..3) = forward windows, rows per forward window, forward
+// workgroups per window of a minibatch of R rows and NNZ nonzeros over an index space of M
+// positions, under xf_tune("fwd_windows") = tune; out[3] = the gradient's windows.  flags: 1 = the
+// minibatch has a key-sorted copy, 2 = row-id cells (w_fixed), 4 = valued cells.
+extern "C" int xf_fwd_windows_rule(uint32_t R, uint64_t NNZ, uint64_t M, int flags, int tune,
+                                   uint32_t *out) {
+  XF_REQUIRE(out && tune >= 0 && tune <= (int)xf::kFwdWinMax, "xf_fwd_windows_rule: bad argument");
+  const uint32_t nwin = std::max<uint32_t>(1, (R + xf::kWinMax - 1) / xf::kWinMax);
+  const uint32_t n = xf::cells_fwd_windows(R, NNZ, M, nwin, (flags & 1) != 0, (flags & 2) != 0,
+                                           (flags & 4) != 0, 0, tune);
+  out[0] = n;
+  out[1] = std::max<uint32_t>(1, (R + n - 1) / n);
+  out[2] = xf::cells_fwd_groups(n);
+  out[3] = nwin;
+  return XF_OK;
+}
+
+namespace xf {
+static int g_path[kPathCount] = {0, 0, 0, 0, 0, 0, 0};
 int path_switch(int which) { return g_path[which]; }
 void set_path_switch(int which, int v) { g_path[which] = v; }
 #ifdef XF_EXPERIMENTS
@@ -290,6 +337,9 @@ extern "C" int xf_tune(const char *name, double value) {
     xf::set_path_switch(xf::kPathLrGradient, (int)value);
   else if (!strcmp(name, "entry_streams") && (value == 0 || value == 1))
     xf::set_path_switch(xf::kPathEntryStreams, (int)value);
+  else if (!strcmp(name, "fwd_windows") && value >= 0 && value <= xf::kFwdWinMax &&
+           value == (int)value)
+    xf::set_path_switch(xf::kPathFwdWindows, (int)value);
   else if (!strcmp(name, "owner_pass") && value >= 0 && value <= 4)
     xf::set_path_switch(xf::kPathOwnerPass, (int)value);
   else if (!strcmp(name, "valued_lr") && (value == 0 || value == 1 || value == 2))

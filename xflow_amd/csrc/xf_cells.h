@@ -84,7 +84,19 @@ struct xf_cells {
   // (whose allocation is what it was).  Valued cells are one segment without holes and have no
   // key-sorted copy (entries_k == entries): one value array serves both passes.
   float *vals = nullptr;            // [NNZ]
-  const uint32_t *fwd_entries() const { return entries_k_ready ? entries_k : entries; }
+  // The forward geometry (cells_fwd_windows; DESIGN 3 "forward windows"): when nwin_f != nwin the
+  // key-sorted copy is grouped by cells of its OWN, finer row windows — forward window v covers
+  // the rows [v * W_f, (v + 1) * W_f) of the minibatch, not nested in the gradient's windows —
+  // with cell offsets and block cells of its own.  Only cells_lr_forward over one segment reads
+  // it; everything else stays on (W, nwin, G) and `entries`.
+  uint32_t W_f = 1, nwin_f = 1, G_f = 1;  // == W, nwin, G when the copy keeps the base geometry
+  uint32_t *cellptr_f = nullptr;    // [nwin_f * nchunk + 1]   (null unless nwin_f != nwin)
+  uint32_t *blk_cell_f = nullptr;   // [nblk + 1]
+  bool split_fwd() const { return nwin_f != nwin; }
+  mutable bool fwd_used = false;    // the last cells_lr_forward ran on the forward geometry
+  const uint32_t *fwd_entries() const {  // the forward's stream ON THE BASE GEOMETRY
+    return entries_k_ready && !split_fwd() ? entries_k : entries;
+  }
   uint32_t *cellptr = nullptr;      // [ncell + 1]
   uint32_t *blk_cell = nullptr;     // [nblk + 1] cell of entry kBlk*b; [nblk] = ncell - 1
   uint32_t *plan = nullptr;         // [4 * (nchunk + 1)] slices per chunk and three scans of them
@@ -147,7 +159,30 @@ int cells_fill_items(xf_cells *c, uint32_t nitems, uint32_t nsplit, hipStream_t 
 int cells_key_sorted_copy(xf_cells *c, hipStream_t stream);
 uint32_t cells_split_chunks(const xf_cells *c);  // over the chain
 
-// scratch of the forward: G * nwin * W partial row sums (fp64)
+// The rule that picks the forward geometry of a minibatch's key-sorted copy (host only,
+// xf_batch.cc): the number of forward row windows, == nwin for "the copy keeps the gradient's
+// windows".  tune: xf_tune("fwd_windows") — 0 the rule, 1 off, n >= 2 forces n windows whatever the
+// density (still off where there is no copy to regroup, or where ceil(R / n) rows do not fit a
+// window).
+constexpr uint32_t kFwdWinDefault = 8;     // the rule's choice where it applies (profiles/fwd_windows/)
+constexpr uint32_t kFwdWinMax = 32;        // G_f >= 8: kFwdGroups / 8 / nwin_f >= 1
+constexpr uint32_t kFwdCellMin = 128;      // average entries per forward cell the rule asks for
+constexpr uint32_t kFwdRowsMin = 1024;     // rows per forward window the rule asks for
+uint32_t cells_fwd_windows(uint32_t R, uint64_t NNZ, uint64_t M, uint32_t nwin,
+                           bool key_sorted_copy, bool w_fixed, bool valued, uint32_t chunk0,
+                           int tune);
+// Forward workgroups per window: a multiple of 8 with at most 32 workgroups per XCD (one per CU:
+// the row window fills the LDS).  Group g of EVERY window runs on XCD g % 8 (k_lr_fwd_cells), so
+// the windows read a weight range through one L2: once from HBM instead of once per window.
+#ifndef XF_FWD_GROUPS
+#define XF_FWD_GROUPS 256
+#endif
+inline uint32_t cells_fwd_groups(uint32_t nwin) {
+  return nwin <= 32 ? ((uint32_t)XF_FWD_GROUPS / 8u / nwin) * 8u : 8u;
+}
+
+// scratch of the forward: G * nwin * W partial row sums (fp64), or the forward geometry's
+// G_f * nwin_f * W_f when that is more
 size_t cells_partial_doubles(const xf_cells *c);
 
 // forward: loss[r] = sigmoid(sum_j w[idx_j]) - label[r]   (lr_worker.cc:121-143)

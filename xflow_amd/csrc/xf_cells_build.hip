@@ -7,6 +7,7 @@
 //                                      range-partitioned builds: xf_keybuild.hip)
 // Layout and rationale: xf_cells.h.  HBM-bound integer/byte work, no MFMA.
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
 
 #include "xf_cells_impl.h"
 
@@ -321,6 +322,105 @@ k_cells_sort_pos(const uint32_t *__restrict__ entries, uint32_t *__restrict__ ou
   }
 }
 
+// The copy on a forward geometry of its own (xf_cells.h: nwin_f != nwin): the entries regrouped
+// by FORWARD cell (forward window vf = global row / W_f, chunk), the row field re-based to the
+// forward window, before k_cells_sort_pos orders every forward cell.  Two passes over the gradient's
+// stream with the same classification — PLACE = false counts the entries of every forward cell,
+// PLACE = true hands out their places behind the scanned counts (cellptr_f).  Nothing is assumed
+// about the order inside a gradient cell (the keyed builds fill a cell through a cursor: rows in
+// no order, holes anywhere): an entry's gradient cell comes from its block's cells as in the
+// forward (blk_cell, cell_of), its forward window from its own row bits.  A hole (a key the
+// table's settled tier does not hold; the kernels skip it) has no row: it goes to the first
+// forward window that meets its gradient window, so that the stream keeps its length.
+// A workgroup takes a block of kBlk entries and counts in LDS first — a bin per (cell of the
+// block, forward window): a block of the config-2 shape lies in 2 or 3 cells — so that memory
+// sees one atomic per bin; a block that spans more cells than the bins hold (a sparse minibatch)
+// counts in memory entry by entry.  The order inside a forward cell is whatever the atomics make
+// of it, as in the sort that follows.
+constexpr uint32_t kRegroupBins = 2048;
+__device__ __forceinline__ uint32_t cell_of_entry(const uint32_t *__restrict__ cellptr, uint32_t lo,
+                                                  uint32_t hi, uint32_t j) {
+  while (lo < hi) {  // the largest c in [lo, hi] with cellptr[c] <= j
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (cellptr[mid] <= j) lo = mid;
+    else
+      hi = mid - 1;
+  }
+  return lo;
+}
+
+template <bool PLACE>
+__global__ void __launch_bounds__(kBlock)
+k_fwd_regroup(const uint32_t *__restrict__ entries, const uint32_t *__restrict__ cellptr,
+              const uint32_t *__restrict__ blk_cell, uint32_t NNZ, uint32_t nchunk, uint32_t W,
+              uint32_t W_f, uint32_t nwin_f, uint32_t *__restrict__ cnt,
+              const uint32_t *__restrict__ cellptr_f, uint32_t *__restrict__ out) {
+  constexpr int E = (int)(kBlk / kBlock);
+  __shared__ uint32_t bins[kRegroupBins];
+  __shared__ uint32_t base[PLACE ? kRegroupBins : 1];
+  const uint32_t tid = threadIdx.x, b = blockIdx.x;
+  const uint32_t lo = blk_cell[b], hi = max(blk_cell[b + 1], lo);
+  const uint32_t nb = (hi - lo + 1) * nwin_f;  // (hi - lo < 2^31 / 32: no overflow that matters)
+  const bool lds = hi - lo < kRegroupBins && nb <= kRegroupBins;  // workgroup-uniform
+  if (lds)
+    for (uint32_t k = tid; k < nb; k += kBlock) bins[k] = 0;
+  __syncthreads();
+  uint32_t e[E], cf[E], bin[E];
+  bool on[E];
+#pragma unroll
+  for (int q = 0; q < E; ++q) {
+    const uint32_t j = b * kBlk + q * kBlock + tid;
+    on[q] = j < NNZ;
+    e[q] = on[q] ? entries[j] : 0xFFFFFFFFu;
+    const uint32_t cell = on[q] ? cell_of_entry(cellptr, lo, hi, j) : lo;
+    const uint32_t v = cell / nchunk, chunk = cell - v * nchunk;
+    const uint32_t row = v * W + (e[q] == 0xFFFFFFFFu ? 0u : (e[q] >> kChunkBits) & kRowMask);
+    const uint32_t vf = min(row / W_f, nwin_f - 1);
+    cf[q] = vf * nchunk + chunk;
+    bin[q] = (cell - lo) * nwin_f + vf;
+    if (e[q] != 0xFFFFFFFFu)  // the row within the forward window
+      e[q] = (e[q] & ~(kRowMask << kChunkBits)) | (((row - vf * W_f) & kRowMask) << kChunkBits);
+    if (on[q]) {
+      if (lds) atomicAdd(&bins[bin[q]], 1u);
+      else if (!PLACE)
+        atomicAdd(&cnt[cf[q]], 1u);
+    }
+  }
+  if (lds) {
+    __syncthreads();
+    for (uint32_t k = tid; k < nb; k += kBlock) {
+      const uint32_t n = bins[k];
+      if (n) {
+        const uint32_t cell = lo + k / nwin_f, vf = k % nwin_f;
+        const uint32_t c = vf * nchunk + cell % nchunk;
+        const uint32_t at = atomicAdd(&cnt[c], n);
+        if (PLACE) {
+          base[k] = cellptr_f[c] + at;
+          bins[k] = 0;
+        }
+      }
+    }
+  }
+  if (!PLACE) return;
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < E; ++q) {
+    if (!on[q]) continue;
+    const uint32_t at = lds ? base[bin[q]] + atomicAdd(&bins[bin[q]], 1u)
+                            : cellptr_f[cf[q]] + atomicAdd(&cnt[cf[q]], 1u);
+    if (at < NNZ) out[at] = e[q];  // (always: the two passes count alike)
+  }
+}
+
+// blk_cell of cell offsets alone: the cell of entry kBlk * b is the largest c with cellptr[c] <=
+// kBlk * b (the one of the cells that begin there which is not empty); [nblk] = ncell - 1
+__global__ void __launch_bounds__(kBlock)
+k_blk_cell_of_ptr(const uint32_t *__restrict__ cellptr, uint32_t nblk, uint32_t ncell,
+                  uint32_t *__restrict__ blk_cell) {
+  XF_GRID_STRIDE(b, (size_t)nblk + 1)
+  blk_cell[b] = b < nblk ? cell_of_entry(cellptr, 0, ncell - 1, (uint32_t)b * kBlk) : ncell - 1;
+}
+
 // the same for nonzeros that come with their row number instead of in CSR order (the owner side
 // of the owner-compute step: nonzeros of several workers' minibatches, rows numbered window by
 // window across the workers)
@@ -349,7 +449,9 @@ void cells_free(xf_cells *c) {
   }
 }
 
-size_t cells_partial_doubles(const xf_cells *c) { return (size_t)c->G * c->nwin * c->W; }
+size_t cells_partial_doubles(const xf_cells *c) {
+  return std::max((size_t)c->G * c->nwin * c->W, (size_t)c->G_f * c->nwin_f * c->W_f);
+}
 
 uint32_t cells_split_chunks(const xf_cells *c) {
   uint32_t n = 0;
@@ -385,10 +487,14 @@ int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
   }
   c->ncell = (uint32_t)ncell64;
   c->nblk = (NNZ + kBlk - 1) / kBlk;
-  // Groups per window: a multiple of 8 with at most 32 workgroups per XCD (one per CU: the row
-  // window fills the LDS).  Group g of EVERY window runs on XCD g % 8 (k_lr_fwd_cells), so the
-  // windows read a weight range through one L2: once from HBM instead of once per window.
-  c->G = c->nwin <= 32 ? (kFwdGroups / 8 / c->nwin) * 8 : 8;
+  c->G = cells_fwd_groups(c->nwin);  // (xf_cells.h)
+  // the forward geometry of the key-sorted copy (== the base one unless the rule splits it)
+  c->nwin_f = cells_fwd_windows(R, NNZ, M, c->nwin, key_sorted_copy, w_fixed != 0, valued, chunk0,
+                                path_switch(kPathFwdWindows));
+  const bool split = c->nwin_f != c->nwin;
+  c->W_f = split ? std::max<uint32_t>(1, (R + c->nwin_f - 1) / c->nwin_f) : c->W;
+  c->G_f = split ? cells_fwd_groups(c->nwin_f) : c->G;
+  const size_t ncell_f = split ? (size_t)c->nwin_f * c->nchunk : 0;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t o_ent = 0;
   const size_t o_entk = o_ent + al((size_t)NNZ * 4);
@@ -397,7 +503,10 @@ int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
   const size_t o_plan = o_blk + al(((size_t)c->nblk + 1) * 4);
   // (the values behind everything a binary minibatch has: its offsets and size stay what they were)
   const size_t o_vals = o_plan + al(4 * ((size_t)c->nchunk + 1) * 4);
-  const size_t total = o_vals + (valued ? al((size_t)NNZ * 4) : 0) + 256;
+  // (and the forward geometry's offsets behind those: nothing before them moves)
+  const size_t o_cellptr_f = o_vals + (valued ? al((size_t)NNZ * 4) : 0);
+  const size_t o_blk_f = o_cellptr_f + (split ? al((ncell_f + 1) * 4) : 0);
+  const size_t total = o_blk_f + (split ? al(((size_t)c->nblk + 1) * 4) : 0) + 256;
   int rc = blob_alloc((void **)&c->blob, total, &c->blob_bytes);
   if (rc != XF_OK) {
     delete c;
@@ -409,6 +518,10 @@ int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
   c->blk_cell = (uint32_t *)(c->blob + o_blk);
   c->plan = (uint32_t *)(c->blob + o_plan);
   if (valued) c->vals = (float *)(c->blob + o_vals);
+  if (split) {
+    c->cellptr_f = (uint32_t *)(c->blob + o_cellptr_f);
+    c->blk_cell_f = (uint32_t *)(c->blob + o_blk_f);
+  }
   *out = c;
   return XF_OK;
 }
@@ -417,8 +530,68 @@ int cells_alloc(xf_cells **out, uint32_t R, uint32_t NNZ, uint32_t M, int mode,
 // chunk), so that neighbouring lanes gather neighbouring weights (forward kernel 58 -> 42 us on
 // the config-2 shape): k_cells_sort_pos.  A minibatch that is stepped once goes without and the
 // forward reads the row-sorted cells.  In stream order, nothing is waited for.
+//
+// On a forward geometry of its own (c->split_fwd(), xf_cells.h) the entries are first regrouped
+// by forward cell — count (k_fwd_regroup<false>), scan (cellptr_f), place (k_fwd_regroup<true>,
+// into a staging array), blk_cell_f — and the same sort then runs over the forward cells.  The
+// staging array and the counters are the calling thread's, kept between builds; a build waits
+// ON THE DEVICE for the last build that used them (an event), never on the host.
+namespace {
+struct FwdStage {
+  char *p = nullptr;
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;  // the last build's sort has read the staging array
+};
+FwdStage &fwd_stage() {
+  static thread_local FwdStage f;
+  return f;
+}
+}  // namespace
+
+static int cells_copy_split(xf_cells *c, hipStream_t s) {
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const uint32_t ncell_f = c->nwin_f * c->nchunk;
+  size_t scan_bytes = 0;
+  XF_HIP(rocprim::exclusive_scan(nullptr, scan_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u,
+                                 (size_t)ncell_f + 1, rocprim::plus<uint32_t>(), s));
+  const size_t o_stage = 0, o_cnt = o_stage + al((size_t)c->NNZ * 4);
+  const size_t o_scan = o_cnt + al(((size_t)ncell_f + 1) * 4), total = o_scan + al(scan_bytes) + 256;
+  FwdStage &f = fwd_stage();
+  if (!f.ev) XF_HIP(hipEventCreateWithFlags(&f.ev, hipEventDisableTiming));
+  else
+    XF_HIP(hipStreamWaitEvent(s, f.ev, 0));
+  if (total > f.cap) {
+    if (f.p) XF_HIP(hipFree(f.p));  // (waits for the device)
+    f.p = nullptr;
+    f.cap = 0;
+    XF_HIP(hipMalloc((void **)&f.p, total + total / 8));
+    f.cap = total + total / 8;
+  }
+  uint32_t *stage = (uint32_t *)(f.p + o_stage), *cnt = (uint32_t *)(f.p + o_cnt);
+  XF_HIP(hipMemsetAsync(cnt, 0, ((size_t)ncell_f + 1) * 4, s));
+  hipLaunchKernelGGL(k_fwd_regroup<false>, dim3(c->nblk), dim3(kBlock), 0, s, c->entries, c->cellptr,
+                     c->blk_cell, c->NNZ, c->nchunk, c->W, c->W_f, c->nwin_f, cnt,
+                     (const uint32_t *)nullptr, (uint32_t *)nullptr);
+  XF_HIP(rocprim::exclusive_scan(f.p + o_scan, scan_bytes, cnt, c->cellptr_f, 0u,
+                                 (size_t)ncell_f + 1, rocprim::plus<uint32_t>(), s));
+  XF_HIP(hipMemsetAsync(cnt, 0, ((size_t)ncell_f + 1) * 4, s));
+  hipLaunchKernelGGL(k_fwd_regroup<true>, dim3(c->nblk), dim3(kBlock), 0, s, c->entries, c->cellptr,
+                     c->blk_cell, c->NNZ, c->nchunk, c->W, c->W_f, c->nwin_f, cnt, c->cellptr_f,
+                     stage);
+  hipLaunchKernelGGL(k_blk_cell_of_ptr, dim3(grid_for((size_t)c->nblk + 1)), dim3(kBlock), 0, s,
+                     c->cellptr_f, c->nblk, ncell_f, c->blk_cell_f);
+  const uint32_t nsort = (ncell_f + kSortCells - 1) / kSortCells;
+  hipLaunchKernelGGL(k_cells_sort_pos, dim3(nsort + c->nblk), dim3(kBlock), 0, s, stage, c->entries_k,
+                     c->cellptr_f, c->blk_cell_f, ncell_f, nsort);
+  XF_HIP(hipGetLastError());
+  XF_HIP(hipEventRecord(f.ev, s));
+  c->entries_k_ready = true;
+  return XF_OK;
+}
+
 int cells_key_sorted_copy(xf_cells *c, hipStream_t s) {
   if (!c->NNZ || c->entries_k == c->entries) return XF_OK;
+  if (c->split_fwd()) return cells_copy_split(c, s);
   const uint32_t nsort = (c->ncell + kSortCells - 1) / kSortCells;
   hipLaunchKernelGGL(k_cells_sort_pos, dim3(nsort + c->nblk), dim3(kBlock), 0, s, c->entries,
                      c->entries_k, c->cellptr, c->blk_cell, c->ncell, nsort);
@@ -759,5 +932,19 @@ extern "C" int xf_batch_cells_info(const xf_batch *b, uint32_t *out) {
   const uint32_t v[8] = {c->W, c->nwin, nchunk, c->G, nitems, nseg, xf::cells_split_chunks(c),
                          c->M};
   for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return XF_OK;
+}
+
+// the forward geometry of a batch's cells (xf_cells.h): out[0..6) = rows per forward window,
+// forward windows, forward workgroups per window, 1 when the key-sorted copy is grouped by them
+// (else the three are W, nwin, G), 1 when that copy has been built, 1 when the last forward
+// (step or predict) ran on them
+extern "C" int xf_batch_fwd_info(const xf_batch *b, uint32_t *out) {
+  XF_REQUIRE(b && out, "xf_batch_fwd_info: null argument");
+  XF_REQUIRE(b->cells, "xf_batch_fwd_info: the batch has no cells yet");
+  const xf_cells *c = b->cells;
+  const uint32_t v[6] = {c->W_f, c->nwin_f, c->G_f, c->split_fwd() ? 1u : 0u,
+                         c->entries_k_ready ? 1u : 0u, c->fwd_used ? 1u : 0u};
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
   return XF_OK;
 }

@@ -176,9 +176,10 @@ k_lr_finalize_cells(const double *__restrict__ partial, const int32_t *__restric
 }
 
 // the finalize launch; fetch_c != null: with the fetch blocks for fetch_c->entries behind it
-int launch_finalize(const xf_cells *c, const double *d_partial, const int32_t *d_labels,
-                    float *d_loss, float *d_pctr, float neg_w, const xf_cells *fetch_c,
-                    hipStream_t s) {
+// (W, G): the geometry the partial sums were written on
+int launch_finalize(const xf_cells *c, uint32_t W, uint32_t G, const double *d_partial,
+                    const int32_t *d_labels, float *d_loss, float *d_pctr, float neg_w,
+                    const xf_cells *fetch_c, hipStream_t s) {
   const uint32_t nfin = (uint32_t)(((size_t)c->R * 4 + kBlock - 1) / kBlock);
   const uint4 *fetch = nullptr;
   uint32_t nvec = 0;
@@ -192,7 +193,7 @@ int launch_finalize(const xf_cells *c, const double *d_partial, const int32_t *d
   }
   const uint32_t nfetch = (nvec + kFetchVec - 1) / kFetchVec;
   hipLaunchKernelGGL(k_lr_finalize_cells, dim3(nfin + nfetch), dim3(kBlock), 0, s, d_partial,
-                     d_labels, c->R, c->W, c->G, d_loss, d_pctr, neg_w, nfin, fetch, nvec);
+                     d_labels, c->R, W, G, d_loss, d_pctr, neg_w, nfin, fetch, nvec);
   XF_HIP(hipGetLastError());
   return XF_OK;
 }
@@ -211,23 +212,36 @@ int cells_lr_forward(const xf_cells *c, const float *d_w, const int32_t *d_label
     first = resume_from;
     acc = 1;
   }
-  for (const xf_cells *q = first; q; q = q->next, acc = 1)
-    hipLaunchKernelGGL(k_lr_fwd_cells, dim3(q->nwin * q->G), dim3(kFwdBlock), 0, s, q->fwd_entries(),
-                       q->cellptr, q->blk_cell, q->nchunk, q->W, q->G,
-                       d_w + (size_t)q->chunk0 * kChunk, d_partial, acc);
+  // The forward geometry (xf_cells.h: the key-sorted copy on finer row windows of its own — the
+  // partial sums are G * 8 bytes per row whatever the windows) serves ONE segment run
+  // from the start: the segments of a chain share one partial array, so their geometry has to
+  // agree, and a resumed forward adds to sums that were left on the base geometry.  Those read the
+  // segment's `entries` on the base geometry (fwd_entries()): the one-shot path.
+  const bool split = !resume_from && !c->next && c->split_fwd() && c->entries_k_ready;
+  c->fwd_used = split;
+  if (split)
+    hipLaunchKernelGGL(k_lr_fwd_cells, dim3(c->nwin_f * c->G_f), dim3(kFwdBlock), 0, s, c->entries_k,
+                       c->cellptr_f, c->blk_cell_f, c->nchunk, c->W_f, c->G_f,
+                       d_w + (size_t)c->chunk0 * kChunk, d_partial, 0);
+  else
+    for (const xf_cells *q = first; q; q = q->next, acc = 1)
+      hipLaunchKernelGGL(k_lr_fwd_cells, dim3(q->nwin * q->G), dim3(kFwdBlock), 0, s,
+                         q->fwd_entries(), q->cellptr, q->blk_cell, q->nchunk, q->W, q->G,
+                         d_w + (size_t)q->chunk0 * kChunk, d_partial, acc);
   // The gradient's entries fetched under the finalize: the FIRST segment's, when the forward
   // read its key-sorted copy (a forward over `entries` itself has just brought them in).  Later
   // segments of a chain hold the keys that arrived after the table was settled: few, and their
   // entries have just been written.  (entry_streams = 1, xf_common.h: the finalize launch alone.)
   const bool fetch = grad_follows && !resume_from && path_switch(kPathEntryStreams) == 0 &&
                      c->entries_k_ready && c->entries_k != c->entries;
-  return launch_finalize(c, d_partial, d_labels, d_loss, d_pctr, neg_weight, fetch ? c : nullptr, s);
+  return launch_finalize(c, split ? c->W_f : c->W, split ? c->G_f : c->G, d_partial, d_labels,
+                         d_loss, d_pctr, neg_weight, fetch ? c : nullptr, s);
 }
 
 // the rows' losses from the partial sums a forward kernel of another file left (xf_cells_valued.hip)
 int cells_lr_finalize(const xf_cells *c, const double *d_partial, const int32_t *d_labels,
                       float *d_loss, float *d_pctr, hipStream_t s, float neg_weight) {
-  return launch_finalize(c, d_partial, d_labels, d_loss, d_pctr, neg_weight, nullptr, s);
+  return launch_finalize(c, c->W, c->G, d_partial, d_labels, d_loss, d_pctr, neg_weight, nullptr, s);
 }
 
 // forward up to the row sums: d_rowsum[window * W + row-in-window] = sum of the row's weights
@@ -288,6 +302,6 @@ extern "C" int xf_cells_finalize_rows(const double *d_partial, const int32_t *d_
   c.R = R;
   c.W = W;
   c.G = G;
-  return launch_finalize(&c, d_partial, d_labels, d_loss, d_pctr, neg_weight, nullptr,
+  return launch_finalize(&c, W, G, d_partial, d_labels, d_loss, d_pctr, neg_weight, nullptr,
                          (hipStream_t)stream);
 }

@@ -33,6 +33,9 @@ void scratch_poison();
 //   entry_streams  where the gradient + Push of a kept minibatch finds its entries (xf_cells_fwd.hip,
 //                DESIGN 3): 0 fetched by extra blocks of the finalize launch; 1 the finalize launch
 //                alone, the entries from wherever they are (HBM, when many minibatches are cycled)
+//   fwd_windows  the row windows of a kept minibatch's key-sorted copy, the forward's stream
+//                (xf_cells.h: cells_fwd_windows): 0 by shape; 1 the gradient's windows;
+//                n = 2 .. 32 n windows whatever the density of the cells
 //   owner_pass   an owner's gradient + Pushes for several workers: 0 by shape; 1 the general
 //                loop (a sweep per worker); 2 the workers' phases merged (k_lr_grad_ranked);
 //                3 the same with 32-bit worker masks; 4 a phase per worker (k_lr_grad_multi)
@@ -41,7 +44,7 @@ void scratch_poison();
 //                tile kernels (xf_valued.hip); 2 the local build + the valued cell kernels
 //                (xf_cells_valued.hip)
 enum PathSwitch { kPathKeyBuild = 0, kPathOldWeight, kPathLrGradient, kPathOwnerPass,
-                  kPathValuedLr, kPathEntryStreams, kPathCount };
+                  kPathValuedLr, kPathEntryStreams, kPathFwdWindows, kPathCount };
 int path_switch(int which);
 void set_path_switch(int which, int v);
 inline int key_build_mode() { return path_switch(kPathKeyBuild); }

@@ -1491,6 +1491,12 @@ extern "C" int xf_sbatch_cells_info(const xf_sbatch *b, uint32_t *out) {
   return xf_batch_cells_info(b->b, out);
 }
 
+extern "C" int xf_sbatch_fwd_info(const xf_sbatch *b, uint32_t *out) {
+  XF_REQUIRE(b && out, "xf_sbatch_fwd_info: null argument");
+  XF_REQUIRE(b->b, "xf_sbatch_fwd_info: the minibatch has no cells over a table's rows");
+  return xf_batch_fwd_info(b->b, out);
+}
+
 // the static part of the weight / gradient exchange of a minibatch with a key list (b->b):
 // contiguous owner ranges of the sorted unique keys (ps-lite's slicer), the keys to their
 // owners — once — and the owner's merged walking order
