@@ -1335,6 +1335,60 @@ int xf_cross_apply(xf_cross *x, const uint64_t *rowptr, const uint64_t *keys, co
 int xf_cross_stats(const xf_cross *x, uint64_t *rows_seen, uint64_t *nonzeros_in,
                    uint64_t *nonzeros_crossed);
 
+/* ---------------------------------------------------------------- row normalisation    */
+/* Instance-wise L2 normalisation as a GPU stage ahead of the key build (not in the reference;
+ * libffm and xLearn apply it by default).  It is the LAST stage, behind the cross, which adds
+ * nonzeros, and admission, which removes them: a row is given unit length over the nonzeros the
+ * model receives.  It changes the values only; keys, fgid, offsets and labels are not touched.
+ * Definition (csrc/xf_rownorm.h, one for the host and the kernel).  A row has nonzeros x_0 ..
+ * x_{m-1} in row order; a key that occurs twice counts twice.
+ *   s = the sum of (double)x_i * (double)x_i (each product exact in fp64), added by the pairwise
+ *       tree over the positions in row order, padded with +0.0 to a power of two: level 0 adds
+ *       positions (0,1), (2,3), ...; level 1 adds those sums in adjacent pairs; and so on.  Every
+ *       addend is >= 0, so the padding changes no bit: the result depends on the row alone, never
+ *       on a launch shape.
+ *   s > 0 and finite:  rs = 1.0 / sqrt(s), y_i = (float)((double)x_i * rs) — division, square root
+ *       and product IEEE fp64 (no fast-math, no contraction); |y_i| <= 1 up to the last rounding,
+ *       also for a row of subnormals.
+ *   otherwise:  y_i = x_i bit for bit: an empty row, a row of zeros, a row that holds a NaN or an
+ *       infinity.  Such rows stay the model's business.
+ * xf_rownorm_create: kind must be XF_ROWNORM_L2 (anything else: XF_EINVAL); nothing is allocated
+ * on the device before the first apply.
+ * xf_rownorm_apply_dev: device arrays (d_rowptr row-relative u32, R + 1; the caller guarantees
+ * rowptr[0] = 0, ascending, rowptr[R] = NNZ — the kernel still treats a row whose offsets descend
+ * or leave the arrays as empty, so it never reads or writes outside them).  Runs on `stream` with
+ * no host wait; R = 0 launches nothing.  *d_vals_out: NNZ normalised values, *d_sumsq_out (may be
+ * NULL: then the sums are not written): the R values of s.  Both are device arrays owned by the
+ * stage, grown geometrically, written in the order of `stream` and valid until the next apply on
+ * the object.  The inputs are never written.  A row of any length up to NNZ takes the same entry.
+ * xf_rownorm_apply: rows [row_begin, row_end) of a block's host arrays: checks the offsets on the
+ * CPU (descending ones are XF_EINVAL and the object lives on), uploads the slice with an uploader
+ * of its own (rowptr rebased to u32; keys, fgid when given and labels when given unchanged) and
+ * calls the device entry.  vals is required where there are nonzeros.
+ * xf_rownorm_row: the definition as host code: y[0 .. m) from x[0 .. m) (y may be x), *sumsq = s.
+ * A NULL x or y with m > 0 is XF_EINVAL naming the argument.
+ * xf_rownorm_stats, summed over the applies: rows seen (counted on the host) and rows scaled
+ * (counted on the device; reading it is the one wait of the stage).
+ * xf_rownorm_shape: {lanes that share a row, rows of a workgroup}.  xf_rownorm_launches: kernels
+ * launched by the stage in this process. */
+enum { XF_ROWNORM_L2 = 1 };
+typedef struct xf_rownorm xf_rownorm;
+int xf_rownorm_create(xf_rownorm **out, int kind);
+int xf_rownorm_destroy(xf_rownorm *n);
+int xf_rownorm_apply_dev(xf_rownorm *n, const float *d_vals, const uint32_t *d_rowptr, uint32_t R,
+                         uint32_t NNZ, void *stream, const float **d_vals_out,
+                         const double **d_sumsq_out);
+int xf_rownorm_apply(xf_rownorm *n, const uint64_t *rowptr, const uint64_t *keys,
+                     const int32_t *fgid, const float *vals, const int32_t *labels,
+                     size_t row_begin, size_t row_end, void *stream, const uint64_t **d_keys_out,
+                     const int32_t **d_fgid_out, const float **d_vals_out,
+                     const uint32_t **d_rowptr_out, const int32_t **d_labels_out, uint32_t *R_out,
+                     uint32_t *NNZ_out, const double **d_sumsq_out);
+int xf_rownorm_row(const float *x, size_t m, float *y, double *sumsq);
+int xf_rownorm_stats(const xf_rownorm *n, uint64_t *rows_seen, uint64_t *rows_scaled);
+void xf_rownorm_shape(uint32_t out[2]);
+uint64_t xf_rownorm_launches(void);
+
 /* ---------------------------------------------------------------- metrics             */
 /* Base::calculate_auc (base.h:84-110): reference-format logloss (mean of y*log2 p +
  * (1-y)*log2(1-p), negative), AUC by descending-pctr rank sum, plus the conventional
@@ -1395,6 +1449,12 @@ int XFDestroy(void **h);
  *        cross_fgid_base(N, default 0: the crossed nonzeros' fgids are N + the pair's index; read
  *        only with fm_mode=field_aware, where N + pairs <= fields).  XFGetMetric: cross_in
  *        cross_out (nonzeros into and out of the stage)
+ *        row_norm(off|l2, default off: row normalisation, xf_rownorm_* — every minibatch of this
+ *        rank's own rows, training, the held part of holdout and predict, is given unit L2 length
+ *        per row on the GPU as the last stage, behind the cross and admission; needs
+ *        feature_values=on, core_num 1, key_build=gpu, parity=exact; the setting is not saved
+ *        with the model: predict needs the same row_norm=; rank 0 prints "row_norm: rows = ...
+ *        scaled = ... left = ..." after training).  XFGetMetric: norm_rows norm_rows_scaled
  *        progress(0|1, default 0: progressive validation, xf_progress_* — every training step
  *        counts its rows' losses under the weights it is about to change, with no host wait inside
  *        an epoch; at the end of every epoch, replayed ones included, the counts are read, summed

@@ -368,6 +368,18 @@ SIGNATURES = {
                                  C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32)]),
     "xf_cross_stats": (C.c_int, [vp, u64p, u64p, u64p]),
+    "xf_rownorm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
+    "xf_rownorm_destroy": (C.c_int, [vp]),
+    "xf_rownorm_apply_dev": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.POINTER(vp),
+                                       C.POINTER(vp)]),
+    "xf_rownorm_apply": (C.c_int, [vp, u64p, u64p, i32p, f32p, i32p, C.c_size_t, C.c_size_t, vp,
+                                   C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                   C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                   C.POINTER(vp)]),
+    "xf_rownorm_row": (C.c_int, [f32p, C.c_size_t, f32p, C.POINTER(C.c_double)]),
+    "xf_rownorm_stats": (C.c_int, [vp, u64p, u64p]),
+    "xf_rownorm_shape": (None, [u32p]),
+    "xf_rownorm_launches": (C.c_uint64, []),
     "XFCreate": (C.c_int, [C.POINTER(vp), C.c_char_p, C.c_char_p]),
     "XFStartTrain": (C.c_int, [C.POINTER(vp)]),
     "XFDestroy": (C.c_int, [C.POINTER(vp)]),
@@ -1350,6 +1362,117 @@ class Cross:
         return tuple(x.value for x in v)
 
 
+ROWNORM_L2 = 1
+
+
+def rownorm_row(x):
+    """(y, s): one row's values normalised to unit L2 length and its sum of squares, by the
+    definition of csrc/xf_rownorm.h as host code (xf_rownorm_row; no GPU)"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.empty_like(x)
+    s = C.c_double()
+    one = np.zeros(1, np.float32)
+    check(lib().xf_rownorm_row(_p(x if len(x) else one, f32p), len(x),
+                               _p(y if len(y) else one, f32p), C.byref(s)))
+    return y, s.value
+
+
+class RowNorm:
+    """Row normalisation (xf_rownorm_*): every row of a minibatch scaled to unit L2 length over
+    its nonzeros; a row whose sum of squares is 0, infinite or NaN is left as it is.  Only the
+    values change.  Stateless but for the statistics."""
+
+    def __init__(self, kind=ROWNORM_L2):
+        self.h = vp()
+        check(lib().xf_rownorm_create(C.byref(self.h), int(kind)))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().xf_rownorm_destroy(self.h)
+            self.h = None
+
+    @staticmethod
+    def shape():
+        """(lanes that share a row, rows of a workgroup)"""
+        out = np.zeros(2, np.uint32)
+        lib().xf_rownorm_shape(_p(out, u32p))
+        return int(out[0]), int(out[1])
+
+    @staticmethod
+    def launches():
+        """kernels launched by the stage in this process"""
+        return int(lib().xf_rownorm_launches())
+
+    def apply_dev(self, rowptr, keys, values, labels=None, fgid=None, row_begin=0, row_end=None,
+                  stream=None):
+        """host arrays in (rows [row_begin, row_end) uploaded by the stage), the minibatch with
+        normalised values as an AdmitDev out, and the device pointer of the rows' sums of squares
+        (device arrays owned by the stage, valid until its next apply).  WRITTEN IN THE ORDER OF
+        `stream`; the call does not wait: hand them to work on the same stream or wait first"""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        assert len(rowptr) >= 1
+        row_end = len(rowptr) - 1 if row_end is None else row_end
+        args = []
+        for a, dt, pt in ((fgid, np.int32, i32p), (values, np.float32, f32p)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=dt)
+                assert len(a) == len(keys), "one entry per key"
+                a = a if len(a) else np.zeros(1, dt)
+            args.append((a, pt))
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            assert len(labels) == len(rowptr) - 1, "one label per row"
+            labels = labels if len(labels) else np.zeros(1, np.int32)
+        args.append((labels, i32p))
+        if len(keys) == 0:
+            keys = np.zeros(1, np.uint64)
+        ptr = [(_p(a, pt) if a is not None else None) for a, pt in args]
+        dk, dfg, dv, dr, dl, ds = vp(), vp(), vp(), vp(), vp(), vp()
+        Ro, No = C.c_uint32(), C.c_uint32()
+        check(lib().xf_rownorm_apply(self.h, _p(rowptr, u64p), _p(keys, u64p), ptr[0], ptr[1],
+                                     ptr[2], row_begin, row_end, stream, C.byref(dk),
+                                     C.byref(dfg), C.byref(dv), C.byref(dr), C.byref(dl),
+                                     C.byref(Ro), C.byref(No), C.byref(ds)))
+        return AdmitDev(dk.value, dr.value, dl.value, Ro.value, No.value, dfg.value,
+                        dv.value), ds.value
+
+    def norm_dev(self, d_vals, d_rowptr, R, NNZ, stream=None, want_sumsq=True):
+        """xf_rownorm_apply_dev: device pointers in (ints), (d_vals_out, d_sumsq_out) out"""
+        dv, ds = vp(), vp()
+        check(lib().xf_rownorm_apply_dev(self.h, d_vals, d_rowptr, R, NNZ, stream, C.byref(dv),
+                                         C.byref(ds) if want_sumsq else None))
+        return dv.value, ds.value
+
+    @staticmethod
+    def download(ptr, n, dtype):
+        """n entries of a device array, after a wait for the device"""
+        check(lib().xf_stream_sync(None))
+        a = np.zeros(n, dtype)
+        if a.nbytes:
+            check(lib().xf_copy_to_host(a.ctypes.data, ptr, a.nbytes))
+        return a
+
+    def apply(self, rowptr, keys, values, labels=None, fgid=None, row_begin=0, row_end=None):
+        """the host arrays of the normalised minibatch (downloaded): (rowptr uint32, keys, values,
+        sums of squares float64) and then, for each of labels / fgid that was given, its array"""
+        d, ds = self.apply_dev(rowptr, keys, values, labels, fgid, row_begin, row_end)
+        out = [self.download(d.d_rowptr, d.R + 1, np.uint32),
+               self.download(d.d_keys, d.NNZ, np.uint64),
+               self.download(d.d_vals, d.NNZ, np.float32), self.download(ds, d.R, np.float64)]
+        if labels is not None:
+            out.append(self.download(d.d_labels, d.R, np.int32))
+        if fgid is not None:
+            out.append(self.download(d.d_fgid, d.NNZ, np.int32))
+        return tuple(out)
+
+    def stats(self):
+        """(rows seen, rows scaled), summed over the applies; reading waits for the device"""
+        v = [C.c_uint64() for _ in range(2)]
+        check(lib().xf_rownorm_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
 class Batch:
     """A compiled minibatch (host arrays; device mirror after upload())."""
 
@@ -2239,7 +2362,8 @@ class Sharded:
 
 
 class XFlow:
-    """XFCreate / XFSetParam / XFStartTrain / XFGetMetric / XFDestroy."""
+    """XFCreate / XFSetParam / XFStartTrain / XFGetMetric / XFDestroy.  Every keyword is an
+    XFSetParam name (include/xflow_amd.h lists them): cross="2*3", row_norm="l2", ..."""
 
     def __init__(self, train_prefix, test_prefix, **params):
         self.h = vp()

@@ -34,6 +34,9 @@ int main(int argc, char *argv[]) {
               << "feature crosses (a nonzero per listed pair of fields and per pair of their "
                  "members, formed on the GPU; predict needs the same spec): append cross=2*3,16*17 "
                  "[cross_fgid_base=N with fm_mode=field_aware]\n"
+              << "row normalisation (every row scaled to unit L2 length on the GPU, behind the "
+                 "crosses and admission; needs feature_values=on; predict needs the same "
+                 "setting): append row_norm=l2\n"
               << "held-out validation (a hash-chosen share r of the training rows is never trained "
                  "on and scored after every E-th epoch; stop after P validated epochs without "
                  "improvement): append holdout=r [holdout_every=E early_stop=P "

@@ -57,6 +57,7 @@ Worker::~Worker() {
   if (admit_) xf_admit_destroy(admit_);
   if (sample_) xf_negsample_destroy(sample_);
   if (cross_) xf_cross_destroy(cross_);
+  if (norm_) xf_rownorm_destroy(norm_);
   if (slicer_) xf_slices_destroy(slicer_);
   if (sharded_) xf_sharded_destroy(sharded_);  // owns the tables
   if (group_) xf_group_destroy(group_);
@@ -76,11 +77,15 @@ static const char *env_first(std::initializer_list<const char *> names) {
 // environment, as scripts/local.sh sets it) this process joins the group — one process per
 // GPU — and its tables are one key-range shard of the parameter table.
 int Worker::create_tables() {
+  // (row_norm's refusals by its own name, also where XFLoadModel builds the tables: ahead of the
+  // warm-up below, which would refuse a valued minibatch on key_build=host in its own words)
+  XF_TRY(check_rownorm());
   if (sharded_) {
     XF_TRY(create_admit());
     XF_TRY(create_negsample());
     XF_TRY(create_holdout());
-    return create_cross();
+    XF_TRY(create_cross());
+    return create_rownorm();
   }
   int w = world;
   if (w <= 0) {
@@ -163,7 +168,8 @@ int Worker::create_tables() {
   XF_TRY(create_admit());
   XF_TRY(create_negsample());
   XF_TRY(create_holdout());
-  return create_cross();
+  XF_TRY(create_cross());
+  return create_rownorm();
 }
 
 static int world_from_env(int world) {
@@ -675,6 +681,64 @@ int Worker::create_cross() {
   return rc;
 }
 
+// Row normalisation rescales a minibatch's values on the GPU immediately ahead of the key build:
+// without feature values there is nothing to scale, core_num > 1 slices a block after it was
+// read, and the host key build and the reference-order forward take host arrays.  All refused by
+// name, before any rendezvous.
+int Worker::check_rownorm() const {
+  if (!row_norm) return XF_OK;
+  XF_REQUIRE(feature_values, "XFStartTrain: row_norm=l2 needs feature_values=on: without values "
+             "every nonzero is 1 and a row has nothing to scale");
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: row_norm=l2 needs core_num=1, not core_num=%d",
+             core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: row_norm=l2 together with key_build=host: the "
+             "normalised minibatch is born on the GPU (use key_build=gpu)");
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: row_norm=l2 together with "
+             "parity=reference_order: that mode builds its keys on the host");
+  return XF_OK;
+}
+
+int Worker::create_rownorm() {
+  if (!row_norm || norm_) return XF_OK;
+  XF_TRY(check_rownorm());
+  XF_TRY(xf_rownorm_create(&norm_, XF_ROWNORM_L2));
+  // the stage's first launch, on two rows of a private stage: start-up work like the two-row
+  // update of create_tables (the worker's own stage keeps its statistics clean)
+  xf_rownorm *warm = nullptr;
+  XF_TRY(xf_rownorm_create(&warm, XF_ROWNORM_L2));
+  static const uint64_t rp[3] = {0, 2, 4}, keys[4] = {11, 12, 12, 13};
+  static const float vals[4] = {1.0f, 0.5f, 0.25f, 2.0f};
+  void *stream = nullptr;
+  int rc = xf_sharded_stream(sharded_, &stream);
+  const uint64_t *fk = nullptr;
+  const float *fv = nullptr;
+  const uint32_t *fr = nullptr;
+  uint32_t R = 0, NNZ = 0;
+  if (rc == XF_OK)
+    rc = xf_rownorm_apply(warm, rp, keys, nullptr, vals, nullptr, 0, 2, stream, &fk, nullptr, &fv,
+                          &fr, nullptr, &R, &NNZ, nullptr);
+  if (rc == XF_OK) rc = xf_stream_sync(stream);
+  xf_rownorm_destroy(warm);
+  return rc;
+}
+
+// rows [start, end) of host arrays through row normalisation alone: uploaded by the stage, then
+// the _dev compile of the worker's mode
+int Worker::compile_normed(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                           const int32_t *fgid, const float *vals, const int32_t *labels,
+                           size_t start, size_t end, int keep) {
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const uint64_t *fk = nullptr;
+  const int32_t *ff = nullptr, *fl = nullptr;
+  const float *fv = nullptr;
+  const uint32_t *fr = nullptr;
+  uint32_t R = 0, NNZ = 0;
+  XF_TRY(xf_rownorm_apply(norm_, rowptr, keys, fm_mode == XF_FM_FIELD_AWARE ? fgid : nullptr, vals,
+                          labels, start, end, stream, &fk, &ff, &fv, &fr, &fl, &R, &NNZ, nullptr));
+  return compile_dev_mode(b, fk, ff, fv, fr, fl, R, NNZ, keep);
+}
+
 // the stages that follow sampling, on device arrays: the cross, when on (a block without rows has
 // nothing to cross), admission, when on, and the _dev compile of the worker's mode
 int Worker::compile_staged_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
@@ -806,6 +870,9 @@ int Worker::compile_rows_unsliced(xf_sharded *trainer, xf_sbatch **b, int update
                                   keep);
     return compile_admitted(b, update, rowptr, keys, fgid, vals, labels, start, end, keep);
   }
+  // (row normalisation with no other stage on: rows of this rank's own, training and predict)
+  if (norm_ && trainer == sharded_ && rowptr && end > start)
+    return compile_normed(b, rowptr, keys, fgid, vals, labels, start, end, keep);
   if (fm_mode == XF_FM_FIELD_AWARE)
     return xf_sharded_compile_fielded(trainer, b, rowptr, keys, fgid,
                                       feature_values ? vals : nullptr, labels, start, end, keep);
@@ -816,10 +883,22 @@ int Worker::compile_rows_unsliced(xf_sharded *trainer, xf_sbatch **b, int update
   return compile_no_rows(trainer, b, keep);
 }
 
-// the _dev compile of the worker's mode on device arrays
+// row normalisation, when on — the last stage, over the nonzeros the model receives — and the _dev
+// compile of the worker's mode on device arrays
 int Worker::compile_dev_arrays(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
                                const float *d_vals, const uint32_t *d_rowptr,
                                const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
+  if (norm_ && R) {
+    void *stream = nullptr;
+    XF_TRY(xf_sharded_stream(sharded_, &stream));
+    XF_TRY(xf_rownorm_apply_dev(norm_, d_vals, d_rowptr, R, NNZ, stream, &d_vals, nullptr));
+  }
+  return compile_dev_mode(b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
+}
+
+int Worker::compile_dev_mode(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
+                             const float *d_vals, const uint32_t *d_rowptr,
+                             const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
   if (fm_mode == XF_FM_FIELD_AWARE)
     return xf_sharded_compile_fielded_dev(sharded_, b, d_keys, d_fgid,
                                           feature_values ? d_vals : nullptr, d_rowptr, d_labels, R,
@@ -1527,6 +1606,7 @@ int Worker::train() {
   slices_have_ = false;
   XF_TRY(check_evict());
   XF_TRY(check_cross());
+  XF_TRY(check_rownorm());
   XF_TRY(create_tables());
   XF_TRY(start_ingest());
   std::cout << "my rank is = " << rank << std::endl;
@@ -1536,6 +1616,15 @@ int Worker::train() {
     XF_TRY(XFLoadModel(self, model_in.c_str()));
   }
   XF_TRY(batch_training());
+  if (norm_ && rank == 0) {  // (the training minibatches and the held ones; predict follows)
+    uint64_t rows = 0, scaled = 0;
+    XF_TRY(xf_rownorm_stats(norm_, &rows, &scaled));
+    char line[160];
+    snprintf(line, sizeof(line), "row_norm: rows = %llu scaled = %llu left = %llu",
+             (unsigned long long)rows, (unsigned long long)scaled,
+             (unsigned long long)(rows - scaled));
+    std::cout << line << std::endl;
+  }
   if (!model_out.empty()) {
     void *self = this;
     XF_TRY(XFSaveModel(self, model_out.c_str()));
@@ -1699,6 +1788,14 @@ int Worker::set_param(const char *name, const char *value) {
   } else if (n == "cross") {
     XF_REQUIRE(!cross_, "XFSetParam: cross cannot change once the stage exists");
     cross_spec = value;
+  } else if (n == "row_norm") {
+    const bool on = !strcmp(value, "l2");
+    XF_REQUIRE(on || !strcmp(value, "off"), "XFSetParam: row_norm must be l2 or off, not '%s'",
+               value);
+    // (the stages are created with the tables: from then on the worker runs with or without one)
+    XF_REQUIRE(!sharded_ || on == row_norm,
+               "XFSetParam: row_norm cannot change once the stage exists");
+    row_norm = on;
   } else if (n == "cross_fgid_base") {
     XF_REQUIRE(!cross_, "XFSetParam: cross_fgid_base cannot change once the stage exists");
     cross_fgid_base = atoi(value);
@@ -1785,6 +1882,10 @@ int Worker::get_metric(const char *name, double *value) {
     uint64_t in = 0, crossed = 0;
     if (cross_) XF_TRY(xf_cross_stats(cross_, nullptr, &in, &crossed));
     *value = (double)(n == "cross_in" ? in : in + crossed);
+  } else if (n == "norm_rows" || n == "norm_rows_scaled") {
+    uint64_t rows = 0, scaled = 0;
+    if (norm_) XF_TRY(xf_rownorm_stats(norm_, &rows, &scaled));
+    *value = (double)(n == "norm_rows" ? rows : scaled);
   } else if (n == "admit_seen" || n == "admit_kept") {
     uint64_t seen = 0, kept = 0;
     if (admit_) XF_TRY(xf_admit_stats(admit_, &seen, &kept));

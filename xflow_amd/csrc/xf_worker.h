@@ -101,6 +101,13 @@ class Worker {
   // read only with fm_mode=field_aware (base + pairs <= fields).  Nothing travels with the model.
   std::string cross_spec;
   int cross_fgid_base = 0;
+  // Row normalisation (xf_rownorm.hip): row_norm = l2: every minibatch of this rank's own rows —
+  // training, the held part of holdout, predict — gets unit L2 length per row on the GPU.  The
+  // LAST stage, immediately ahead of the key build: ingest, split, negsample, slices, cross,
+  // admission, row norm, compile — over the nonzeros the model receives.  Off = nothing is
+  // created.  Needs feature_values=on, core_num 1, key_build=gpu, parity=exact (checked where
+  // training starts).  Nothing travels with the model: predict needs the same row_norm=.
+  bool row_norm = false;
   // Progressive validation (xf_progress.hip): progress = 1: every training step counts its rows'
   // losses — formed under the weights the step is about to change — on the GPU, with no host wait
   // inside an epoch; at the end of each epoch (replayed ones included) the counts are read, merged
@@ -246,6 +253,18 @@ class Worker {
   int compile_dev_arrays(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
                          const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
                          uint32_t R, uint32_t NNZ, int keep);
+  // ... compile_dev_arrays without row normalisation in front (the values are normalised already)
+  int compile_dev_mode(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
+                       const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
+                       uint32_t R, uint32_t NNZ, int keep);
+  xf_rownorm *norm_ = nullptr;  // row_norm=l2: the stage, created with the tables
+  int check_rownorm() const;    // the refusals of row_norm, before any rendezvous
+  int create_rownorm();
+  // rows [start, end) of host arrays with no other stage on: uploaded by the stage, then the
+  // _dev compile
+  int compile_normed(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
+                     const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
+                     size_t end, int keep);
   uint64_t keys_seen_ = 0;  // the table's keys at the last look (defrag_if_grown: the inflow per minibatch)
   bool rank_given_ = false;
 
