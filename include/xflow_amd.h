@@ -1273,6 +1273,90 @@ int xf_sharded_validate(xf_sharded *st, xf_sbatch *b);
 int xf_sharded_holdout_read(xf_sharded *st, uint64_t *counts, uint64_t *other, int reset,
                             int merged);
 
+/* ---------------------------------------------------------------- grouped AUC, held-out */
+/* The AUC inside each value of ONE field (user, query, placement ...), averaged with the group's
+ * rows as weight (GAUC; not in the reference), on the held-out rows: it rewards ordering the
+ * impressions WITHIN a group, which a global AUC does not.  An AUC needs a group's rows ordered by
+ * score, so the device keeps a log of records and a reduce sorts it.  The device only produces
+ * integers, so its result depends on nothing but the multiset of records — not the order of the
+ * appends, the launch shapes or how many appends the records came in — and is compared with ==.
+ * Record.  A row leaves (id, code): id its slice id by xf_slices' rule for field F; with
+ * rank = xf_progress_rank(loss), pos = (label != 0), C as in progressive validation:
+ *   rank == XF_PROGRESS_RANKS (NaN, q > 1): counted in other[pos], no record
+ *   otherwise id == XF_SLICE_NONE:          counted in none[pos], no record
+ *   otherwise score = pos ? 2C - rank : rank (monotone in p: the score rank the global AUC uses),
+ *             code = (score << 1) | pos, a uint32
+ * xf_gauc_code is that function as host code, from the one definition the kernel uses; UINT32_MAX
+ * for the `other` case.
+ * Group figures.  XF_GAUC_WORDS = 4 64-bit words per distinct id: P and N, the group's positive
+ * and negative records; U2 = the sum over the group's distinct scores b, ascending, of
+ * pos_b (2 neg_below_b + neg_b); T = the sum of pos_b neg_b, the tie mass.  Exact integers; with
+ * fewer than 2^30 records U2 < 2^60.
+ * xf_gauc_append_dev: R rows of device arrays, one launch on `stream` (none with R = 0); the
+ * records go to a device log of two arrays (ids u64, codes u32), none[2] and other[2] are counted
+ * on the device.  The log grows on demand in the order of the stream; growing waits for the
+ * stream, so xf_gauc_reserve(g, rows) sizes the log ahead and an append then waits for nothing.
+ * xf_gauc_append: ready-made records from host arrays (a UINT32_MAX or otherwise impossible code
+ * or the id XF_SLICE_NONE: XF_EINVAL); waits.  xf_gauc_export: the log as it stands (ids and codes
+ * both NULL: only *n), one wait.
+ * xf_gauc_reduce: the figures of everything appended so far: *n entries of (id, P, N, U2, T), five
+ * words each, sorted by id ascending, and none[2] / other[2] (either may be NULL).  entries == NULL:
+ * only *n and the two pairs (reset must be 0).  *n > cap: XF_EINVAL, nothing reset.  reset != 0:
+ * the log and the counters are emptied after the copy.  Reducing twice without a reset gives the
+ * same result; no records: *n = 0 and no launch; 2^30 records or more: XF_EINVAL.  The records are
+ * sorted by code and then stably by id (two passes of xf_sort_key_pos); one segmented pass forms
+ * the figures.  xf_gauc_launches: the pack launches since the library was loaded.  xf_gauc_shape:
+ * {rows of a pack workgroup, records of a reduce workgroup}, for the tests that aim at the edges.
+ * Summary (host, no GPU), fp64, the groups in the order given (ascending id; anything else is
+ * XF_EINVAL).  A group is scored iff P > 0 and N > 0:
+ *   auc_g = fl(U2) / fl(2 P N), slack_g = fl(T) / fl(2 P N), rows_g = P + N
+ *   gauc = the sum over the scored groups of w_g * auc_g, w_g = fl(rows_g) / fl(rows_scored) the
+ *   group's share of the scored groups' rows (one group alone weighs exactly 1: its gauc is its auc
+ *   bit for bit); gauc_slack the same with slack_g; macro_auc = (sum of auc_g) / fl(groups_scored)
+ *   groups, groups_scored, rows (every record), rows_scored, rows_one_class, none_rows, other_rows
+ * No scored group: the three means are NaN and the call succeeds.  The exact tie-aware GAUC of the
+ * rows' p lies within gauc +- gauc_slack (progress's argument for auc_slack, per group).  auc and
+ * slack (may be NULL): n per-group values, NaN for a group that is not scored.
+ * Tap.  On VALIDATE only, never on a training step or on predict.  xf_workspace_gauc(ws, g)
+ * attaches an object (NULL: off, the default; the caller keeps g alive); xf_workspace_gauc_ids(ws,
+ * d_id, R) names the ids of the NEXT xf_lr_validate / xf_fm_validate's rows (a device array the
+ * caller keeps alive until that validate has run).  That validate appends right after its
+ * xf_progress_accumulate_dev, from the same losses and labels, and forgets the ids; ids of another
+ * R are XF_EINVAL naming both; a validate without ids appends nothing.  With nothing attached
+ * validate, predict and every step are launch for launch and bit for bit what they were.
+ * xf_sharded_gauc(st, enable): the trainer owns one (created at 1, freed at 0); needs
+ * xf_sharded_holdout on and inherits its refusals.  xf_sharded_validate then appends the records
+ * of a minibatch that carries ids (xf_sbatch_set_slices) on both of its paths.
+ * xf_sharded_gauc_read: flushes, then reduces this rank's records; merged != 0: COLLECTIVE, the
+ * ranks' exported records go to rank 0 (xf_group_gatherv_host) and are reduced there — a group's
+ * rows are spread over the ranks, so figures of parts cannot be merged; rank 0 gets the result,
+ * the others *n = 0 and zeros; reset empties every rank's log. */
+#define XF_GAUC_WORDS 4
+typedef struct xf_gauc xf_gauc;
+typedef struct {
+  double gauc, gauc_slack, macro_auc;
+  uint64_t groups, groups_scored, rows, rows_scored, rows_one_class, none_rows, other_rows;
+} xf_gauc_metrics;
+uint32_t xf_gauc_code(float loss, int32_t label);
+int xf_gauc_summary(const uint64_t *entries, uint64_t n, const uint64_t *none,
+                    const uint64_t *other, xf_gauc_metrics *out, double *auc, double *slack);
+int xf_gauc_create(xf_gauc **out);
+int xf_gauc_destroy(xf_gauc *g);
+int xf_gauc_reserve(xf_gauc *g, uint64_t rows);
+int xf_gauc_append_dev(xf_gauc *g, const float *d_loss, const int32_t *d_labels,
+                       const uint64_t *d_id, uint32_t R, void *stream);
+int xf_gauc_append(xf_gauc *g, const uint64_t *ids, const uint32_t *codes, uint64_t n);
+int xf_gauc_export(xf_gauc *g, uint64_t *ids, uint32_t *codes, uint64_t cap, uint64_t *n);
+int xf_gauc_reduce(xf_gauc *g, uint64_t *entries, uint64_t cap, uint64_t *n, uint64_t *none,
+                   uint64_t *other, int reset);
+uint64_t xf_gauc_launches(void);
+void xf_gauc_shape(uint32_t out[2]);
+int xf_workspace_gauc(xf_workspace *ws, xf_gauc *g);
+int xf_workspace_gauc_ids(xf_workspace *ws, const uint64_t *d_id, uint32_t R);
+int xf_sharded_gauc(xf_sharded *st, int enable);
+int xf_sharded_gauc_read(xf_sharded *st, uint64_t *entries, uint64_t cap, uint64_t *n,
+                         uint64_t *none, uint64_t *other, int reset, int merged);
+
 /* ---------------------------------------------------------------- feature crosses      */
 /* Crossed features as a GPU stage ahead of the key build (not in the reference).  Like admission
  * and negative subsampling it works on a minibatch's CSR arrays and its result goes to any *_dev
@@ -1498,7 +1582,19 @@ int XFDestroy(void **h);
  *        after-the-last-epoch pass, save and predict follow) early_stop_delta(d >= 0, default 0).
  *        XFGetMetric: holdout_rows holdout_logloss holdout_auc holdout_auc_slack holdout_ctr
  *        holdout_pctr (the last validated epoch) holdout_logloss_first holdout_best_epoch
- *        holdout_best_logloss epochs_run; rows_trained excludes held rows */
+ *        holdout_best_logloss epochs_run; rows_trained excludes held rows
+ *        holdout_by(F in 0 .. 2^31 - 1, default off; needs holdout > 0: the grouped AUC of the
+ *        held rows, xf_gauc_* — a held row's group is the key of its first nonzero of field F, named
+ *        on the GPU as the split hands the held part over, before the cross and admission; every
+ *        validated epoch appends the held rows' records, and after the "holdout epoch E:" line the
+ *        records are reduced — merged on rank 0 over the workers — and rank 0 prints "holdout groups
+ *        epoch E: field = F groups = G scored = S rows = ... scored_rows = ... none_rows = ... gauc =
+ *        ... (+- slack) macro_auc = ..." (and other_rows = ... when there are any).  core_num 1,
+ *        key_build=gpu, ingest=host or gpu_fields; the early-stop rule keeps reading the logloss;
+ *        nothing is saved with the model) holdout_groups_out(PATH: rank 0 appends one tab-separated
+ *        line per group and epoch, by key: epoch, key (0x...), P, N, auc, slack).  XFGetMetric (the
+ *        last validated epoch): holdout_gauc holdout_gauc_slack holdout_macro_auc holdout_groups
+ *        holdout_groups_scored holdout_gauc_rows (the scored groups' rows) */
 int XFSetParam(void *h, const char *name, const char *value);
 /* after XFStartTrain: logloss_ref, logloss_nat, auc, tp, fp, rows_trained, train_seconds,
  * examples_per_sec, keys */

@@ -20,7 +20,7 @@ LIB_SOURCES = ["xf_table.hip", "xf_model.hip", "xf_calib.hip", "xf_batch_dev.hip
                "xf_admit_host.cc", "xf_negsample.hip", "xf_cross.hip", "xf_cross_host.cc",
                "xf_progress.hip", "xf_progress_host.cc", "xf_scalar_probe.hip", "xf_evict.hip",
                "xf_slices.hip", "xf_slices_host.cc", "xf_holdout.hip", "xf_holdout_host.cc",
-               "xf_rownorm.hip", "xf_rownorm_host.cc"]
+               "xf_rownorm.hip", "xf_rownorm_host.cc", "xf_gauc.hip", "xf_gauc_host.cc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-result", "-Wno-unused-value",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]

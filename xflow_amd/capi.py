@@ -348,6 +348,23 @@ SIGNATURES = {
     "xf_slices_read": (C.c_int, [vp, u64p, C.c_uint64, u64p, u64p, u64p, C.c_int]),
     "xf_slices_launches": (C.c_uint64, []),
     "xf_slices_shape": (None, [C.POINTER(C.c_uint32)]),
+    "xf_gauc_code": (C.c_uint32, [C.c_float, C.c_int32]),
+    "xf_gauc_summary": (C.c_int, [u64p, C.c_uint64, u64p, u64p, vp, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double)]),
+    "xf_gauc_create": (C.c_int, [C.POINTER(vp)]),
+    "xf_gauc_destroy": (C.c_int, [vp]),
+    "xf_gauc_reserve": (C.c_int, [vp, C.c_uint64]),
+    "xf_gauc_append_dev": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp]),
+    "xf_gauc_append": (C.c_int, [vp, u64p, C.POINTER(C.c_uint32), C.c_uint64]),
+    "xf_gauc_export": (C.c_int, [vp, u64p, C.POINTER(C.c_uint32), C.c_uint64, u64p]),
+    "xf_gauc_reduce": (C.c_int, [vp, u64p, C.c_uint64, u64p, u64p, u64p, C.c_int]),
+    "xf_gauc_launches": (C.c_uint64, []),
+    "xf_gauc_shape": (None, [C.POINTER(C.c_uint32)]),
+    "xf_workspace_gauc": (C.c_int, [vp, vp]),
+    "xf_workspace_gauc_ids": (C.c_int, [vp, vp, C.c_uint32]),
+    "xf_sharded_gauc": (C.c_int, [vp, C.c_int]),
+    "xf_sharded_gauc_read": (C.c_int, [vp, u64p, C.c_uint64, u64p, u64p, u64p, C.c_int,
+                                       C.c_int]),
     "xf_workspace_slices": (C.c_int, [vp, vp]),
     "xf_workspace_slice_ids": (C.c_int, [vp, vp, C.c_uint32]),
     "xf_sharded_slices": (C.c_int, [vp, C.c_int, C.c_int32, C.c_int]),
@@ -1258,6 +1275,127 @@ class Slices:
         return _slices_result(entries, n.value, none, overflow)
 
 
+GAUC_WORDS = 4
+GAUC_OTHER = 2**32 - 1
+u32p = C.POINTER(C.c_uint32)
+
+
+class GaucMetrics(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("gauc", "gauc_slack", "macro_auc")] + \
+               [(n, C.c_uint64) for n in ("groups", "groups_scored", "rows", "rows_scored",
+                                          "rows_one_class", "none_rows", "other_rows")]
+
+
+def gauc_code(loss, label):
+    """the code of a row's record (xf_gauc_code; host code, the kernel's own definition):
+    (score << 1) | pos, GAUC_OTHER for a NaN loss and q > 1"""
+    return int(lib().xf_gauc_code(float(np.float32(loss)), int(np.int32(label))))
+
+
+def gauc_summary(ids, figures, none=None, other=None):
+    """xf_gauc_summary (host code): ids uint64 [n] ascending, figures uint64 [n, 4] = P, N, U2, T
+    -> (a dict of the metrics' fields, auc [n], slack [n])"""
+    ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+    figures = np.ascontiguousarray(figures, dtype=np.uint64).reshape(-1, GAUC_WORDS)
+    assert len(ids) == len(figures)
+    n = len(ids)
+    entries = np.zeros((max(n, 1), GAUC_WORDS + 1), np.uint64)
+    entries[:n, 0] = ids
+    entries[:n, 1:] = figures
+    none = np.ascontiguousarray(none if none is not None else [0, 0], dtype=np.uint64)
+    other = np.ascontiguousarray(other if other is not None else [0, 0], dtype=np.uint64)
+    auc, slack = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+    m = GaucMetrics()
+    dp = C.POINTER(C.c_double)
+    check(lib().xf_gauc_summary(_p(entries, u64p), n, _p(none, u64p), _p(other, u64p),
+                                C.byref(m), _p(auc, dp), _p(slack, dp)))
+    return {k: getattr(m, k) for k, _ in GaucMetrics._fields_}, auc[:n], slack[:n]
+
+
+def gauc_launches():
+    return int(lib().xf_gauc_launches())
+
+
+def gauc_shape():
+    """{rows of a pack workgroup, records of a reduce workgroup}"""
+    out = (C.c_uint32 * 2)()
+    lib().xf_gauc_shape(out)
+    return dict(zip(("pack_rows", "reduce_records"), list(out)))
+
+
+def _gauc_result(entries, n, none, other):
+    e = entries[:n]
+    return e[:, 0].copy(), e[:, 1:].copy(), none, other
+
+
+class Gauc:
+    """Grouped AUC on the held-out rows (xf_gauc_*): a device log of (id, code) records.
+    append_dev() packs rows' records, append() takes ready-made ones; attach it to a Workspace
+    (Workspace.gauc / gauc_ids); reduce() returns (ids ascending, figures [n, 4] = P, N, U2, T,
+    none [2], other [2]); summary() forms the metrics on the host."""
+
+    code = staticmethod(gauc_code)
+
+    def __init__(self):
+        require_gpu()
+        self.h = vp()
+        check(lib().xf_gauc_create(C.byref(self.h)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().xf_gauc_destroy(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+    def reserve(self, rows):
+        check(lib().xf_gauc_reserve(self.h, int(rows)))
+
+    def append_dev(self, d_loss, d_labels, d_id, R, stream=None):
+        """device pointers (ints): R losses (f32), labels (i32) and ids (u64); one launch"""
+        check(lib().xf_gauc_append_dev(self.h, d_loss, d_labels, d_id, int(R), stream))
+
+    def append(self, ids, codes):
+        ids = np.ascontiguousarray(ids, dtype=np.uint64)
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        assert len(ids) == len(codes)
+        check(lib().xf_gauc_append(self.h, _p(ids, u64p) if len(ids) else None,
+                                   _p(codes, u32p) if len(ids) else None, len(ids)))
+
+    def count(self):
+        n = C.c_uint64()
+        check(lib().xf_gauc_export(self.h, None, None, 0, C.byref(n)))
+        return n.value
+
+    def export(self):
+        """(ids, codes) of the log as it stands, in the log's order"""
+        cap = max(self.count(), 1)
+        ids, codes = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+        n = C.c_uint64()
+        check(lib().xf_gauc_export(self.h, _p(ids, u64p), _p(codes, u32p), cap, C.byref(n)))
+        return ids[:n.value].copy(), codes[:n.value].copy()
+
+    def groups(self):
+        """the distinct ids (a reduce that copies no entry)"""
+        n = C.c_uint64()
+        check(lib().xf_gauc_reduce(self.h, None, 0, C.byref(n), None, None, 0))
+        return n.value
+
+    def reduce(self, reset=False, cap=None):
+        cap = max(self.groups(), 1) if cap is None else int(cap)
+        entries = np.zeros((max(cap, 1), GAUC_WORDS + 1), np.uint64)
+        none, other = np.zeros(2, np.uint64), np.zeros(2, np.uint64)
+        n = C.c_uint64()
+        check(lib().xf_gauc_reduce(self.h, _p(entries, u64p), cap, C.byref(n), _p(none, u64p),
+                                   _p(other, u64p), 1 if reset else 0))
+        return _gauc_result(entries, n.value, none, other)
+
+    def summary(self, reset=False):
+        ids, fig, none, other = self.reduce(reset)
+        return gauc_summary(ids, fig, none, other)[0]
+
+
 def slice_ids(rowptr, keys, fgid, field, row_begin=0, row_end=None):
     """the slice ids of the rows of host arrays for field `field`, computed on the GPU (a
     throw-away Slices object's extract)"""
@@ -1963,6 +2101,17 @@ class Workspace:
         training step's R rows; None: that step counts no slice"""
         check(lib().xf_workspace_slice_ids(self.h, d_id, int(R)))
 
+    def gauc(self, g):
+        """attach a Gauc (None: off, the default): a VALIDATE that was given its rows' ids
+        (gauc_ids) appends their records right after the progress has counted them"""
+        check(lib().xf_workspace_gauc(self.h, g.h if g is not None else None))
+        self._gauc = g
+
+    def gauc_ids(self, d_id, R):
+        """the group ids (a device pointer the caller keeps alive until the validate has run) of
+        the NEXT lr_validate / fm_validate's R rows; None: that validate appends nothing"""
+        check(lib().xf_workspace_gauc_ids(self.h, d_id, int(R)))
+
     def fetch(self, U, R):
         wu = np.empty(U, np.float32)
         loss = np.empty(R, np.float32)
@@ -2223,6 +2372,28 @@ class Sharded:
         check(lib().xf_sharded_holdout_read(self.h, _p(counts, u64p), _p(other, u64p),
                                             1 if reset else 0, 1 if merged else 0))
         return counts, other
+
+    def set_gauc(self, enable):
+        """the grouped AUC of the held rows (xf_sharded_gauc): validate() appends the records of
+        minibatches that carry ids (batch_slices); needs set_holdout(True)"""
+        check(lib().xf_sharded_gauc(self.h, 1 if enable else 0))
+
+    def gauc_read(self, reset=False, merged=False, cap=None):
+        """(ids ascending, figures [n, 4] = P, N, U2, T, none [2], other [2]) of this rank's
+        records; merged=True: COLLECTIVE, every rank's records reduced on rank 0 (the others get
+        n = 0)"""
+        n = C.c_uint64()
+        if cap is None:
+            check(lib().xf_sharded_gauc_read(self.h, None, 0, C.byref(n), None, None, 0,
+                                             1 if merged else 0))
+            cap = n.value
+        cap = max(int(cap), 1)
+        entries = np.zeros((cap, GAUC_WORDS + 1), np.uint64)
+        none, other = np.zeros(2, np.uint64), np.zeros(2, np.uint64)
+        check(lib().xf_sharded_gauc_read(self.h, _p(entries, u64p), cap, C.byref(n),
+                                         _p(none, u64p), _p(other, u64p), 1 if reset else 0,
+                                         1 if merged else 0))
+        return _gauc_result(entries, n.value, none, other)
 
     def set_slices(self, enable, field=0, log2_slots=16):
         """sliced progressive validation on the trainer's training steps (xf_sharded_slices);

@@ -36,6 +36,7 @@
 #include "xf_negsample.h"
 #include "xf_progress.h"
 #include "xf_slices.h"
+#include "xf_gauc.h"
 #include "xf_scratch.h"
 #include "xf_wave.h"
 
@@ -1615,6 +1616,12 @@ struct xf_workspace {
   xf_slices *slices = nullptr;
   const uint64_t *slice_ids = nullptr;
   uint32_t slice_R = 0;
+  // grouped AUC on the held-out rows (xf_workspace_gauc; null: off) and the group ids of the next
+  // VALIDATE's rows (xf_workspace_gauc_ids; null: that validate appends nothing): score_out
+  // appends right after the progress and forgets the ids.  No training step and no predict reads it
+  xf_gauc *gauc = nullptr;
+  const uint64_t *gauc_ids = nullptr;
+  uint32_t gauc_R = 0;
   // the cells lr_step last ran over (compared, never dereferenced): a minibatch stepped twice in
   // a row has its entries where the step before left them, and nothing is fetched for it
   const xf_cells *last_cells = nullptr;
@@ -1883,6 +1890,23 @@ extern "C" int xf_workspace_slice_ids(xf_workspace *ws, const uint64_t *d_id, ui
   return XF_OK;
 }
 
+extern "C" int xf_workspace_gauc(xf_workspace *ws, xf_gauc *g) {
+  XF_REQUIRE(ws, "xf_workspace_gauc: null workspace");
+  ws->gauc = g;
+  ws->gauc_ids = nullptr;
+  return XF_OK;
+}
+
+extern "C" int xf_workspace_gauc_ids(xf_workspace *ws, const uint64_t *d_id, uint32_t R) {
+  XF_REQUIRE(ws, "xf_workspace_gauc_ids: null workspace");
+  XF_REQUIRE(!d_id || ws->gauc,
+             "xf_workspace_gauc_ids: group ids need a grouped-AUC object attached "
+             "(xf_workspace_gauc)");
+  ws->gauc_ids = d_id;
+  ws->gauc_R = d_id ? R : 0;
+  return XF_OK;
+}
+
 // between a training step's forward and whatever reads its losses: progressive validation counts
 // them as the forward left them, then the negatives take their weight (no launch for either when
 // nothing is attached and the weight is 1)
@@ -1909,7 +1933,18 @@ static float ws_finalize_weight(const xf_workspace *ws) {
 // — one launch, no wait (xf_lr_validate, xf_fm_validate)
 static int score_out(xf_workspace *ws, const int32_t *labels, uint32_t R, float *pctr_out,
                      xf_progress *tap) {
-  if (tap) return xf::progress_accumulate(tap, ws->loss, labels, R, nullptr);
+  if (tap) {
+    XF_TRY(xf::progress_accumulate(tap, ws->loss, labels, R, nullptr));
+    if (ws->gauc && ws->gauc_ids) {
+      const uint64_t *ids = ws->gauc_ids;
+      ws->gauc_ids = nullptr;  // (they name this validate's rows only)
+      XF_REQUIRE(ws->gauc_R == R,
+                 "a validate of %u rows with the group ids of %u rows (xf_workspace_gauc_ids)", R,
+                 ws->gauc_R);
+      XF_TRY(xf::gauc_append(ws->gauc, ws->loss, labels, ids, R, nullptr));
+    }
+    return XF_OK;
+  }
   if (R) XF_HIP(hipMemcpy(pctr_out, ws->pctr, (size_t)R * 4, hipMemcpyDeviceToHost));
   return XF_OK;
 }
@@ -2836,7 +2871,9 @@ extern "C" int xf_lr_predict(xf_table *w, xf_batch *b, xf_workspace *ws, float *
 
 extern "C" int xf_lr_validate(xf_table *w, xf_batch *b, xf_workspace *ws, xf_progress *p) {
   XF_REQUIRE(w && b && ws && p, "xf_lr_validate: null argument");
-  return lr_score(w, b, ws, nullptr, p);
+  const int rc = lr_score(w, b, ws, nullptr, p);
+  ws->gauc_ids = nullptr;  // (also when nothing was scored)
+  return rc;
 }
 
 static int fm_score(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws, float *pctr_out,
@@ -2897,7 +2934,9 @@ extern "C" int xf_fm_predict(xf_table *w, xf_table *vt, xf_batch *b, xf_workspac
 extern "C" int xf_fm_validate(xf_table *w, xf_table *vt, xf_batch *b, xf_workspace *ws,
                               xf_progress *p) {
   XF_REQUIRE(w && vt && b && ws && p, "xf_fm_validate: null argument");
-  return fm_score(w, vt, b, ws, nullptr, p);
+  const int rc = fm_score(w, vt, b, ws, nullptr, p);
+  ws->gauc_ids = nullptr;  // (also when nothing was scored)
+  return rc;
 }
 
 // parity hook: intermediates of the last step

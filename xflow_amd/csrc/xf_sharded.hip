@@ -54,6 +54,7 @@
 #include "xf_negsample.h"
 #include "xf_progress.h"
 #include "xf_slices.h"
+#include "xf_gauc.h"
 #include "xf_scratch.h"
 
 namespace xf {
@@ -241,6 +242,7 @@ struct xf_sharded {
   xf_progress *progress = nullptr;         // progressive validation (xf_sharded_progress); null: off
   xf_progress *holdout = nullptr;          // held-out validation (xf_sharded_holdout); null: off
   xf_slices *slices = nullptr;             // its slices (xf_sharded_slices); null: off
+  xf_gauc *gauc = nullptr;                 // grouped AUC of the held rows (xf_sharded_gauc); null: off
   uint64_t seen_upper = 0;     // world 1: host-side upper bound on the keys in the table
   Dev<double> partial;         // LR forward scratch
   // the owner-compute compile's staging: the worker's nonzeros grouped by owner (sent from
@@ -1428,6 +1430,7 @@ extern "C" int xf_sharded_destroy(xf_sharded *st) {
   if (st->progress) xf_progress_destroy(st->progress);
   if (st->holdout) xf_progress_destroy(st->holdout);
   if (st->slices) xf_slices_destroy(st->slices);
+  if (st->gauc) xf_gauc_destroy(st->gauc);
   if (st->tw) xf_table_destroy(st->tw);
   if (st->tv) xf_table_destroy(st->tv);
   if (st->main) (void)hipStreamDestroy(st->main);
@@ -1980,6 +1983,8 @@ extern "C" int xf_sharded_validate(xf_sharded *st, xf_sbatch *b) {
   XF_REQUIRE(st->holdout, "xf_sharded_validate: held-out validation is off (xf_sharded_holdout)");
   if (st->fused) {
     XF_TRY(wait_stream(st, st->main));
+    if (st->gauc)  // (the ids of this validate's rows, or none: the workspace forgets them after it)
+      XF_TRY(xf_workspace_gauc_ids(st->ws, b->has_slices ? b->slice_ids.p : nullptr, b->R));
     if (st->cfg.model == 0) return xf_lr_validate(st->tw, b->b, st->ws, st->holdout);
     return xf_fm_validate(st->tw, st->tv, b->b, st->ws, st->holdout);
   }
@@ -1996,6 +2001,8 @@ extern "C" int xf_sharded_validate(xf_sharded *st, xf_sbatch *b) {
   XF_TRY(front_pull(st, b, B, st->main));
   XF_TRY(front_compute(st, b, B, pctr.p, false, st->main));
   XF_TRY(xf::progress_accumulate(st->holdout, B.loss.p, b->b->view.labels, b->R, st->main));
+  if (st->gauc && b->has_slices)  // (a minibatch without ids leaves no record)
+    XF_TRY(xf::gauc_append(st->gauc, B.loss.p, b->b->view.labels, b->slice_ids.p, b->R, st->main));
   return wait_stream(st, st->main);  // (predict's wait: pctr goes out of scope)
 }
 
@@ -2195,6 +2202,8 @@ extern "C" int xf_sharded_holdout(xf_sharded *st, int enable) {
   if (enable && !st->holdout) {
     XF_TRY(xf_progress_create(&st->holdout));
   } else if (!enable && st->holdout) {
+    XF_REQUIRE(!st->gauc, "xf_sharded_holdout: the grouped AUC of the held rows is on "
+               "(xf_sharded_gauc): switch that off first");
     XF_TRY(xf_sharded_flush(st));
     xf_progress_destroy(st->holdout);
     st->holdout = nullptr;
@@ -2228,6 +2237,97 @@ extern "C" int xf_sharded_holdout_read(xf_sharded *st, uint64_t *counts, uint64_
   XF_REQUIRE(st->holdout, "xf_sharded_holdout_read: held-out validation is off "
              "(xf_sharded_holdout)");
   return read_counts(st, st->holdout, counts, other, reset, merged);
+}
+
+// grouped AUC of the held rows: beside the holdout's progress, tapped by xf_sharded_validate alone
+extern "C" int xf_sharded_gauc(xf_sharded *st, int enable) {
+  XF_REQUIRE(st, "xf_sharded_gauc: null trainer");
+  XF_ALIVE(st);
+  if (enable) {
+    XF_REQUIRE(st->fused || !owner_dataflow(st->cfg.schedule),
+               "xf_sharded_gauc: the grouped AUC of the held rows on schedule %s: the owners' "
+               "finalize kernels form the loss where no tap reads it (use schedule sequential or "
+               "stale1)", schedule_name(st->cfg.schedule));
+    XF_REQUIRE(st->holdout, "xf_sharded_gauc: the grouped AUC needs held-out validation on "
+               "(xf_sharded_holdout): the records are appended where it taps the losses");
+    if (!st->gauc) XF_TRY(xf_gauc_create(&st->gauc));
+  } else if (st->gauc) {
+    XF_TRY(xf_sharded_flush(st));
+    if (st->fused) XF_TRY(xf_workspace_gauc(st->ws, nullptr));
+    xf_gauc_destroy(st->gauc);
+    st->gauc = nullptr;
+  }
+  if (st->fused) XF_TRY(xf_workspace_gauc(st->ws, st->gauc));
+  return XF_OK;
+}
+
+extern "C" int xf_sharded_gauc_read(xf_sharded *st, uint64_t *entries, uint64_t cap, uint64_t *n,
+                                    uint64_t *none, uint64_t *other, int reset, int merged) {
+  XF_REQUIRE(st && n, "xf_sharded_gauc_read: null argument");
+  XF_REQUIRE(st->gauc, "xf_sharded_gauc_read: the grouped AUC of the held rows is off "
+             "(xf_sharded_gauc)");
+  XF_TRY(xf_sharded_flush(st));
+  if (!merged || !st->g || st->world <= 1)
+    return xf_gauc_reduce(st->gauc, entries, cap, n, none, other, reset);
+  XF_REQUIRE(entries || !reset,
+             "xf_sharded_gauc_read: a read without entries only counts them and cannot reset");
+  // COLLECTIVE: every rank's records (and its none / other) to rank 0, reduced there in a scratch
+  // object — a group's rows are spread over the ranks, so the figures of parts cannot be merged
+  uint64_t mine_n = 0;
+  XF_TRY(xf_gauc_export(st->gauc, nullptr, nullptr, 0, &mine_n));
+  // a rank's message: none[2], other[2], the ids, the codes (padded to whole 64-bit words)
+  const size_t code_words = ((size_t)mine_n + 1) / 2, words = 4 + (size_t)mine_n + code_words;
+  std::vector<uint64_t> mine(words, 0);
+  uint64_t got = 0, groups = 0;
+  XF_TRY(xf_gauc_reduce(st->gauc, nullptr, 0, &groups, mine.data(), mine.data() + 2, 0));
+  XF_TRY(xf_gauc_export(st->gauc, mine.data() + 4, (uint32_t *)(mine.data() + 4 + mine_n), mine_n,
+                        &got));
+  XF_REQUIRE(got == mine_n, "xf_sharded_gauc_read: the log changed between two reads");
+  std::vector<uint64_t> counts((size_t)st->world), sizes((size_t)st->world);
+  XF_TRY(xf_group_allgather_host(st->g, &mine_n, 8, counts.data()));
+  size_t all_words = 0;
+  for (int r = 0; r < st->world; ++r) {
+    sizes[(size_t)r] = (4 + counts[(size_t)r] + (counts[(size_t)r] + 1) / 2) * 8;
+    all_words += (size_t)sizes[(size_t)r] / 8;
+  }
+  std::vector<uint64_t> all(st->rank == 0 ? all_words : 1);
+  XF_TRY(xf_group_gatherv_host(st->g, mine.data(), words * 8, all.data(), sizes.data()));
+  int32_t rc = XF_OK;
+  std::string msg;
+  uint64_t sum_none[2] = {0, 0}, sum_other[2] = {0, 0}, out_n = 0;
+  if (st->rank == 0) {
+    xf_gauc *scratch = nullptr;
+    rc = xf_gauc_create(&scratch);
+    size_t at = 0;
+    for (int r = 0; r < st->world && rc == XF_OK; ++r) {
+      const uint64_t *m = all.data() + at, c = counts[(size_t)r];
+      for (int q = 0; q < 2; ++q) {
+        sum_none[q] += m[q];
+        sum_other[q] += m[2 + q];
+      }
+      rc = xf_gauc_append(scratch, m + 4, (const uint32_t *)(m + 4 + c), c);
+      at += (size_t)sizes[(size_t)r] / 8;
+    }
+    if (rc == XF_OK) rc = xf_gauc_reduce(scratch, entries, cap, &out_n, nullptr, nullptr, 0);
+    if (rc != XF_OK) msg = xf_last_error();
+    xf_gauc_destroy(scratch);
+  }
+  // a refusal on rank 0 (entries that do not fit) is one on every rank, and nothing is reset
+  std::vector<int32_t> rcs((size_t)st->world);
+  XF_TRY(xf_group_allgather_host(st->g, &rc, 4, rcs.data()));
+  if (rcs[0] != XF_OK)
+    return xf::set_error(rcs[0], "xf_sharded_gauc_read: %s",
+                         st->rank == 0 ? msg.c_str() : "rank 0 could not reduce the merged records");
+  *n = out_n;
+  for (int q = 0; q < 2; ++q) {
+    if (none) none[q] = sum_none[q];
+    if (other) other[q] = sum_other[q];
+  }
+  if (reset) {
+    std::vector<uint64_t> drop((size_t)std::max<uint64_t>(groups, 1) * (XF_GAUC_WORDS + 1));
+    XF_TRY(xf_gauc_reduce(st->gauc, drop.data(), groups, &got, nullptr, nullptr, 1));
+  }
+  return XF_OK;
 }
 
 // sliced progressive validation: beside the progress, tapped at the same two places

@@ -59,6 +59,7 @@ Worker::~Worker() {
   if (cross_) xf_cross_destroy(cross_);
   if (norm_) xf_rownorm_destroy(norm_);
   if (slicer_) xf_slices_destroy(slicer_);
+  if (gslicer_) xf_slices_destroy(gslicer_);
   if (sharded_) xf_sharded_destroy(sharded_);  // owns the tables
   if (group_) xf_group_destroy(group_);
 }
@@ -487,11 +488,77 @@ int Worker::check_holdout() const {
   return XF_OK;
 }
 
+// The grouped AUC names the held part's rows on the GPU from the nonzeros' field ids, as sliced
+// progressive validation names the training rows: the same requirements, and held-out validation
+// on.  All refused by name, before any rendezvous.
+int Worker::check_gauc() const {
+  if (!holdout_by_set) return XF_OK;
+  XF_REQUIRE(holdout_by >= 0 && holdout_by <= 0x7fffffffll,
+             "XFStartTrain: holdout_by must be a field id in 0 .. 2147483647, not %lld", holdout_by);
+  XF_REQUIRE(holdout > 0.0f, "XFStartTrain: holdout_by=%lld without holdout: the groups are those "
+             "of the held-out rows (use holdout=r)", holdout_by);
+  XF_REQUIRE(!ingest_gpu, "XFStartTrain: holdout_by=%lld together with ingest=gpu: the GPU "
+             "tokeniser hands out no fgid (use ingest=gpu_fields)", holdout_by);
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: holdout_by=%lld needs core_num=1, not core_num=%d",
+             holdout_by, core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: holdout_by=%lld together with key_build=host: the "
+             "rows are named on the GPU (use key_build=gpu)", holdout_by);
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: holdout_by=%lld together with "
+             "parity=reference_order: that mode builds its keys on the host", holdout_by);
+  return XF_OK;
+}
+
+// after the holdout line of a validated epoch: the held rows' records reduced — on several ranks
+// merged on rank 0 — and reset, the summary to every rank (the metrics), rank 0 prints
+int Worker::gauc_epoch(int epoch) {
+  if (!gslicer_) return XF_OK;
+  constexpr size_t E = XF_GAUC_WORDS + 1;
+  const int merged = world > 1;
+  uint64_t n = 0, none[2] = {0, 0}, other[2] = {0, 0};
+  XF_TRY(xf_sharded_gauc_read(sharded_, nullptr, 0, &n, nullptr, nullptr, 0, merged));
+  std::vector<uint64_t> entries(std::max<uint64_t>(n, 1) * E);
+  XF_TRY(xf_sharded_gauc_read(sharded_, entries.data(), std::max<uint64_t>(n, 1), &n, none, other,
+                              1, merged));
+  std::vector<double> auc((size_t)n + 1), slack((size_t)n + 1);
+  xf_gauc_metrics m;
+  XF_TRY(xf_gauc_summary(entries.data(), n, none, other, &m, auc.data(), slack.data()));
+  if (merged) {  // (rank 0 reduced: its summary is everybody's)
+    std::vector<xf_gauc_metrics> all((size_t)world);
+    XF_TRY(xf_group_allgather_host(group_, &m, sizeof(m), all.data()));
+    m = all[0];
+  }
+  gauc_last_ = m;
+  gauc_have_ = true;
+  if (rank != 0) return XF_OK;
+  printf("holdout groups epoch %d: field = %lld groups = %llu scored = %llu rows = %llu "
+         "scored_rows = %llu none_rows = %llu gauc = %.6f (+- %.1e) macro_auc = %.6f",
+         epoch, holdout_by, (unsigned long long)m.groups, (unsigned long long)m.groups_scored,
+         (unsigned long long)m.rows, (unsigned long long)m.rows_scored,
+         (unsigned long long)m.none_rows, m.gauc, m.gauc_slack, m.macro_auc);
+  if (m.other_rows) printf(" other_rows = %llu", (unsigned long long)m.other_rows);
+  printf("\n");
+  fflush(stdout);
+  if (!holdout_groups_out.empty()) {  // one line per group, by key
+    FILE *f = fopen(holdout_groups_out.c_str(), "a");
+    XF_REQUIRE(f, "holdout_groups_out: cannot append to %s", holdout_groups_out.c_str());
+    for (size_t i = 0; i < (size_t)n; ++i)
+      fprintf(f, "%d\t0x%016llx\t%llu\t%llu\t%.17g\t%.17g\n", epoch,
+              (unsigned long long)entries[i * E], (unsigned long long)entries[i * E + 1],
+              (unsigned long long)entries[i * E + 2], auc[i], slack[i]);
+    fclose(f);
+  }
+  return XF_OK;
+}
+
 int Worker::create_holdout() {
   XF_TRY(check_holdout());
   if (holdout == 0.0f || split_) return XF_OK;
   XF_TRY(xf_holdout_create(&split_, holdout, seed));
   XF_TRY(xf_sharded_holdout(sharded_, 1));
+  if (holdout_by_set) {
+    XF_TRY(xf_slices_create(&gslicer_, (int32_t)holdout_by, xf::kSlicesMinLog2));
+    XF_TRY(xf_sharded_gauc(sharded_, 1));
+  }
   // the split's first launches, on two rows of a private object: start-up work like the two-row
   // update of create_tables (the worker's own object keeps its statistics clean)
   xf_holdout *warm = nullptr;
@@ -520,8 +587,18 @@ int Worker::keep_held(const xf_holdout_part &held) {
   if (!held.d_rowptr && !admit_) {  // (a turn without rows of this rank's own)
     XF_TRY(compile_no_rows(sharded_, &hb, 1));
   } else {
+    // (the rows' groups, named as the split hands them over: neither the cross nor admission adds
+    // or removes rows, so the ids fit the minibatch compiled below)
+    const uint64_t *ids = nullptr;
+    if (gslicer_ && held.R && held.d_rowptr) {
+      void *stream = nullptr;
+      XF_TRY(xf_sharded_stream(sharded_, &stream));
+      XF_TRY(xf_slices_extract_dev(gslicer_, held.d_keys, held.d_fgid, held.d_rowptr, held.R,
+                                   held.NNZ, stream, &ids));
+    }
     XF_TRY(compile_staged_dev(&hb, 0, held.d_keys, held.d_fgid, held.d_vals, held.d_rowptr,
                               held.d_labels, held.R, held.NNZ, 1));
+    if (ids && hb) XF_TRY(xf_sbatch_set_slices(hb, ids, held.R));
   }
   if (hb) held_.push_back(hb);
   return XF_OK;
@@ -534,7 +611,8 @@ int Worker::split_dev(size_t first_row, const uint64_t **d_keys, const int32_t *
   XF_TRY(xf_sharded_stream(sharded_, &stream));
   xf_holdout_part tr, he;
   XF_TRY(xf_holdout_split_dev(split_, (uint64_t)(uint32_t)rank, ordinal_ + first_row, *d_keys,
-                              fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? *d_fgid : nullptr,
+                              fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ || gslicer_
+                                  ? *d_fgid : nullptr,
                               feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
                               stream, &tr, &he));
   pending_held_ = he;  // (the caller compiles the train part, then keep_held(pending_held_))
@@ -559,7 +637,8 @@ int Worker::compile_split(xf_sbatch **b, const uint64_t *rowptr, const uint64_t 
   XF_TRY(xf_sharded_stream(sharded_, &stream));
   xf_holdout_part tr, he;
   XF_TRY(xf_holdout_split(split_, (uint64_t)(uint32_t)rank, ordinal_ + start, rowptr, keys,
-                          fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? fgid : nullptr,
+                          fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ || gslicer_ ? fgid
+                                                                                         : nullptr,
                           feature_values ? vals : nullptr, labels, start, end, stream, &tr, &he));
   train_block_first_ = train_ordinal_;
   train_ordinal_ += tr.R;
@@ -604,6 +683,7 @@ int Worker::holdout_epoch(int epoch, bool last, bool *stop) {
       snprintf(line + at, sizeof(line) - at, " other = %.17g", m.other);
     std::cout << line << std::endl;
   }
+  XF_TRY(gauc_epoch(epoch));
   int best = -1;
   const int s = xf_holdout_should_stop(holdout_curve_.data(), (int)holdout_curve_.size(),
                                        early_stop, early_stop_delta, &best);
@@ -948,7 +1028,8 @@ int Worker::compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr,
 // field-aware FM, the third field with feature values; neither: the tokeniser of ingest = gpu
 int Worker::set_ingest_fields(xf_ingest *g) {
   return xf_ingest_set_fields(g, ingest_fields && (fm_mode == XF_FM_FIELD_AWARE ||
-                                                   !cross_spec.empty() || progress_by_set),
+                                                   !cross_spec.empty() || progress_by_set ||
+                                                   holdout_by_set),
                               ingest_fields && feature_values);
 }
 
@@ -1599,6 +1680,8 @@ int Worker::train() {
   }
   XF_TRY(check_admit());  // before any rendezvous of a group
   XF_TRY(check_negsample());
+  XF_TRY(check_gauc());  // (ahead of the holdout's own: the refusals they share name holdout_by)
+  gauc_have_ = false;
   XF_TRY(check_holdout());
   XF_TRY(check_progress());
   progress_have_ = false;
@@ -1750,6 +1833,16 @@ int Worker::set_param(const char *name, const char *value) {
   } else if (n == "holdout") {
     XF_REQUIRE(!split_, "XFSetParam: holdout cannot change once the split stage exists");
     holdout = strtof(value, nullptr);
+  } else if (n == "holdout_by") {
+    XF_REQUIRE(!sharded_, "XFSetParam: holdout_by cannot change after training started");
+    char *end = nullptr;
+    const long long f = strtoll(value, &end, 10);
+    XF_REQUIRE(end != value && *end == '\0', "XFSetParam: holdout_by must be a field id, not '%s'",
+               value);
+    holdout_by = f;
+    holdout_by_set = true;
+  } else if (n == "holdout_groups_out") {
+    holdout_groups_out = value;
   } else if (n == "holdout_every") {
     holdout_every = atoi(value);
   } else if (n == "early_stop") {
@@ -1846,6 +1939,14 @@ int Worker::get_metric(const char *name, double *value) {
     *value = slices_last_[n == "slices" ? 0 : n == "slice_rows" ? 1 : n == "slice_none_rows" ? 2 : 3];
   } else if (n == "epochs_run") {
     *value = (double)epochs_run_;
+  } else if (n == "holdout_gauc" || n == "holdout_gauc_slack" || n == "holdout_macro_auc" ||
+             n == "holdout_groups" || n == "holdout_groups_scored" || n == "holdout_gauc_rows") {
+    XF_REQUIRE(gauc_have_, "XFGetMetric: %s: no epoch has been reduced (holdout_by=F, after a "
+               "validated epoch)", name);
+    const xf_gauc_metrics &m = gauc_last_;
+    *value = n == "holdout_gauc" ? m.gauc : n == "holdout_gauc_slack" ? m.gauc_slack
+             : n == "holdout_macro_auc" ? m.macro_auc : n == "holdout_groups" ? (double)m.groups
+             : n == "holdout_groups_scored" ? (double)m.groups_scored : (double)m.rows_scored;
   } else if (n.rfind("holdout_", 0) == 0) {
     XF_REQUIRE(!holdout_curve_.empty(), "XFGetMetric: %s: no epoch has been validated (holdout=r, "
                "after XFStartTrain)", name);

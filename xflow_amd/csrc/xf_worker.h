@@ -152,8 +152,25 @@ class Worker {
   int holdout_every = 1;
   int early_stop = 0;
   double early_stop_delta = 0.0;
+  // Grouped AUC on the held-out rows (xf_gauc.hip): holdout_by = F (with holdout > 0): the held
+  // part's rows are named by the key of their first nonzero of field F as the split hands it over —
+  // before the cross and admission, which neither add nor remove rows — and the ids stay with the
+  // held minibatch.  Every validated epoch appends the held rows' records; after the holdout line
+  // the records are reduced (merged on rank 0 over the ranks) and reset, rank 0 prints one line
+  // and appends a TSV line per group to holdout_groups_out.  The early-stop rule keeps reading the
+  // logloss.  core_num 1, key_build=gpu, not ingest=gpu (checked where training starts).  Nothing
+  // travels with the model.
+  bool holdout_by_set = false;
+  long long holdout_by = -1;
+  std::string holdout_groups_out;
 
  private:
+  int check_gauc() const;  // the refusals of holdout_by, before any rendezvous
+  int gauc_epoch(int epoch);  // COLLECTIVE at world > 1: reduce (merged), reset, summarise, print
+  // the stage that names the held rows' groups (its own table is never fed); created with the split
+  xf_slices *gslicer_ = nullptr;
+  xf_gauc_metrics gauc_last_{};
+  bool gauc_have_ = false;
   int check_holdout() const;  // the refusals of holdout / early_stop, before any rendezvous
   int create_holdout();
   // COLLECTIVE at world > 1: validate the held list, read, merge, reset, summarise, print; *stop:
