@@ -444,19 +444,6 @@ int Worker::create_negsample() {
   return rc;
 }
 
-int Worker::sample_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
-                       const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
-                       uint32_t *R, uint32_t *NNZ) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  // (with holdout on the sampler numbers the rows of the TRAIN part: split_dev's running count)
-  return xf_negsample_apply_dev(sample_, sample_stream_,
-                                split_ ? train_block_first_ : ordinal_ + first_row, *d_keys,
-                                fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? *d_fgid : nullptr,
-                                feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
-                                stream, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ);
-}
-
 // Held-out validation splits a training block on the GPU ahead of every other stage: core_num > 1
 // slices a block after it was read (a row would have no file-wide index), the host key build and
 // the reference-order forward take host arrays, and on several workers the owner-compute schedules
@@ -581,75 +568,33 @@ int Worker::create_holdout() {
 // looks at the held ones (on a file of one block: the filter the test file will meet).  Only while
 // the first epoch runs: an epoch that reads the text again drops it.  Without rows: no minibatch
 // on one worker, the empty minibatch in a group.
-int Worker::keep_held(const xf_holdout_part &held) {
+int Worker::keep_held(const DevRows &held) {
   if (held_complete_ || (held.R == 0 && world <= 1)) return XF_OK;
   xf_sbatch *hb = nullptr;
-  if (!held.d_rowptr && !admit_) {  // (a turn without rows of this rank's own)
+  if (!held.rowptr && !admit_) {  // (a turn without rows of this rank's own)
     XF_TRY(compile_no_rows(sharded_, &hb, 1));
   } else {
     // (the rows' groups, named as the split hands them over: neither the cross nor admission adds
     // or removes rows, so the ids fit the minibatch compiled below)
     const uint64_t *ids = nullptr;
-    if (gslicer_ && held.R && held.d_rowptr) {
+    if (gslicer_ && held.R && held.rowptr) {
       void *stream = nullptr;
       XF_TRY(xf_sharded_stream(sharded_, &stream));
-      XF_TRY(xf_slices_extract_dev(gslicer_, held.d_keys, held.d_fgid, held.d_rowptr, held.R,
-                                   held.NNZ, stream, &ids));
+      XF_TRY(xf_slices_extract_dev(gslicer_, held.keys, held.fgid, held.rowptr, held.R, held.NNZ,
+                                   stream, &ids));
     }
-    XF_TRY(compile_staged_dev(&hb, 0, held.d_keys, held.d_fgid, held.d_vals, held.d_rowptr,
-                              held.d_labels, held.R, held.NNZ, 1));
+    XF_TRY(stage_rows(&hb, 0, held, kCross, 1));
     if (ids && hb) XF_TRY(xf_sbatch_set_slices(hb, ids, held.R));
   }
   if (hb) held_.push_back(hb);
   return XF_OK;
 }
 
-int Worker::split_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
-                      const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
-                      uint32_t *R, uint32_t *NNZ) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  xf_holdout_part tr, he;
-  XF_TRY(xf_holdout_split_dev(split_, (uint64_t)(uint32_t)rank, ordinal_ + first_row, *d_keys,
-                              fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ || gslicer_
-                                  ? *d_fgid : nullptr,
-                              feature_values ? *d_vals : nullptr, *d_rowptr, *d_labels, *R, *NNZ,
-                              stream, &tr, &he));
-  pending_held_ = he;  // (the caller compiles the train part, then keep_held(pending_held_))
+// the split's train part: its rows are numbered on from the train parts of the blocks before it
+Worker::DevRows Worker::count_train(const xf_holdout_part &train) {
   train_block_first_ = train_ordinal_;
-  train_ordinal_ += tr.R;
-  *d_keys = tr.d_keys;
-  *d_fgid = tr.d_fgid;
-  *d_vals = tr.d_vals;
-  *d_rowptr = tr.d_rowptr;
-  *d_labels = tr.d_labels;
-  *R = tr.R;
-  *NNZ = tr.NNZ;
-  return XF_OK;
-}
-
-// rows [start, end) of host arrays: uploaded by the split; the train part then takes the stages a
-// sampled block takes (a train part without rows is a block without rows)
-int Worker::compile_split(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                          const int32_t *fgid, const float *vals, const int32_t *labels,
-                          size_t start, size_t end, int keep) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  xf_holdout_part tr, he;
-  XF_TRY(xf_holdout_split(split_, (uint64_t)(uint32_t)rank, ordinal_ + start, rowptr, keys,
-                          fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ || gslicer_ ? fgid
-                                                                                         : nullptr,
-                          feature_values ? vals : nullptr, labels, start, end, stream, &tr, &he));
-  train_block_first_ = train_ordinal_;
-  train_ordinal_ += tr.R;
-  const uint64_t *dk = tr.d_keys;
-  const int32_t *dfg = tr.d_fgid, *dl = tr.d_labels;
-  const float *dv = tr.d_vals;
-  const uint32_t *drp = tr.d_rowptr;
-  uint32_t R = tr.R, NNZ = tr.NNZ;
-  if (sample_) XF_TRY(sample_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ));
-  XF_TRY(compile_sampled_dev(b, dk, dfg, dv, drp, dl, R, NNZ, keep));
-  return keep_held(he);
+  train_ordinal_ += train.R;
+  return dev_rows(train);
 }
 
 // the end of an epoch, after the flush and before table maintenance: every holdout_every-th epoch
@@ -697,14 +642,6 @@ int Worker::holdout_epoch(int epoch, bool last, bool *stop) {
     }
   }
   return XF_OK;
-}
-
-int Worker::compile_sampled_dev(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
-                                const float *d_vals, const uint32_t *d_rowptr,
-                                const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
-  *b = nullptr;
-  if (R == 0 && world <= 1) return XF_OK;  // (every row dropped: a block without rows)
-  return compile_staged_dev(b, 1, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
 }
 
 // Feature crosses add nonzeros to a block on the GPU ahead of the key build, from the nonzeros'
@@ -802,91 +739,77 @@ int Worker::create_rownorm() {
   return rc;
 }
 
-// rows [start, end) of host arrays through row normalisation alone: uploaded by the stage, then
-// the _dev compile of the worker's mode
-int Worker::compile_normed(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                           const int32_t *fgid, const float *vals, const int32_t *labels,
-                           size_t start, size_t end, int keep) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  const uint64_t *fk = nullptr;
-  const int32_t *ff = nullptr, *fl = nullptr;
-  const float *fv = nullptr;
-  const uint32_t *fr = nullptr;
-  uint32_t R = 0, NNZ = 0;
-  XF_TRY(xf_rownorm_apply(norm_, rowptr, keys, fm_mode == XF_FM_FIELD_AWARE ? fgid : nullptr, vals,
-                          labels, start, end, stream, &fk, &ff, &fv, &fr, &fl, &R, &NNZ, nullptr));
-  return compile_dev_mode(b, fk, ff, fv, fr, fl, R, NNZ, keep);
+// Field-aware FM reads a nonzero's fgid, so there every stage carries it.  Otherwise it is carried
+// only as far as a stage that reads it: the slices and the cross sit behind the sampler, so the
+// split and the sampler carry it for them; the held rows' groups are named as the split hands the
+// held part over, so for them the split alone does — the sampler sees training rows only.
+bool Worker::carries_fgid(Stage s) const {
+  return fm_mode == XF_FM_FIELD_AWARE || (s <= kSample && (cross_ || slicer_)) ||
+         (s == kSplit && gslicer_);
 }
 
-// the stages that follow sampling, on device arrays: the cross, when on (a block without rows has
-// nothing to cross), admission, when on, and the _dev compile of the worker's mode
-int Worker::compile_staged_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
-                               const int32_t *d_fgid, const float *d_vals,
-                               const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
-                               uint32_t NNZ, int keep) {
-  // (training blocks only: the rows' slices, named before the cross adds its nonzeros; neither
-  // the cross nor admission drops or reorders rows, so the ids fit the minibatch compiled below)
-  const uint64_t *ids = nullptr;
-  const uint32_t id_rows = R;
-  if (slicer_ && update && R) {
-    void *stream = nullptr;
-    XF_TRY(xf_sharded_stream(sharded_, &stream));
-    XF_TRY(xf_slices_extract_dev(slicer_, d_keys, d_fgid, d_rowptr, R, NNZ, stream, &ids));
+// The stage order, on device arrays.  `from` is the first stage still to run: a caller whose first
+// stage took the host arrays enters below it.  update: a training block — the split, the sampler
+// and the slices run on those only, and admission counts.  Neither the cross nor admission drops
+// or reorders rows, so the slice ids named ahead of them fit the minibatch.
+int Worker::stage_rows(xf_sbatch **b, int update, DevRows rows, Stage from, int keep) {
+  *b = nullptr;
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const bool split = from <= kSplit && update && split_;
+  DevRows held{};
+  if (split) {
+    xf_holdout_part tr, he;
+    XF_TRY(xf_holdout_split_dev(split_, (uint64_t)(uint32_t)rank, ordinal_, rows.keys,
+                                carries_fgid(kSplit) ? rows.fgid : nullptr,
+                                feature_values ? rows.vals : nullptr, rows.rowptr, rows.labels,
+                                rows.R, rows.NNZ, stream, &tr, &he));
+    rows = count_train(tr);
+    held = dev_rows(he);
   }
-  if (cross_ && R) {
-    void *stream = nullptr;
-    XF_TRY(xf_sharded_stream(sharded_, &stream));
-    const int32_t *ff = nullptr;
-    const float *fv = nullptr;
-    XF_TRY(xf_cross_apply_dev(cross_, d_keys, d_fgid, feature_values ? d_vals : nullptr, d_rowptr,
-                              R, NNZ, stream, fm_mode == XF_FM_FIELD_AWARE, &d_keys, &ff, &fv,
-                              &d_rowptr, &NNZ));
-    d_fgid = ff;
-    d_vals = fv;
+  // (under the split the sampler numbers the rows of the TRAIN part: count_train's running count)
+  if (from <= kSample && update && sample_)
+    XF_TRY(xf_negsample_apply_dev(sample_, sample_stream_, split_ ? train_block_first_ : ordinal_,
+                                  rows.keys, carries_fgid(kSample) ? rows.fgid : nullptr,
+                                  feature_values ? rows.vals : nullptr, rows.rowptr, rows.labels,
+                                  rows.R, rows.NNZ, stream, &rows.keys, &rows.fgid, &rows.vals,
+                                  &rows.rowptr, &rows.labels, &rows.R, &rows.NNZ));
+  // a block that the split or the sampler left without rows is a block without rows: no minibatch
+  // on one worker, the empty minibatch in a group
+  const bool gone = from <= kSlices && update && (split_ || sample_) && rows.R == 0 && world <= 1;
+  if (!gone) {
+    const uint64_t *ids = nullptr;
+    const uint32_t id_rows = rows.R;
+    if (from <= kSlices && update && slicer_ && rows.R)
+      XF_TRY(xf_slices_extract_dev(slicer_, rows.keys, rows.fgid, rows.rowptr, rows.R, rows.NNZ,
+                                   stream, &ids));
+    if (from <= kCross && cross_ && rows.R) {  // (a block without rows has nothing to cross)
+      const int32_t *ff = nullptr;
+      const float *fv = nullptr;
+      XF_TRY(xf_cross_apply_dev(cross_, rows.keys, rows.fgid, feature_values ? rows.vals : nullptr,
+                                rows.rowptr, rows.R, rows.NNZ, stream, carries_fgid(kCross),
+                                &rows.keys, &ff, &fv, &rows.rowptr, &rows.NNZ));
+      rows.fgid = ff;
+      rows.vals = fv;
+    }
+    if (from <= kAdmit && admit_) {  // (without rows too: a shared filter's apply is collective)
+      const int32_t *ff = nullptr;
+      const float *fv = nullptr;
+      XF_TRY(xf_admit_apply_dev(admit_, update, rows.keys,
+                                carries_fgid(kAdmit) ? rows.fgid : nullptr,
+                                feature_values ? rows.vals : nullptr, rows.rowptr, rows.R, rows.NNZ,
+                                stream, &rows.keys, &ff, &fv, &rows.rowptr, &rows.NNZ));
+      rows.fgid = ff;
+      rows.vals = fv;
+    }
+    if (from <= kNorm && norm_ && rows.R)
+      XF_TRY(xf_rownorm_apply_dev(norm_, rows.vals, rows.rowptr, rows.R, rows.NNZ, stream,
+                                  &rows.vals, nullptr));
+    XF_TRY(compile_dev_mode(b, rows, keep));
+    if (ids && *b) XF_TRY(xf_sbatch_set_slices(*b, ids, id_rows));
   }
-  if (admit_)
-    XF_TRY(compile_admitted_dev(b, update, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ,
-                                keep));
-  else
-    XF_TRY(compile_dev_arrays(b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep));
-  if (ids && *b) XF_TRY(xf_sbatch_set_slices(*b, ids, id_rows));
-  return XF_OK;
-}
-
-// rows [start, end) of host arrays through the cross: uploaded by the stage, then as above
-int Worker::compile_crossed(xf_sbatch **b, int update, const uint64_t *rowptr,
-                            const uint64_t *keys, const int32_t *fgid, const float *vals,
-                            const int32_t *labels, size_t start, size_t end, int keep) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  const uint64_t *fk = nullptr;
-  const int32_t *ff = nullptr, *fl = nullptr;
-  const float *fv = nullptr;
-  const uint32_t *fr = nullptr;
-  uint32_t R = 0, NNZ = 0;
-  XF_TRY(xf_cross_apply(cross_, rowptr, keys, fgid, feature_values ? vals : nullptr, labels, start,
-                        end, stream, fm_mode == XF_FM_FIELD_AWARE, &fk, &ff, &fv, &fr, &fl, &R,
-                        &NNZ));
-  if (admit_) return compile_admitted_dev(b, update, fk, ff, fv, fr, fl, R, NNZ, keep);
-  return compile_dev_arrays(b, fk, ff, fv, fr, fl, R, NNZ, keep);
-}
-
-int Worker::compile_sampled(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                            const int32_t *fgid, const float *vals, const int32_t *labels,
-                            size_t start, size_t end, int keep) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  const uint64_t *fk = nullptr;
-  const int32_t *ff = nullptr, *fl = nullptr;
-  const float *fv = nullptr;
-  const uint32_t *fr = nullptr;
-  uint32_t R = 0, NNZ = 0;
-  XF_TRY(xf_negsample_apply(sample_, sample_stream_, ordinal_ + start, rowptr, keys,
-                            fm_mode == XF_FM_FIELD_AWARE || cross_ || slicer_ ? fgid : nullptr,
-                            feature_values ? vals : nullptr, labels, start, end, stream, &fk, &ff,
-                            &fv, &fr, &fl, &R, &NNZ));
-  return compile_sampled_dev(b, fk, ff, fv, fr, fl, R, NNZ, keep);
+  // (the held part AFTER the train part: the filter has counted the block's train rows by now)
+  return split ? keep_held(held) : XF_OK;
 }
 
 // a rank without rows of its own still takes part in the (collective) step: the empty minibatch
@@ -895,133 +818,85 @@ int Worker::compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep) {
   return xf_sharded_compile(trainer, b, kNoRows, nullptr, (const int32_t *)kNoRows, 0, 0, keep);
 }
 
-// the compile of the worker's mode on rows [start, end) of a block's host arrays (fgid and vals
-// are looked at only in the modes that read them); update: the admission filter counts the keys
+// The one host entry (fgid and vals are looked at only in the modes and stages that read them).
+// Each stage's host API is "upload the slice, then the stage on device arrays", so the rows go up
+// once, by the first stage that is on, and stage_rows runs what is left.  The stages are for rows
+// of this rank's own; the split, the sampler and the slices for training rows only.
 int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
                          const uint64_t *keys, const int32_t *fgid, const float *vals,
                          const int32_t *labels, size_t start, size_t end, int keep) {
-  // (sliced progressive validation: training rows of this rank's own.  Under negative subsampling
-  // the block is on the device when its rows are named — compile_staged_dev; otherwise here)
-  // (held-out validation: a training block of this rank's own is split first, on the device; in
-  // a group a turn without rows still adds the empty minibatch to the held list, so that every
-  // rank validates equally often)
-  if (split_ && update && trainer == sharded_) {
-    if (rowptr && end > start)
-      return compile_split(b, rowptr, keys, fgid, vals, labels, start, end, keep);
-    if (world > 1) {  // (the train part first, as compile_split does)
-      XF_TRY(compile_rows_unsliced(trainer, b, update, rowptr, keys, fgid, vals, labels, start, end,
-                                   keep));
-      return keep_held(xf_holdout_part{});
+  const bool own = trainer == sharded_, rows_here = own && rowptr && end > start;
+  const bool train = rows_here && update;
+  void *stream = nullptr;
+  if (own) XF_TRY(xf_sharded_stream(sharded_, &stream));
+  const float *v = feature_values ? vals : nullptr;
+  DevRows d{};
+  xf_holdout_part tr, he{};
+  const uint64_t *ids = nullptr;  // (the slices with neither split nor sampler in front: named
+  uint32_t id_rows = 0;           // from the stage's own upload, as a run with that stage alone)
+  Stage next = kCompile;
+  bool staged = true;
+  if (train && split_) {
+    XF_TRY(xf_holdout_split(split_, (uint64_t)(uint32_t)rank, ordinal_ + start, rowptr, keys,
+                            carries_fgid(kSplit) ? fgid : nullptr, v, labels, start, end, stream,
+                            &tr, &he));
+    d = count_train(tr);
+    next = kSample;
+  } else if (train && sample_) {
+    XF_TRY(xf_negsample_apply(sample_, sample_stream_, ordinal_ + start, rowptr, keys,
+                              carries_fgid(kSample) ? fgid : nullptr, v, labels, start, end, stream,
+                              &d.keys, &d.fgid, &d.vals, &d.rowptr, &d.labels, &d.R, &d.NNZ));
+    next = kSlices;
+  } else {
+    if (train && slicer_)
+      XF_TRY(xf_slices_extract(slicer_, rowptr, keys, fgid, start, end, stream, &ids, &id_rows));
+    if (rows_here && cross_) {
+      XF_TRY(xf_cross_apply(cross_, rowptr, keys, fgid, v, labels, start, end, stream,
+                            carries_fgid(kCross), &d.keys, &d.fgid, &d.vals, &d.rowptr, &d.labels,
+                            &d.R, &d.NNZ));
+      next = kAdmit;
+    } else if (own && admit_ && rowptr) {
+      XF_TRY(xf_admit_apply(admit_, update, rowptr, keys, carries_fgid(kAdmit) ? fgid : nullptr, v,
+                            labels, start, end, stream, &d.keys, &d.fgid, &d.vals, &d.rowptr,
+                            &d.labels, &d.R, &d.NNZ));
+      next = kNorm;
+    } else if (own && admit_) {
+      next = kAdmit;  // (a turn without rows under a shared filter: in the collective apply)
+    } else if (rows_here && norm_) {
+      XF_TRY(xf_rownorm_apply(norm_, rowptr, keys, carries_fgid(kNorm) ? fgid : nullptr, vals,
+                              labels, start, end, stream, &d.keys, &d.fgid, &d.vals, &d.rowptr,
+                              &d.labels, &d.R, &d.NNZ, nullptr));
+    } else {
+      staged = false;  // no stage takes these rows: the host compile of the worker's mode
+      if (fm_mode == XF_FM_FIELD_AWARE)
+        XF_TRY(xf_sharded_compile_fielded(trainer, b, rowptr, keys, fgid, v, labels, start, end,
+                                          keep));
+      else if (feature_values)
+        XF_TRY(xf_sharded_compile_valued(trainer, b, rowptr, keys, vals, labels, start, end, keep));
+      else if (end > start)
+        XF_TRY(xf_sharded_compile(trainer, b, rowptr, keys, labels, start, end, keep));
+      else
+        XF_TRY(compile_no_rows(trainer, b, keep));
     }
   }
-  if (slicer_ && !sample_ && update && trainer == sharded_ && rowptr && end > start)
-    return compile_sliced(b, rowptr, keys, fgid, vals, labels, start, end, keep);
-  return compile_rows_unsliced(trainer, b, update, rowptr, keys, fgid, vals, labels, start, end,
-                               keep);
-}
-
-int Worker::compile_sliced(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                           const int32_t *fgid, const float *vals, const int32_t *labels,
-                           size_t start, size_t end, int keep) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  const uint64_t *ids = nullptr;
-  uint32_t R = 0;
-  XF_TRY(xf_slices_extract(slicer_, rowptr, keys, fgid, start, end, stream, &ids, &R));
-  XF_TRY(compile_rows_unsliced(sharded_, b, 1, rowptr, keys, fgid, vals, labels, start, end, keep));
-  if (*b) XF_TRY(xf_sbatch_set_slices(*b, ids, R));
+  if (staged) XF_TRY(stage_rows(b, update, d, next, keep));
+  if (ids && *b) XF_TRY(xf_sbatch_set_slices(*b, ids, id_rows));
+  // (held-out validation: the held part after the train part; in a group a turn without rows
+  // still adds the empty minibatch to the held list, so that every rank validates equally often)
+  if (own && update && split_ && (rows_here || world > 1)) return keep_held(dev_rows(he));
   return XF_OK;
 }
 
-int Worker::compile_rows_unsliced(xf_sharded *trainer, xf_sbatch **b, int update,
-                                  const uint64_t *rowptr, const uint64_t *keys, const int32_t *fgid,
-                                  const float *vals, const int32_t *labels, size_t start,
-                                  size_t end, int keep) {
-  // (training blocks only — predict passes update 0 — and only rows of this rank's own)
-  if (sample_ && update && trainer == sharded_ && rowptr && end > start)
-    return compile_sampled(b, rowptr, keys, fgid, vals, labels, start, end, keep);
-  // (rows of this rank's own, training and predict; a rank without rows has nothing to cross)
-  if (cross_ && trainer == sharded_ && rowptr && end > start)
-    return compile_crossed(b, update, rowptr, keys, fgid, vals, labels, start, end, keep);
-  if (admit_ && trainer == sharded_) {  // (core_num 1: filtered, compiled from device arrays)
-    // (a rank without rows of its own — a shared filter — is in the collective apply all the same)
-    if (!rowptr)
-      return compile_admitted_dev(b, update, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0,
-                                  keep);
-    return compile_admitted(b, update, rowptr, keys, fgid, vals, labels, start, end, keep);
-  }
-  // (row normalisation with no other stage on: rows of this rank's own, training and predict)
-  if (norm_ && trainer == sharded_ && rowptr && end > start)
-    return compile_normed(b, rowptr, keys, fgid, vals, labels, start, end, keep);
+// the _dev compile of the worker's mode on device arrays
+int Worker::compile_dev_mode(xf_sbatch **b, const DevRows &r, int keep) {
   if (fm_mode == XF_FM_FIELD_AWARE)
-    return xf_sharded_compile_fielded(trainer, b, rowptr, keys, fgid,
-                                      feature_values ? vals : nullptr, labels, start, end, keep);
+    return xf_sharded_compile_fielded_dev(sharded_, b, r.keys, r.fgid,
+                                          feature_values ? r.vals : nullptr, r.rowptr, r.labels,
+                                          r.R, r.NNZ, keep);
   if (feature_values)
-    return xf_sharded_compile_valued(trainer, b, rowptr, keys, vals, labels, start, end, keep);
-  if (end > start)
-    return xf_sharded_compile(trainer, b, rowptr, keys, labels, start, end, keep);
-  return compile_no_rows(trainer, b, keep);
-}
-
-// row normalisation, when on — the last stage, over the nonzeros the model receives — and the _dev
-// compile of the worker's mode on device arrays
-int Worker::compile_dev_arrays(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
-                               const float *d_vals, const uint32_t *d_rowptr,
-                               const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
-  if (norm_ && R) {
-    void *stream = nullptr;
-    XF_TRY(xf_sharded_stream(sharded_, &stream));
-    XF_TRY(xf_rownorm_apply_dev(norm_, d_vals, d_rowptr, R, NNZ, stream, &d_vals, nullptr));
-  }
-  return compile_dev_mode(b, d_keys, d_fgid, d_vals, d_rowptr, d_labels, R, NNZ, keep);
-}
-
-int Worker::compile_dev_mode(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
-                             const float *d_vals, const uint32_t *d_rowptr,
-                             const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep) {
-  if (fm_mode == XF_FM_FIELD_AWARE)
-    return xf_sharded_compile_fielded_dev(sharded_, b, d_keys, d_fgid,
-                                          feature_values ? d_vals : nullptr, d_rowptr, d_labels, R,
-                                          NNZ, keep);
-  if (feature_values)
-    return xf_sharded_compile_valued_dev(sharded_, b, d_keys, d_vals, d_rowptr, d_labels, R, NNZ,
-                                         keep);
-  return xf_sharded_compile_dev(sharded_, b, d_keys, d_rowptr, d_labels, R, NNZ, keep);
-}
-
-int Worker::compile_admitted_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
-                                 const int32_t *d_fgid, const float *d_vals,
-                                 const uint32_t *d_rowptr, const int32_t *d_labels, uint32_t R,
-                                 uint32_t NNZ, int keep) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  const uint64_t *fk = nullptr;
-  const int32_t *ff = nullptr;
-  const float *fv = nullptr;
-  const uint32_t *fr = nullptr;
-  uint32_t kept = 0;
-  XF_TRY(xf_admit_apply_dev(admit_, update, d_keys,
-                            fm_mode == XF_FM_FIELD_AWARE ? d_fgid : nullptr,
-                            feature_values ? d_vals : nullptr, d_rowptr, R, NNZ, stream, &fk, &ff,
-                            &fv, &fr, &kept));
-  return compile_dev_arrays(b, fk, ff, fv, fr, d_labels, R, kept, keep);
-}
-
-int Worker::compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr,
-                             const uint64_t *keys, const int32_t *fgid, const float *vals,
-                             const int32_t *labels, size_t row_begin, size_t row_end, int keep) {
-  void *stream = nullptr;
-  XF_TRY(xf_sharded_stream(sharded_, &stream));
-  const uint64_t *fk = nullptr;
-  const int32_t *ff = nullptr, *fl = nullptr;
-  const float *fv = nullptr;
-  const uint32_t *fr = nullptr;
-  uint32_t R = 0, kept = 0;
-  XF_TRY(xf_admit_apply(admit_, update, rowptr, keys,
-                        fm_mode == XF_FM_FIELD_AWARE ? fgid : nullptr,
-                        feature_values ? vals : nullptr, labels, row_begin, row_end, stream, &fk,
-                        &ff, &fv, &fr, &fl, &R, &kept));
-  return compile_dev_arrays(b, fk, ff, fv, fr, fl, R, kept, keep);
+    return xf_sharded_compile_valued_dev(sharded_, b, r.keys, r.vals, r.rowptr, r.labels, r.R,
+                                         r.NNZ, keep);
+  return xf_sharded_compile_dev(sharded_, b, r.keys, r.rowptr, r.labels, r.R, r.NNZ, keep);
 }
 
 // ingest = gpu_fields: what the tokeniser reads beside the fid is what the model needs — fgid for
@@ -1468,24 +1343,14 @@ int Worker::text_epoch(int epoch, int keep, bool *took) {
     size_t rows = 0;
     bool on_gpu = false;
     if (!mine_done) {
-      const uint64_t *dk = nullptr;
-      const uint32_t *drp = nullptr;
-      const int32_t *dl = nullptr;
-      uint32_t R = 0, NNZ = 0;
+      DevRows d{};
       int ok = 0;
-      rc = xf_ingest_block(ingest_[k], nullptr, p->len, stream, &dk, &drp, &dl, &R, &NNZ, &ok);
+      rc = xf_ingest_block(ingest_[k], nullptr, p->len, stream, &d.keys, &d.rowptr, &d.labels, &d.R,
+                           &d.NNZ, &ok);
       if (rc == XF_OK && ok) {
-        const int32_t *dfg = nullptr;
-        const float *dv = nullptr;
-        rc = xf_ingest_fields(ingest_[k], &dfg, &dv);
-        rows = R;
-        if (rc == XF_OK && split_) rc = split_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ);
-        if (rc == XF_OK && (sample_ || split_)) {
-          if (sample_) rc = sample_dev(0, &dk, &dfg, &dv, &drp, &dl, &R, &NNZ);
-          if (rc == XF_OK) rc = compile_sampled_dev(&b, dk, dfg, dv, drp, dl, R, NNZ, keep);
-          if (rc == XF_OK && split_) rc = keep_held(pending_held_);
-        } else if (rc == XF_OK)
-          rc = compile_staged_dev(&b, 1, dk, dfg, dv, drp, dl, R, NNZ, keep);
+        rc = xf_ingest_fields(ingest_[k], &d.fgid, &d.vals);
+        rows = d.R;
+        if (rc == XF_OK) rc = stage_rows(&b, 1, d, kSplit, keep);
         on_gpu = true;
         ++blocks_gpu;
       } else if (rc == XF_OK) {  // not of the common shape: the host parser's

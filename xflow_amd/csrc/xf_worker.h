@@ -103,8 +103,9 @@ class Worker {
   int cross_fgid_base = 0;
   // Row normalisation (xf_rownorm.hip): row_norm = l2: every minibatch of this rank's own rows —
   // training, the held part of holdout, predict — gets unit L2 length per row on the GPU.  The
-  // LAST stage, immediately ahead of the key build: ingest, split, negsample, slices, cross,
-  // admission, row norm, compile — over the nonzeros the model receives.  Off = nothing is
+  // LAST stage, immediately ahead of the key build (the order of the stages is the enum Stage
+  // below, which stage_rows runs top to bottom) — over the nonzeros the model receives.  Off =
+  // nothing is
   // created.  Needs feature_values=on, core_num 1, key_build=gpu, parity=exact (checked where
   // training starts).  Nothing travels with the model: predict needs the same row_norm=.
   bool row_norm = false;
@@ -185,17 +186,6 @@ class Worker {
   std::vector<int> holdout_epochs_;    // ... and which epoch that was
   xf_progress_metrics holdout_last_{}, holdout_first_{};
   int epochs_run_ = 0;
-  // split a training block (device arrays): the train part in the arguments, the held part in
-  // pending_held_
-  int split_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
-                const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
-                uint32_t *R, uint32_t *NNZ);
-  int keep_held(const xf_holdout_part &held);
-  xf_holdout_part pending_held_{};  // split_dev's held part, until the train part is compiled
-  // ... or rows [start, end) of host arrays; then the train part's stages and compile
-  int compile_split(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                    const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
-                    size_t end, int keep);
   int check_evict() const;      // the refusals of evict_n, before any rendezvous
   int evict_epoch(int epoch);   // COLLECTIVE at world > 1: evict, sum the counts, print
   uint64_t evict_seen_ = 0, evict_dropped_ = 0;  // totals of the run, summed over the ranks
@@ -210,14 +200,6 @@ class Worker {
   xf_slices *slicer_ = nullptr;
   double slices_last_[4] = {0, 0, 0, 0};  // slices, rows, none rows, overflow rows of the last epoch
   bool slices_have_ = false;
-  // rows [start, end) of host arrays with the feature on: the ids from the stage's own upload,
-  // then the compile the block would have taken, then the ids onto the minibatch
-  int compile_sliced(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                     const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
-                     size_t end, int keep);
-  int compile_rows_unsliced(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
-                            const uint64_t *keys, const int32_t *fgid, const float *vals,
-                            const int32_t *labels, size_t start, size_t end, int keep);
   int create_tables();
   int defrag_if_grown(int percent);
   int any_rank(bool mine, bool *any);
@@ -229,59 +211,49 @@ class Worker {
   uint64_t sample_stream_ = 0;      // (epoch << 32) | rank of the running epoch
   int check_negsample() const;      // the refusals of neg_keep, before any rendezvous
   int create_negsample();
-  // sample a training block (device arrays, replaced in place by the sampler's; fgid / vals only
-  // in the modes that read them), rows numbered from ordinal_ + first_row
-  int sample_dev(size_t first_row, const uint64_t **d_keys, const int32_t **d_fgid,
-                 const float **d_vals, const uint32_t **d_rowptr, const int32_t **d_labels,
-                 uint32_t *R, uint32_t *NNZ);
-  // ... or rows [start, end) of host arrays; then admission, when on, and the _dev compile.  A
-  // block whose rows are all dropped is a block without rows: on one worker no minibatch
-  // (*b = nullptr), in a group the empty minibatch
-  int compile_sampled(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                      const int32_t *fgid, const float *vals, const int32_t *labels,
-                      size_t start, size_t end, int keep);
-  int compile_sampled_dev(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
-                          const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
-                          uint32_t R, uint32_t NNZ, int keep);
   xf_cross *cross_ = nullptr;  // cross=SPEC: the stage, created with the tables
   int check_cross() const;     // the refusals of cross, before any rendezvous
   int create_cross();
-  // device arrays: the cross, when on, then admission, when on, then the _dev compile
-  int compile_staged_dev(xf_sbatch **b, int update, const uint64_t *d_keys, const int32_t *d_fgid,
-                         const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
-                         uint32_t R, uint32_t NNZ, int keep);
-  // ... rows [start, end) of host arrays, uploaded by the cross
-  int compile_crossed(xf_sbatch **b, int update, const uint64_t *rowptr, const uint64_t *keys,
-                      const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
-                      size_t end, int keep);
-  // filter a block (host arrays and a row slice / device arrays), then the matching _dev compile
-  int compile_admitted(xf_sbatch **b, int update, const uint64_t *rowptr, const uint64_t *keys,
-                       const int32_t *fgid, const float *vals, const int32_t *labels,
-                       size_t row_begin, size_t row_end, int keep);
-  int compile_admitted_dev(xf_sbatch **b, int update, const uint64_t *d_keys,
-                           const int32_t *d_fgid, const float *d_vals, const uint32_t *d_rowptr,
-                           const int32_t *d_labels, uint32_t R, uint32_t NNZ, int keep);
-  // the compile of the worker's mode: rows [start, end) of host arrays on `trainer` (admitted,
-  // fielded, valued, plain, or — no rows — the empty minibatch), device arrays on sharded_
-  int compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
-                   const uint64_t *keys, const int32_t *fgid, const float *vals,
-                   const int32_t *labels, size_t start, size_t end, int keep);
-  int compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep);
-  int compile_dev_arrays(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
-                         const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
-                         uint32_t R, uint32_t NNZ, int keep);
-  // ... compile_dev_arrays without row normalisation in front (the values are normalised already)
-  int compile_dev_mode(xf_sbatch **b, const uint64_t *d_keys, const int32_t *d_fgid,
-                       const float *d_vals, const uint32_t *d_rowptr, const int32_t *d_labels,
-                       uint32_t R, uint32_t NNZ, int keep);
   xf_rownorm *norm_ = nullptr;  // row_norm=l2: the stage, created with the tables
   int check_rownorm() const;    // the refusals of row_norm, before any rendezvous
   int create_rownorm();
-  // rows [start, end) of host arrays with no other stage on: uploaded by the stage, then the
-  // _dev compile
-  int compile_normed(xf_sbatch **b, const uint64_t *rowptr, const uint64_t *keys,
-                     const int32_t *fgid, const float *vals, const int32_t *labels, size_t start,
-                     size_t end, int keep);
+  // ---- from a block's rows to its compiled minibatch.  The stages in the order they run:
+  // stage_rows IS this order.  Each runs only while its parameter is on.
+  enum Stage {
+    kSplit,    // holdout: training blocks; the held part leaves the chain here (keep_held)
+    kSample,   // neg_keep: training blocks; under the split it numbers the rows of the train part
+    kSlices,   // progress_by: training blocks; names the rows before the cross adds nonzeros
+    kCross,    // cross
+    kAdmit,    // admit_count: counts on training blocks, filters on every block
+    kNorm,     // row_norm: over the nonzeros the model receives
+    kCompile   // the _dev compile of the worker's mode
+  };
+  struct DevRows {  // a block's rows as device arrays, in the order of the trainer's stream
+    const uint64_t *keys;
+    const int32_t *fgid;
+    const float *vals;
+    const uint32_t *rowptr;
+    const int32_t *labels;
+    uint32_t R, NNZ;
+  };
+  static DevRows dev_rows(const xf_holdout_part &p) {
+    return {p.d_keys, p.d_fgid, p.d_vals, p.d_rowptr, p.d_labels, p.R, p.NNZ};
+  }
+  DevRows count_train(const xf_holdout_part &train);  // ... and the train part's running counts
+  bool carries_fgid(Stage s) const;  // does stage s hand the nonzeros' fgid to those behind it
+  // rows [start, end) of a block's host arrays on `trainer`; update: a training block.  This
+  // rank's own rows enter the chain through the first stage that is on — its own upload — and go
+  // on below it; a foreign trainer, no stage on, or a turn without rows: the host compile of the
+  // worker's mode (fielded, valued, plain, or the empty minibatch)
+  int compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const uint64_t *rowptr,
+                   const uint64_t *keys, const int32_t *fgid, const float *vals,
+                   const int32_t *labels, size_t start, size_t end, int keep);
+  // device arrays through the stages from `from` on.  A block that the split or the sampler leaves
+  // without rows is no minibatch on one worker (*b = nullptr), the empty minibatch in a group
+  int stage_rows(xf_sbatch **b, int update, DevRows rows, Stage from, int keep);
+  int keep_held(const DevRows &held);  // the split's held part: named, staged, onto the held list
+  int compile_no_rows(xf_sharded *trainer, xf_sbatch **b, int keep);
+  int compile_dev_mode(xf_sbatch **b, const DevRows &rows, int keep);
   uint64_t keys_seen_ = 0;  // the table's keys at the last look (defrag_if_grown: the inflow per minibatch)
   bool rank_given_ = false;
 
