@@ -1473,6 +1473,82 @@ int xf_rownorm_stats(const xf_rownorm *n, uint64_t *rows_seen, uint64_t *rows_sc
 void xf_rownorm_shape(uint32_t out[2]);
 uint64_t xf_rownorm_launches(void);
 
+/* ---------------------------------------------------------------- value binning        */
+/* Equal-frequency discretisation of numeric fields as a GPU stage ahead of the cross (not in the
+ * reference; libffm's Criteo recipe, xLearn's preprocessing and every GBDT front end do it
+ * offline).  A listed field's nonzero gives up its value for the key of the bucket the value falls
+ * into; the buckets are learned from the data.  Everything is integer-exact.
+ * Spec.  1 .. 64 pairs field:bins, the fields distinct and in 0 .. 2^31 - 1, bins in 2 .. 255.
+ * xf_bin_parse reads "13:32,14:32,20:16" (decimal, no blanks) into arrays of `cap` entries; a
+ * malformed spec is XF_EINVAL naming the offending piece.  xf_bin_create checks the same rules.
+ * Code of a value (csrc/xf_bin.h, one for the host and the kernels), XF_BIN_CODE_BITS = 12 bits:
+ *   -0.0f counts as +0.0f; a NaN of any sign and payload has code 4095; otherwise, with u the bits
+ *   of v, k = (u >> 31) ? ~u : (u | 0x80000000) and code = k >> 20.
+ * The code is monotone in v and keeps the sign, the exponent and 3 mantissa bits: the integers
+ * 1 .. 15 each have a code of their own, +infinity has 4088, only NaNs reach 4095.  xf_bin_code is
+ * that function as host code.
+ * Fit.  count[c] = the fitted nonzeros of the field with code c, an exact 64-bit total.
+ *   T = the sum of count[c] over c < 4095 (NaNs are left out); C(c) = the sum of count[j] over
+ *   j < c; lut[c] = min(bins - 1, floor(C(c) * bins / T)) for c < 4095, 0 when T = 0;
+ *   lut[4095] = bins: NaN has a bucket of its own, hence bins <= 255 and a table of bytes.
+ * T >= 2^56 is XF_EINVAL (the product stays inside 64 bits).  Bucket ids need not be dense: a heavy
+ * code spans several quantiles.  xf_bin_lut_from_counts is that cut, a pure host function of one
+ * field's 4096 counts.
+ * Rewrite.  A nonzero (key, fgid, val) whose fgid is listed becomes
+ *   (xf_bin_key(key, fgid, lut[code(val)]), fgid, 1.0f),
+ *   xf_bin_key(key, f, b) = mix64(mix64(key ^ XF_BIN_SALT) + ((uint64)(uint32)f << 32 | b)),
+ * mix64 as for admission, 64-bit wrapping.  Every other nonzero passes bit for bit; rows, offsets,
+ * fgid and labels are not touched.
+ * xf_bin_count_dev: one launch over NNZ nonzeros of device arrays (none with NNZ = 0), no host
+ * wait; the totals of several counts add.  xf_bin_count: rows [row_begin, row_end) of a block's
+ * host arrays: uploads the slice's fgid and vals and runs the device form.  xf_bin_counts: the
+ * n x 4096 totals, in spec order (one wait).  xf_bin_fit cuts the totals and freezes the LUTs: a
+ * count after it is XF_EINVAL, and so is an apply, a save or xf_bin_lut before it.  xf_bin_lut:
+ * the n x 4096 bytes; xf_bin_set_lut: the inverse — it freezes too (a bucket above its field's
+ * bins is XF_EINVAL).
+ * xf_bin_apply_dev: device arrays; *d_keys_out and *d_vals_out are NNZ rewritten keys and values,
+ * device arrays owned by the stage, grown geometrically, written in the order of `stream` with no
+ * host wait and valid until the next apply on the object.  The inputs are never written.
+ * xf_bin_apply: rows [row_begin, row_end) of a block's host arrays: checks the offsets on the CPU,
+ * uploads the slice (rowptr rebased to u32; fgid and labels unchanged) and calls the device entry.
+ * xf_bin_save / xf_bin_load: the LUTs with their spec in a file; loading a file fitted for another
+ * spec is XF_EINVAL naming both.  xf_bin_stats, summed over the applies: nonzeros seen (counted on
+ * the host) and nonzeros binned (counted on the device; reading it is the one wait).
+ * xf_bin_shape: {nonzeros of a count tile, listed fields of a count workgroup, the count's widest
+ * grid, nonzeros of an apply tile}, for the tests that aim at the edges.  xf_bin_launches: count
+ * and apply kernels launched in this process. */
+#define XF_BIN_CODE_BITS 12
+#define XF_BIN_SALT 0x62696e5f76616c73ull
+typedef struct xf_bin xf_bin;
+int xf_bin_parse(const char *spec, int32_t *field, int32_t *bins, int cap, int *n);
+int xf_bin_create(xf_bin **out, const int32_t *field, const int32_t *bins, int n);
+int xf_bin_destroy(xf_bin *b);
+int xf_bin_params(const xf_bin *b, int32_t *field, int32_t *bins, int cap, int *n);
+uint32_t xf_bin_code(float v);
+uint64_t xf_bin_key(uint64_t key, int32_t f, uint32_t b);
+int xf_bin_lut_from_counts(const uint64_t *count, int bins, uint8_t *lut);
+int xf_bin_count_dev(xf_bin *b, const int32_t *d_fgid, const float *d_vals, uint32_t NNZ,
+                     void *stream);
+int xf_bin_count(xf_bin *b, const uint64_t *rowptr, const int32_t *fgid, const float *vals,
+                 size_t row_begin, size_t row_end, void *stream);
+int xf_bin_counts(const xf_bin *b, uint64_t *count, size_t cap);
+int xf_bin_fit(xf_bin *b);
+int xf_bin_lut(const xf_bin *b, uint8_t *lut, size_t cap);
+int xf_bin_set_lut(xf_bin *b, const uint8_t *lut, size_t bytes);
+int xf_bin_apply_dev(xf_bin *b, const uint64_t *d_keys, const int32_t *d_fgid, const float *d_vals,
+                     uint32_t NNZ, void *stream, const uint64_t **d_keys_out,
+                     const float **d_vals_out);
+int xf_bin_apply(xf_bin *b, const uint64_t *rowptr, const uint64_t *keys, const int32_t *fgid,
+                 const float *vals, const int32_t *labels, size_t row_begin, size_t row_end,
+                 void *stream, const uint64_t **d_keys_out, const int32_t **d_fgid_out,
+                 const float **d_vals_out, const uint32_t **d_rowptr_out,
+                 const int32_t **d_labels_out, uint32_t *R_out, uint32_t *NNZ_out);
+int xf_bin_save(const xf_bin *b, const char *path);
+int xf_bin_load(xf_bin *b, const char *path);
+int xf_bin_stats(const xf_bin *b, uint64_t *nonzeros_seen, uint64_t *nonzeros_binned);
+void xf_bin_shape(uint32_t out[4]);
+uint64_t xf_bin_launches(void);
+
 /* ---------------------------------------------------------------- metrics             */
 /* Base::calculate_auc (base.h:84-110): reference-format logloss (mean of y*log2 p +
  * (1-y)*log2(1-p), negative), AUC by descending-pctr rank sum, plus the conventional
@@ -1539,6 +1615,17 @@ int XFDestroy(void **h);
  *        feature_values=on, core_num 1, key_build=gpu, parity=exact; the setting is not saved
  *        with the model: predict needs the same row_norm=; rank 0 prints "row_norm: rows = ...
  *        scaled = ... left = ..." after training).  XFGetMetric: norm_rows norm_rows_scaled
+ *        bin(SPEC, e.g. 13:32,14:16; default off: value binning, xf_bin_* — a listed field's
+ *        nonzero gives up its value for the key of its equal-frequency bucket, on the GPU, behind
+ *        the slices and ahead of the cross: slices and held-row groups are named by the raw key,
+ *        the cross, admission, the norm and the model see the bucket keys; before epoch 0 the host
+ *        reader goes over the training file once and the stage counts and fits, rank 0 prints
+ *        "bin: fields = n fit_rows = ... fit_nonzeros = ..."; XFSaveModel writes <path>.bins beside
+ *        the model, XFLoadModel needs it and refuses one fitted for another spec, and nothing is
+ *        fitted after a load; after training rank 0 prints "bin: nonzeros = ... binned = ...";
+ *        needs feature_values=on, core_num 1, key_build=gpu, parity=exact, not ingest=gpu, one
+ *        worker) bin_fit_rows(N >= 0, default 0 = the whole training file: the fit reads whole
+ *        blocks until it has N rows).  XFGetMetric: bin_fit_rows bin_nonzeros bin_binned
  *        progress(0|1, default 0: progressive validation, xf_progress_* — every training step
  *        counts its rows' losses under the weights it is about to change, with no host wait inside
  *        an epoch; at the end of every epoch, replayed ones included, the counts are read, summed

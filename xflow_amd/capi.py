@@ -397,6 +397,28 @@ SIGNATURES = {
     "xf_rownorm_stats": (C.c_int, [vp, u64p, u64p]),
     "xf_rownorm_shape": (None, [u32p]),
     "xf_rownorm_launches": (C.c_uint64, []),
+    "xf_bin_parse": (C.c_int, [C.c_char_p, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
+    "xf_bin_create": (C.c_int, [C.POINTER(vp), i32p, i32p, C.c_int]),
+    "xf_bin_destroy": (C.c_int, [vp]),
+    "xf_bin_params": (C.c_int, [vp, i32p, i32p, C.c_int, C.POINTER(C.c_int)]),
+    "xf_bin_code": (C.c_uint32, [C.c_float]),
+    "xf_bin_key": (C.c_uint64, [C.c_uint64, C.c_int32, C.c_uint32]),
+    "xf_bin_lut_from_counts": (C.c_int, [u64p, C.c_int, C.POINTER(C.c_uint8)]),
+    "xf_bin_count_dev": (C.c_int, [vp, vp, vp, C.c_uint32, vp]),
+    "xf_bin_count": (C.c_int, [vp, u64p, i32p, f32p, C.c_size_t, C.c_size_t, vp]),
+    "xf_bin_counts": (C.c_int, [vp, u64p, C.c_size_t]),
+    "xf_bin_fit": (C.c_int, [vp]),
+    "xf_bin_lut": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_size_t]),
+    "xf_bin_set_lut": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_size_t]),
+    "xf_bin_apply_dev": (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, C.POINTER(vp), C.POINTER(vp)]),
+    "xf_bin_apply": (C.c_int, [vp, u64p, u64p, i32p, f32p, i32p, C.c_size_t, C.c_size_t, vp,
+                               C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                               C.POINTER(vp), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "xf_bin_save": (C.c_int, [vp, C.c_char_p]),
+    "xf_bin_load": (C.c_int, [vp, C.c_char_p]),
+    "xf_bin_stats": (C.c_int, [vp, u64p, u64p]),
+    "xf_bin_shape": (None, [u32p]),
+    "xf_bin_launches": (C.c_uint64, []),
     "XFCreate": (C.c_int, [C.POINTER(vp), C.c_char_p, C.c_char_p]),
     "XFStartTrain": (C.c_int, [C.POINTER(vp)]),
     "XFDestroy": (C.c_int, [C.POINTER(vp)]),
@@ -1608,6 +1630,175 @@ class RowNorm:
         """(rows seen, rows scaled), summed over the applies; reading waits for the device"""
         v = [C.c_uint64() for _ in range(2)]
         check(lib().xf_rownorm_stats(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+
+BIN_CODES = 4096
+u8p = C.POINTER(C.c_uint8)
+
+
+def bin_code(v):
+    """the 12-bit code of the value v as a float32 (xf_bin_code; host code, the kernels' own
+    definition); bin_code(3) is bin_code(3.0)"""
+    return int(lib().xf_bin_code(C.c_float(float(v))))
+
+
+def bin_key(key, f, b):
+    """the key of a binned nonzero of field f in bucket b (xf_bin_key; host code)"""
+    return int(lib().xf_bin_key(int(key) & (2**64 - 1), int(f), int(b)))
+
+
+def bin_lut(counts, bins):
+    """one field's 4096-byte LUT cut from its 4096 counts (xf_bin_lut_from_counts; no GPU)"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    assert counts.shape == (BIN_CODES,)
+    lut = np.zeros(BIN_CODES, np.uint8)
+    check(lib().xf_bin_lut_from_counts(_p(counts, u64p), int(bins), _p(lut, u8p)))
+    return lut
+
+
+def bin_parse(spec):
+    """"13:32,14:16" as a list of (field, bins) pairs (xf_bin_parse; a malformed spec raises)"""
+    f, b = np.zeros(64, np.int32), np.zeros(64, np.int32)
+    n = C.c_int()
+    check(lib().xf_bin_parse(str(spec).encode(), _p(f, i32p), _p(b, i32p), 64, C.byref(n)))
+    return [(int(f[p]), int(b[p])) for p in range(n.value)]
+
+
+class Bin:
+    """Value binning (xf_bin_*): count() histograms the values of the listed fields on the GPU,
+    fit() cuts the counts into equal-frequency buckets, apply() replaces a listed field's nonzero
+    (key, fgid, val) by (bin_key(key, fgid, bucket), fgid, 1.0).  spec_or_pairs: "13:32,14:16" or a
+    list of (field, bins)."""
+
+    def __init__(self, spec_or_pairs):
+        self.h = vp()
+        pairs = bin_parse(spec_or_pairs) if isinstance(spec_or_pairs, str) else \
+            [(int(a), int(b)) for a, b in spec_or_pairs]
+        self.n = len(pairs)
+        f = np.array([a for a, _ in pairs] or [0], np.int32)
+        b = np.array([b for _, b in pairs] or [0], np.int32)
+        check(lib().xf_bin_create(C.byref(self.h), _p(f, i32p), _p(b, i32p), len(pairs)))
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().xf_bin_destroy(self.h)
+            self.h = None
+
+    @staticmethod
+    def shape():
+        """(nonzeros of a count tile, listed fields of a count workgroup, the count's widest grid,
+        nonzeros of an apply tile)"""
+        out = np.zeros(4, np.uint32)
+        lib().xf_bin_shape(_p(out, u32p))
+        return tuple(int(x) for x in out)
+
+    @staticmethod
+    def launches():
+        """count and apply kernels launched in this process"""
+        return int(lib().xf_bin_launches())
+
+    def params(self):
+        """the spec as a list of (field, bins)"""
+        f, b = np.zeros(64, np.int32), np.zeros(64, np.int32)
+        n = C.c_int()
+        check(lib().xf_bin_params(self.h, _p(f, i32p), _p(b, i32p), 64, C.byref(n)))
+        return [(int(f[p]), int(b[p])) for p in range(n.value)]
+
+    def count(self, fgid, values, rowptr=None, row_begin=0, row_end=None, stream=None):
+        """xf_bin_count: the nonzeros of rows [row_begin, row_end) of host arrays (rowptr None:
+        all of them, as one row) are added to the totals"""
+        fgid = np.ascontiguousarray(fgid, dtype=np.int32)
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        assert len(fgid) == len(values), "one value per field id"
+        rowptr = np.array([0, len(fgid)], np.uint64) if rowptr is None else \
+            np.ascontiguousarray(rowptr, dtype=np.uint64)
+        row_end = len(rowptr) - 1 if row_end is None else row_end
+        if len(fgid) == 0:
+            fgid, values = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        check(lib().xf_bin_count(self.h, _p(rowptr, u64p), _p(fgid, i32p), _p(values, f32p),
+                                 row_begin, row_end, stream))
+
+    def count_dev(self, d_fgid, d_vals, NNZ, stream=None):
+        """xf_bin_count_dev: device pointers in (ints)"""
+        check(lib().xf_bin_count_dev(self.h, d_fgid, d_vals, NNZ, stream))
+
+    def counts(self):
+        """the totals so far: uint64 (fields, 4096), in spec order"""
+        out = np.zeros((self.n, BIN_CODES), np.uint64)
+        check(lib().xf_bin_counts(self.h, _p(out, u64p), out.size))
+        return out
+
+    def fit(self):
+        """cuts the totals into the LUTs and freezes them"""
+        check(lib().xf_bin_fit(self.h))
+
+    def lut(self):
+        """the LUTs: uint8 (fields, 4096), in spec order"""
+        out = np.zeros((self.n, BIN_CODES), np.uint8)
+        check(lib().xf_bin_lut(self.h, _p(out, u8p), out.size))
+        return out
+
+    def set_lut(self, lut):
+        lut = np.ascontiguousarray(lut, dtype=np.uint8)
+        check(lib().xf_bin_set_lut(self.h, _p(lut, u8p), lut.size))
+
+    def save(self, path):
+        check(lib().xf_bin_save(self.h, str(path).encode()))
+
+    def load(self, path):
+        check(lib().xf_bin_load(self.h, str(path).encode()))
+
+    def apply_dev(self, rowptr, keys, fgid, values, labels=None, row_begin=0, row_end=None,
+                  stream=None):
+        """host arrays in (rows [row_begin, row_end) uploaded by the stage), the binned minibatch
+        as an AdmitDev out (device arrays owned by the stage, valid until its next apply).
+        WRITTEN IN THE ORDER OF `stream`; the call does not wait: hand them to work on the same
+        stream or wait first"""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.uint64)
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        fgid = np.ascontiguousarray(fgid, dtype=np.int32)
+        values = np.ascontiguousarray(values, dtype=np.float32)
+        assert len(rowptr) >= 1 and len(fgid) == len(keys) == len(values), "one entry per key"
+        row_end = len(rowptr) - 1 if row_end is None else row_end
+        if labels is not None:
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            assert len(labels) == len(rowptr) - 1, "one label per row"
+            labels = labels if len(labels) else np.zeros(1, np.int32)
+        if len(keys) == 0:
+            keys, fgid = np.zeros(1, np.uint64), np.zeros(1, np.int32)
+            values = np.zeros(1, np.float32)
+        dk, dfg, dv, dr, dl = vp(), vp(), vp(), vp(), vp()
+        Ro, No = C.c_uint32(), C.c_uint32()
+        check(lib().xf_bin_apply(self.h, _p(rowptr, u64p), _p(keys, u64p), _p(fgid, i32p),
+                                 _p(values, f32p),
+                                 _p(labels, i32p) if labels is not None else None, row_begin,
+                                 row_end, stream, C.byref(dk), C.byref(dfg), C.byref(dv),
+                                 C.byref(dr), C.byref(dl), C.byref(Ro), C.byref(No)))
+        return AdmitDev(dk.value, dr.value, dl.value, Ro.value, No.value, dfg.value, dv.value)
+
+    def bin_dev(self, d_keys, d_fgid, d_vals, NNZ, stream=None):
+        """xf_bin_apply_dev: device pointers in (ints), (d_keys_out, d_vals_out) out"""
+        dk, dv = vp(), vp()
+        check(lib().xf_bin_apply_dev(self.h, d_keys, d_fgid, d_vals, NNZ, stream, C.byref(dk),
+                                     C.byref(dv)))
+        return dk.value, dv.value
+
+    def apply(self, rowptr, keys, fgid, values, labels=None, row_begin=0, row_end=None):
+        """the host arrays of the binned minibatch (downloaded): (rowptr uint32, keys, fgid,
+        values) and then labels when they were given"""
+        d = self.apply_dev(rowptr, keys, fgid, values, labels, row_begin, row_end)
+        dl = RowNorm.download
+        out = [dl(d.d_rowptr, d.R + 1, np.uint32), dl(d.d_keys, d.NNZ, np.uint64),
+               dl(d.d_fgid, d.NNZ, np.int32), dl(d.d_vals, d.NNZ, np.float32)]
+        if labels is not None:
+            out.append(dl(d.d_labels, d.R, np.int32))
+        return tuple(out)
+
+    def stats(self):
+        """(nonzeros seen, nonzeros binned), summed over the applies; reading waits for the device"""
+        v = [C.c_uint64() for _ in range(2)]
+        check(lib().xf_bin_stats(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
 

@@ -58,6 +58,7 @@ Worker::~Worker() {
   if (sample_) xf_negsample_destroy(sample_);
   if (cross_) xf_cross_destroy(cross_);
   if (norm_) xf_rownorm_destroy(norm_);
+  if (bin_) xf_bin_destroy(bin_);
   if (slicer_) xf_slices_destroy(slicer_);
   if (gslicer_) xf_slices_destroy(gslicer_);
   if (sharded_) xf_sharded_destroy(sharded_);  // owns the tables
@@ -81,10 +82,12 @@ int Worker::create_tables() {
   // (row_norm's refusals by its own name, also where XFLoadModel builds the tables: ahead of the
   // warm-up below, which would refuse a valued minibatch on key_build=host in its own words)
   XF_TRY(check_rownorm());
+  XF_TRY(check_bin());
   if (sharded_) {
     XF_TRY(create_admit());
     XF_TRY(create_negsample());
     XF_TRY(create_holdout());
+    XF_TRY(create_bin());
     XF_TRY(create_cross());
     return create_rownorm();
   }
@@ -169,6 +172,7 @@ int Worker::create_tables() {
   XF_TRY(create_admit());
   XF_TRY(create_negsample());
   XF_TRY(create_holdout());
+  XF_TRY(create_bin());
   XF_TRY(create_cross());
   return create_rownorm();
 }
@@ -583,7 +587,7 @@ int Worker::keep_held(const DevRows &held) {
       XF_TRY(xf_slices_extract_dev(gslicer_, held.keys, held.fgid, held.rowptr, held.R, held.NNZ,
                                    stream, &ids));
     }
-    XF_TRY(stage_rows(&hb, 0, held, kCross, 1));
+    XF_TRY(stage_rows(&hb, 0, held, kBin, 1));
     if (ids && hb) XF_TRY(xf_sbatch_set_slices(hb, ids, held.R));
   }
   if (hb) held_.push_back(hb);
@@ -739,12 +743,86 @@ int Worker::create_rownorm() {
   return rc;
 }
 
+// Value binning rewrites a block's keys and values on the GPU from the nonzeros' field ids and
+// values: without feature values there is no value to bin, core_num > 1 slices a block after it
+// was read, the host key build and the reference-order forward take host arrays, ingest=gpu
+// hands out no fgid, and the counts of several workers are not merged.  All refused by name,
+// before any rendezvous.
+int Worker::check_bin() const {
+  if (bin_spec.empty()) return XF_OK;
+  int32_t f[64], b[64];
+  int n = 0;
+  XF_TRY(xf_bin_parse(bin_spec.c_str(), f, b, 64, &n));
+  const char *s = bin_spec.c_str();
+  XF_REQUIRE(feature_values, "XFStartTrain: bin=%s needs feature_values=on: the stage reads a "
+             "nonzero's value", s);
+  XF_REQUIRE(core_num <= 1, "XFStartTrain: bin=%s needs core_num=1, not core_num=%d", s, core_num);
+  XF_REQUIRE(key_build_gpu, "XFStartTrain: bin=%s together with key_build=host: the binned "
+             "minibatch is born on the GPU (use key_build=gpu)", s);
+  XF_REQUIRE(parity == XF_PARITY_EXACT_SUMS, "XFStartTrain: bin=%s together with "
+             "parity=reference_order: that mode builds its keys on the host", s);
+  XF_REQUIRE(!ingest_gpu, "XFStartTrain: bin=%s together with ingest=gpu: the GPU tokeniser hands "
+             "out no fgid and no value (use ingest=gpu_fields)", s);
+  XF_REQUIRE(world_from_env(world) <= 1, "XFStartTrain: bin=%s runs on one worker only (world %d): "
+             "the workers' counts are not merged", s, world_from_env(world));
+  return XF_OK;
+}
+
+int Worker::create_bin() {
+  if (bin_spec.empty() || bin_) return XF_OK;
+  XF_TRY(check_bin());
+  int32_t f[64], b[64];
+  int n = 0;
+  XF_TRY(xf_bin_parse(bin_spec.c_str(), f, b, 64, &n));
+  return xf_bin_create(&bin_, f, b, n);  // (its first launches are the fit's, before the clock)
+}
+
+// the fit: the host reader goes over the training file once, values on, at most bin_fit_rows rows
+// in whole blocks; every block is counted on the GPU, then the counts are cut and frozen
+int Worker::fit_bins() {
+  if (!bin_ || bin_fitted_) return XF_OK;
+  xf_reader *rd = nullptr;
+  XF_TRY(xf_reader_open(&rd, train_data_path, (size_t)block_size << 20));
+  struct ReaderGuard {
+    xf_reader *r;
+    ~ReaderGuard() { xf_reader_close(r); }
+  } guard{rd};
+  XF_TRY(xf_reader_set_values(rd, 1));
+  void *stream = nullptr;
+  XF_TRY(xf_sharded_stream(sharded_, &stream));
+  bin_fit_rows_ = bin_fit_nnz_ = 0;
+  while (bin_fit_rows == 0 || bin_fit_rows_ < (uint64_t)bin_fit_rows) {
+    size_t rows = 0, nnz = 0;
+    const uint64_t *rowptr = nullptr, *keys = nullptr;
+    const int32_t *fgid = nullptr, *labels = nullptr;
+    const float *vals = nullptr;
+    XF_TRY(xf_reader_next(rd, &rows, &nnz, &rowptr, &keys, &fgid, &labels));
+    if (rows == 0) break;
+    XF_TRY(xf_reader_values(rd, &vals));
+    XF_TRY(xf_bin_count(bin_, rowptr, fgid, vals, 0, rows, stream));
+    XF_TRY(xf_stream_sync(stream));  // (the reader's arrays are its own again with the next block)
+    bin_fit_rows_ += rows;
+    bin_fit_nnz_ += nnz;
+  }
+  XF_TRY(xf_bin_fit(bin_));
+  bin_fitted_ = true;
+  if (rank == 0) {
+    int n = 0;
+    XF_TRY(xf_bin_params(bin_, nullptr, nullptr, 0, &n));
+    char line[200];
+    snprintf(line, sizeof(line), "bin: fields = %d fit_rows = %llu fit_nonzeros = %llu", n,
+             (unsigned long long)bin_fit_rows_, (unsigned long long)bin_fit_nnz_);
+    std::cout << line << std::endl;
+  }
+  return XF_OK;
+}
+
 // Field-aware FM reads a nonzero's fgid, so there every stage carries it.  Otherwise it is carried
 // only as far as a stage that reads it: the slices and the cross sit behind the sampler, so the
 // split and the sampler carry it for them; the held rows' groups are named as the split hands the
 // held part over, so for them the split alone does — the sampler sees training rows only.
 bool Worker::carries_fgid(Stage s) const {
-  return fm_mode == XF_FM_FIELD_AWARE || (s <= kSample && (cross_ || slicer_)) ||
+  return fm_mode == XF_FM_FIELD_AWARE || (s <= kSample && (cross_ || slicer_ || bin_)) ||
          (s == kSplit && gslicer_);
 }
 
@@ -783,6 +861,10 @@ int Worker::stage_rows(xf_sbatch **b, int update, DevRows rows, Stage from, int 
     if (from <= kSlices && update && slicer_ && rows.R)
       XF_TRY(xf_slices_extract_dev(slicer_, rows.keys, rows.fgid, rows.rowptr, rows.R, rows.NNZ,
                                    stream, &ids));
+    // (the bins behind the slices: a slice is named by the raw input key; fgid passes untouched)
+    if (from <= kBin && bin_ && rows.NNZ)
+      XF_TRY(xf_bin_apply_dev(bin_, rows.keys, rows.fgid, rows.vals, rows.NNZ, stream, &rows.keys,
+                              &rows.vals));
     if (from <= kCross && cross_ && rows.R) {  // (a block without rows has nothing to cross)
       const int32_t *ff = nullptr;
       const float *fv = nullptr;
@@ -850,7 +932,11 @@ int Worker::compile_rows(xf_sharded *trainer, xf_sbatch **b, int update, const u
   } else {
     if (train && slicer_)
       XF_TRY(xf_slices_extract(slicer_, rowptr, keys, fgid, start, end, stream, &ids, &id_rows));
-    if (rows_here && cross_) {
+    if (rows_here && bin_) {
+      XF_TRY(xf_bin_apply(bin_, rowptr, keys, fgid, v, labels, start, end, stream, &d.keys, &d.fgid,
+                          &d.vals, &d.rowptr, &d.labels, &d.R, &d.NNZ));
+      next = kCross;
+    } else if (rows_here && cross_) {
       XF_TRY(xf_cross_apply(cross_, rowptr, keys, fgid, v, labels, start, end, stream,
                             carries_fgid(kCross), &d.keys, &d.fgid, &d.vals, &d.rowptr, &d.labels,
                             &d.R, &d.NNZ));
@@ -903,7 +989,8 @@ int Worker::compile_dev_mode(xf_sbatch **b, const DevRows &r, int keep) {
 // field-aware FM, the third field with feature values; neither: the tokeniser of ingest = gpu
 int Worker::set_ingest_fields(xf_ingest *g) {
   return xf_ingest_set_fields(g, ingest_fields && (fm_mode == XF_FM_FIELD_AWARE ||
-                                                   !cross_spec.empty() || progress_by_set ||
+                                                   !cross_spec.empty() || !bin_spec.empty() ||
+                                                   progress_by_set ||
                                                    holdout_by_set),
                               ingest_fields && feature_values);
 }
@@ -1494,6 +1581,7 @@ int Worker::predict(int rank, int block, bool reader) {
 
 // train (lr_worker.cc:207-217, fm_worker.cc:277-287)
 int Worker::train() {
+  XF_TRY(check_bin());  // (ahead of the modes' own checks: its refusals carry its name)
   if (fm_mode == XF_FM_CANONICAL && !sharded_) {  // before any rendezvous of a group
     XF_REQUIRE(model_ == 1, "XFStartTrain: fm_mode=canonical needs model 1 (FM), not model %d",
                model_);
@@ -1563,7 +1651,16 @@ int Worker::train() {
     void *self = this;
     XF_TRY(XFLoadModel(self, model_in.c_str()));
   }
+  XF_TRY(fit_bins());  // (nothing after a load: the LUTs came with the model)
   XF_TRY(batch_training());
+  if (bin_ && rank == 0) {
+    uint64_t seen = 0, binned = 0;
+    XF_TRY(xf_bin_stats(bin_, &seen, &binned));
+    char line[160];
+    snprintf(line, sizeof(line), "bin: nonzeros = %llu binned = %llu", (unsigned long long)seen,
+             (unsigned long long)binned);
+    std::cout << line << std::endl;
+  }
   if (norm_ && rank == 0) {  // (the training minibatches and the held ones; predict follows)
     uint64_t rows = 0, scaled = 0;
     XF_TRY(xf_rownorm_stats(norm_, &rows, &scaled));
@@ -1591,6 +1688,11 @@ int Worker::save_model(const char *path) {
   if (admit_) XF_TRY(xf_admit_save(admit_, apath.c_str()));
   else
     (void)unlink(apath.c_str());
+  // ... and the bins' LUTs, by the same rule
+  const std::string bpath = std::string(path) + ".bins";
+  if (bin_) XF_TRY(xf_bin_save(bin_, bpath.c_str()));
+  else
+    (void)unlink(bpath.c_str());
   if (world > 1) return xf_sharded_save(sharded_, path);
   XF_TRY(xf_sharded_flush(sharded_));
   XF_TRY(xf::model_write(path, table_w_, table_v_, v_width()));
@@ -1605,6 +1707,11 @@ int Worker::load_model(const char *path) {
   XF_TRY(xf_sharded_load(sharded_, path));
   // with admission on the model comes with its filter (a missing file: XF_EIO naming it)
   if (admit_) XF_TRY(xf_admit_load(admit_, (std::string(path) + ".admit").c_str()));
+  // ... and with its bins' LUTs (fitted for another bin=: XF_EINVAL naming both)
+  if (bin_) {
+    XF_TRY(xf_bin_load(bin_, (std::string(path) + ".bins").c_str()));
+    bin_fitted_ = true;
+  }
   return XF_OK;
 }
 
@@ -1746,6 +1853,16 @@ int Worker::set_param(const char *name, const char *value) {
   } else if (n == "cross") {
     XF_REQUIRE(!cross_, "XFSetParam: cross cannot change once the stage exists");
     cross_spec = value;
+  } else if (n == "bin") {
+    XF_REQUIRE(!sharded_ || bin_spec == value, "XFSetParam: bin cannot change once the stage exists");
+    bin_spec = value;
+  } else if (n == "bin_fit_rows") {
+    char *end = nullptr;
+    const long rows = strtol(value, &end, 10);
+    XF_REQUIRE(end != value && *end == '\0' && rows >= 0,
+               "XFSetParam: bin_fit_rows must be 0 (the whole training file) or a number of rows, "
+               "not '%s'", value);
+    bin_fit_rows = rows;
   } else if (n == "row_norm") {
     const bool on = !strcmp(value, "l2");
     XF_REQUIRE(on || !strcmp(value, "off"), "XFSetParam: row_norm must be l2 or off, not '%s'",
@@ -1852,6 +1969,12 @@ int Worker::get_metric(const char *name, double *value) {
     uint64_t rows = 0, scaled = 0;
     if (norm_) XF_TRY(xf_rownorm_stats(norm_, &rows, &scaled));
     *value = (double)(n == "norm_rows" ? rows : scaled);
+  } else if (n == "bin_fit_rows") {
+    *value = (double)bin_fit_rows_;
+  } else if (n == "bin_nonzeros" || n == "bin_binned") {
+    uint64_t seen = 0, binned = 0;
+    if (bin_) XF_TRY(xf_bin_stats(bin_, &seen, &binned));
+    *value = (double)(n == "bin_nonzeros" ? seen : binned);
   } else if (n == "admit_seen" || n == "admit_kept") {
     uint64_t seen = 0, kept = 0;
     if (admit_) XF_TRY(xf_admit_stats(admit_, &seen, &kept));

@@ -109,6 +109,16 @@ class Worker {
   // created.  Needs feature_values=on, core_num 1, key_build=gpu, parity=exact (checked where
   // training starts).  Nothing travels with the model: predict needs the same row_norm=.
   bool row_norm = false;
+  // Value binning (xf_bin.hip): bin = "13:32,14:16": a listed numeric field's nonzero gives up its
+  // value for the key of the equal-frequency bucket the value falls into, on the GPU, between the
+  // slices and the cross: slices and held-row groups are named by the raw input key, the cross,
+  // admission, the norm and the model see the bucket keys.  Before epoch 0 the host reader goes
+  // over the training file once (at most bin_fit_rows rows, in whole blocks; 0: all of it) and the
+  // stage counts and fits; with model_in the LUTs come from <model>.bins and nothing is fitted.
+  // Empty = off, nothing is created.  Needs feature_values=on, core_num 1, key_build=gpu,
+  // parity=exact, not ingest=gpu, one worker (checked where training starts).
+  std::string bin_spec;
+  long bin_fit_rows = 0;
   // Progressive validation (xf_progress.hip): progress = 1: every training step counts its rows'
   // losses — formed under the weights the step is about to change — on the GPU, with no host wait
   // inside an epoch; at the end of each epoch (replayed ones included) the counts are read, merged
@@ -217,12 +227,19 @@ class Worker {
   xf_rownorm *norm_ = nullptr;  // row_norm=l2: the stage, created with the tables
   int check_rownorm() const;    // the refusals of row_norm, before any rendezvous
   int create_rownorm();
+  xf_bin *bin_ = nullptr;  // bin=SPEC: the stage, created with the tables
+  int check_bin() const;   // the refusals of bin, before any rendezvous
+  int create_bin();
+  int fit_bins();          // the pass over the training file before epoch 0 (not after a load)
+  uint64_t bin_fit_rows_ = 0, bin_fit_nnz_ = 0;  // what the fit read
+  bool bin_fitted_ = false;                      // fitted here or loaded with a model
   // ---- from a block's rows to its compiled minibatch.  The stages in the order they run:
   // stage_rows IS this order.  Each runs only while its parameter is on.
   enum Stage {
     kSplit,    // holdout: training blocks; the held part leaves the chain here (keep_held)
     kSample,   // neg_keep: training blocks; under the split it numbers the rows of the train part
     kSlices,   // progress_by: training blocks; names the rows before the cross adds nonzeros
+    kBin,      // bin: the held part of holdout enters here, named by its raw keys
     kCross,    // cross
     kAdmit,    // admit_count: counts on training blocks, filters on every block
     kNorm,     // row_norm: over the nonzeros the model receives
